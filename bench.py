@@ -3,7 +3,7 @@
 1024x1024 micrographs, 64x64 patches (BASELINE.json configs[1]: ssdn/gaussian, batch 32 per GPU),
 plus the inference legs (filled whole-micrograph forward + NMS, Mpix/s; configs[2] is the 4096^2 one).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1: either launched by `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...` (RANK /
   WORLD_SIZE in the environment), or started bare: the parent then — before anything touches the GPU — starts that very
   launcher as a child, relays rank 0's JSON line and exits with the child's code (self_launch).
@@ -11,6 +11,12 @@ plus the inference legs (filled whole-micrograph forward + NMS, Mpix/s; configs[
 One step = zero_grad -> Denoiser.run_pipeline(train) (2 JointNetwork passes + sigma net + losses)
 -> backward -> [flat gradient all-reduce over RCCL] -> Adam.  Batches are resident in HBM before the
 timed region.  Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+
+A plain run sets up, warms up, times K steps and reports them.  --full adds every other leg after the timed region:
+kernel-class events and the roofline, host enqueue cost, the sustained rate, replay == eager, the second operand
+precision, batch 16, inference, the full pipeline through the CLI and the CPU baselines.  --dump-outputs DIR writes what
+the last timed step computed as DIR/<name>.npy (step_arrays); the inputs are seeded, so runs with the same arguments see
+the same data.
 """
 import argparse
 import ctypes
@@ -269,6 +275,50 @@ def inference_leg(den, dev, size, reps, keep_picks=None):
                             "(includes the D2H of the picks)"}}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_arrays(o, den, stepper):
+    """What a caller of the timed step holds after its last call, as host arrays: every floating-point tensor of the
+    pipeline's output dictionary (static graph buffers: read before any later step overwrites them), the gradient of
+    every trainable parameter (its slice of the flat buffer, in parameter order) and the model state after the optimiser
+    step (floating-point state_dict tensors in order, each once: parameters and BatchNorm buffers)."""
+    arrays = {}
+    for k, v in o.items():
+        if torch.is_tensor(v) and v.is_floating_point() and v.numel():
+            arrays["out_" + k.name.lower()] = v.detach()
+    views = stepper.grads.views
+    arrays["grad"] = torch.cat([views[p.data_ptr()].reshape(-1) for p in stepper.grads.params])
+    state, seen = [], set()
+    for v in den.state_dict(params_only=True).values():
+        # the same module can be registered under two paths: each tensor once
+        if torch.is_tensor(v) and v.is_floating_point() and (v.data_ptr(), v.numel()) not in seen:
+            seen.add((v.data_ptr(), v.numel()))
+            state.append(v.detach().reshape(-1).float())
+    arrays["state"] = torch.cat(state)
+    return {k: v.cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32, copy=False)
+            for k, v in arrays.items()}
+
+
+def write_dump(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays -> path/<name>.npy.  Above `limit` bytes in all, every array is cut to the same fraction of its elements by
+    a fixed seeded sample (flattened, indices ascending), so two builds still compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    budget = limit - 256 * len(arrays)          # room for the .npy headers
+    info = {}
+    for name, a in arrays.items():
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if total > budget:
+            m = max(1, int(a.size * budget / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, m, replace=False))
+            a = a.reshape(-1)[idx]
+            entry["sampled"] = {"elements": m, "seed": 0}
+        np.save(os.path.join(path, name + ".npy"), a)
+        info[name] = entry
+    return {"dir": path, "bytes": sum(os.path.getsize(os.path.join(path, n + ".npy")) for n in info), "arrays": info}
+
+
 def self_launch(gpus):
     """`python bench.py --gpus N` without a launcher around it: start `torch.distributed.run` with N ranks of this script
     as a CHILD process (this process has not touched the GPU and never will: no exec, nothing to tear down), pass its
@@ -324,11 +374,14 @@ def stub_main(args):
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     dt = float(dt)
     if rank == 0:
-        print(json.dumps({"metric": "train_patches_per_sec", "value": world * batch * args.steps / dt, "unit": "patches/s",
-                          "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-                          "higher_is_better": True, "scaling": "strong" if args.global_batch else "weak", "vs_baseline": None,
-                          "dtype": "stub", "data": "none (SPRK_BENCH_STUB)", "config": {"workload": "stub", "per_gpu_batch": batch,
-                                                                                      "global_batch": batch * world}}), flush=True)
+        out = {"metric": "train_patches_per_sec", "value": world * batch * args.steps / dt, "unit": "patches/s",
+               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+               "higher_is_better": True, "scaling": "strong" if args.global_batch else "weak", "vs_baseline": None,
+               "dtype": "stub", "data": "none (SPRK_BENCH_STUB)", "config": {"workload": "stub", "per_gpu_batch": batch,
+                                                                           "global_batch": batch * world}}
+        if args.dump_outputs:
+            out["dump_outputs"] = write_dump(args.dump_outputs, {"stub_buf": buf.numpy()})
+        print(json.dumps(out), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
 
@@ -362,7 +415,16 @@ def main():
                                                     "--agreement f16 --print-interval 16000")
     ap.add_argument("--infer-size", type=int, default=1024, help="side of the small inference micrograph (0 = skip)")
     ap.add_argument("--infer-large", type=int, default=4096, help="side of the configs[2] micrograph (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region run every other leg too (event steps and roofline, host enqueue cost, "
+                         "sustained rate, replay == eager, --also-dtype, --batch16, inference, --full-pipeline, CPU "
+                         "baselines); the options of those legs act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (pipeline outputs, gradients, model state after the "
+                         "optimiser step) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
     if os.environ.get("SPRK_BENCH_STUB"):
@@ -422,22 +484,25 @@ def main():
     # graph.  (1) two eager steps with every MFMA class bracketed pick the class with the most GPU time; (2) the
     # timed region replays the graphs (that is `value`); (3) right after it `--event-steps` eager steps of the SAME
     # kernels on the same batches are bracketed for the dominant class (the roofline leg) and three more for the
-    # others.  With --graph off the timed region itself is bracketed, as in round 1.
+    # others.  With --graph off the timed region itself is bracketed, as in round 1.  All of that is --full only: a plain
+    # run takes the same eager steps unbracketed as warm-up, so the timed region starts from the same parameters either way.
     step(0, eager=True)   # first touch (code objects, LDS opt-ins, allocator): not part of the class ranking
     fence()
-    L.sprk_prof_enable(31)
+    if args.full:
+        L.sprk_prof_enable(31)
     for i in range(2):
         step(i, eager=True)
     fence()
     L.sprk_prof_enable(0)
     log("eager warm-up done")
-    warm = {kc: collect(kc) for kc in KCLASS}
-    DOM = max(KCLASS, key=lambda kc: warm[kc][1])
+    if args.full:
+        warm = {kc: collect(kc) for kc in KCLASS}
+        DOM = max(KCLASS, key=lambda kc: warm[kc][1])
     stepper.prepare(*batches[0])     # captures both flip-axis graphs (no-op with --graph off)
     for i in range(args.warmup):
         step(i)
     fence()
-    if not use_graph:
+    if not use_graph and args.full:
         L.sprk_prof_enable(1 << DOM)
     launches0 = L.sprk_launch_count()
     t0 = time.perf_counter()
@@ -453,10 +518,64 @@ def main():
     log("timed region done: %.1f ms per step" % (dt / args.steps * 1e3))
     launches = L.sprk_launch_count() - launches0
     last_loss = float(torch.mean(o[P.LOSS].detach()))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = write_dump(args.dump_outputs, step_arrays(o, den, stepper))
+        log("outputs of the last timed step written to %s (%.1f MB)" % (args.dump_outputs, dumped["bytes"] / 1e6))
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+
+    def parallelism_of():
+        return ("dp%d (in-place flat fp32 gradient all-reduce over %s, %d floats%s)" % (
+                    world, distributed.backend_name(), stepper.grads.live_numel,
+                    "; forced 1-rank collective" if world == 1 else "")
+                if stepper.grads.collectives else "single GPU")
+
+    def headline(parallelism):
+        """The fields of the result line a plain run reports too."""
+        value = world * batch * args.steps / dt
+        return {
+            "metric": "train_patches_per_sec", "value": value, "unit": "patches/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": "%s: ssdn --noise_style gaussian --noise_value var, joint mode, "
+                                   "64x64 patches from 4 synthetic 1024x1024 micrographs, batch %d per GPU, alpha 0.75, "
+                                   "tau 0.01, Adam; %s" % (
+                                       "BASELINE configs[3] (global batch %d over %d GPUs, data-parallel, RCCL gradient all-reduce)" % (
+                                           batch * world, world) if (args.global_batch and world > 1) else
+                                       ("BASELINE configs[1] per GPU, weak scaling over %d GPUs" % world if world > 1 else
+                                        "BASELINE configs[1]"), batch, "fp32 MFMA convolutions (Winograd F(2x2,3x3) for the wide 3x3 layers)"
+                                                        if args.dtype == "f32" else
+                                                        "%s-operand MFMA convolutions in the U-Nets where faster, fp32 elsewhere" % args.dtype),
+                       "per_gpu_batch": batch, "global_batch": batch * world, "patch": 64,
+                       "parallelism": parallelism,
+                       "execution": ("forward+backward replayed from 2 HIP graphs (one per flip axis, %d kernels each), eager "
+                                     "all-reduce + one-launch Adam (sprk_adam_multi)" % (stepper.kernels_per_step or 0)) if use_graph
+                                    else "every launch enqueued from Python (--graph off)"},
+            "whole_step_mfma_frac": value / world * FLOP_PER_PATCH_STEP / (PEAK_FP32_MFMA_TFLOPS * 1e12),
+            "whole_step_note": "all algorithmic FLOPs of a step (67.90 GFLOP/patch) / step time / the fp32 direct-convolution "
+                               "MFMA peak",
+            "kernel_launches_per_step": (stepper.kernels_per_step if use_graph else launches / args.steps),
+            "host_launch_calls_per_step": launches / args.steps,
+            "host_cpu_ms_per_step": t_cpu / args.steps * 1e3,
+            "host_enqueue_wall_ms_per_step": t_enq / args.steps * 1e3,
+            "final_loss": last_loss, "kernel_source_hash": kernel_source_hash(),
+            "graph_fallback": stepper.fallback_reason, "full": bool(args.full),
+        }
+
+    if not args.full:
+        par = parallelism_of()
+        fence()
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        if rank == 0:
+            out = headline(par)
+            if dumped:
+                out["dump_outputs"] = dumped
+            print(json.dumps(out), flush=True)
+        return
 
     # host cost of enqueueing a step, measured on an idle queue (nothing to wait for): 6 steps from a synchronised GPU
     fence()
@@ -662,10 +781,7 @@ def main():
     log("batch-16 leg done")
     # the last collective is behind us: every rank leaves the process group NOW, together (a rank that tears RCCL down while
     # rank 0 is still busy with the single-GPU legs would leave rank 0's own teardown waiting for peers that are gone)
-    parallelism = ("dp%d (in-place flat fp32 gradient all-reduce over %s, %d floats%s)" % (
-                       world, distributed.backend_name(), stepper.grads.live_numel,
-                       "; forced 1-rank collective" if world == 1 else "")
-                   if stepper.grads.collectives else "single GPU")
+    parallelism = parallelism_of()
     fence()
     if dist.is_initialized():
         dist.destroy_process_group()
@@ -720,24 +836,8 @@ def main():
                 break
         except (OSError, KeyError, ValueError):
             pass
-    out = {
-        "metric": "train_patches_per_sec", "value": value, "unit": "patches/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": "%s: ssdn --noise_style gaussian --noise_value var, joint mode, "
-                               "64x64 patches from 4 synthetic 1024x1024 micrographs, batch %d per GPU, alpha 0.75, "
-                               "tau 0.01, Adam; %s" % (
-                                   "BASELINE configs[3] (global batch %d over %d GPUs, data-parallel, RCCL gradient all-reduce)" % (
-                                       batch * world, world) if (args.global_batch and world > 1) else
-                                   ("BASELINE configs[1] per GPU, weak scaling over %d GPUs" % world if world > 1 else
-                                    "BASELINE configs[1]"), batch, "fp32 MFMA convolutions (Winograd F(2x2,3x3) for the wide 3x3 layers)"
-                                                    if args.dtype == "f32" else
-                                                    "%s-operand MFMA convolutions in the U-Nets where faster, fp32 elsewhere" % args.dtype),
-                   "per_gpu_batch": batch, "global_batch": batch * world, "patch": 64,
-                   "parallelism": parallelism,
-                   "execution": ("forward+backward replayed from 2 HIP graphs (one per flip axis, %d kernels each), eager "
-                                 "all-reduce + one-launch Adam (sprk_adam_multi)" % (stepper.kernels_per_step or 0)) if use_graph
-                                else "every launch enqueued from Python (--graph off)"},
+    out = headline(parallelism)
+    out.update({
         "roofline": {"bound": "mfma", "kernel": nm, "kernel_note": note,
                      "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
                      "peak_note": "fp32 MFMA dense peak %.1f TF x %.2f (algorithmic FLOPs per issued MFMA FLOP of this "
@@ -749,9 +849,6 @@ def main():
                                        "batches; HIP events cannot bracket nodes inside a replayed graph)" % args.event_steps)
                                       if use_graph else "the timed region",
                      "gpu_time_share_in_warmup": warm[DOM][1] / max(sum(w[1] for w in warm.values()), 1e-9)},
-        "whole_step_mfma_frac": value / world * FLOP_PER_PATCH_STEP / (PEAK_FP32_MFMA_TFLOPS * 1e12),
-        "whole_step_note": "all algorithmic FLOPs of a step (67.90 GFLOP/patch) / step time / the fp32 direct-convolution "
-                           "MFMA peak",
         "other_mfma_kernels": [{"kernel": KCLASS[k][0], "launches": prof[k][0],
                                 "avg_launch_ms": prof[k][1] / max(prof[k][0], 1),
                                 "achieved_tflops": prof[k][2] / (prof[k][1] * 1e-3) / 1e12 if prof[k][1] > 0 else 0.0,
@@ -760,15 +857,11 @@ def main():
                                for k in others],
         "other_mfma_note": "three extra steps after the timed region with every MFMA launch bracketed by events",
         "all_conv_mfma_tflops": all_fl / (all_ms * 1e-3) / 1e12 if all_ms > 0 else 0.0,
-        "kernel_launches_per_step": (stepper.kernels_per_step if use_graph else launches / args.steps),
-        "host_launch_calls_per_step": launches / args.steps,
         "host_enqueue_ms_per_step": t_host * 1e3,
         "host_enqueue_note": "wall time per step until the launching thread has enqueued it, from an idle queue (6 steps)",
-        "host_cpu_ms_per_step": t_cpu / args.steps * 1e3,
-        "host_enqueue_wall_ms_per_step": t_enq / args.steps * 1e3,
-        "final_loss": last_loss, "kernel_source_hash": khash,
-        "graph_fallback": stepper.fallback_reason,
-    }
+    })
+    if dumped:
+        out["dump_outputs"] = dumped
     if sustained:
         out["sustained_patches_per_sec"] = sustained["value"]
         out["sustained"] = sustained

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect the round's profile artefacts on the GPU box (run from the repo root through gpurun):
 #   bash profiles/collect.sh r01
-# runs the bench plain, under the kernel trace and under three PMC passes, then profiles/summarize.py on the
+# runs the whole bench (--full) un-profiled, under the kernel trace and under three PMC passes, then profiles/summarize.py on the
 # databases; gpurun_out/prof_<tag>/summary/ holds the files to copy into profiles/.
 # (PMC passes are separate runs with --kernel-trace only, as MI355X_MICROARCH.md prescribes.)
 # PARTS="16" re-collects only the bf16 passes (the other summaries under profiles/ are kept).
@@ -13,10 +13,10 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
 if [ "$PARTS" = "all" ]; then
-python3 $R/bench.py --cpu-seconds 12 > $OUT/bench.log 2> $OUT/bench.err
+python3 $R/bench.py --full --cpu-seconds 12 > $OUT/bench.log 2> $OUT/bench.err
 grep '^{"metric"' $OUT/bench.log > $OUT/bench.json
 fi
-ARGS="--steps 10 --warmup 3 --no-cpu-baseline --infer-size 0 --infer-large 0 --also-dtype none --graph off --sustain-seconds 0 --batch16 off --full-pipeline off"
+ARGS="--full --steps 10 --warmup 3 --no-cpu-baseline --infer-size 0 --infer-large 0 --also-dtype none --graph off --sustain-seconds 0 --batch16 off --full-pipeline off"
 if [ "$PARTS" = "all" ]; then
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python3 $R/bench.py $ARGS > $OUT/trace.log 2>&1
 grep '^{"metric"' $OUT/trace.log > $OUT/bench_under_rocprof.json

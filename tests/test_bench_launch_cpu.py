@@ -41,3 +41,28 @@ def test_bench_exits_nonzero_when_a_rank_fails():
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert "rank 1 fails on purpose" in r.stderr
+
+
+def test_bench_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs DIR: what the timed step computed lands as DIR/<name>.npy (float32 here), named in the result line."""
+    import numpy as np
+    d = str(tmp_path / "dump")
+    r = _run(["--gpus", "1", "--steps", "2", "--warmup", "0", "--dump-outputs", d])
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0
+    assert sorted(os.listdir(d)) == ["stub_buf.npy"] and j["dump_outputs"]["arrays"]["stub_buf"]["shape"] == [1024]
+    a = np.load(os.path.join(d, "stub_buf.npy"))
+    assert a.dtype == np.float32 and a.shape == (1024,) and np.all(a == 1.0)
+
+
+def test_bench_dump_is_sampled_to_the_size_limit(tmp_path):
+    """Above the limit every array keeps the same share of its elements, by a fixed seeded sample."""
+    import numpy as np
+    import bench
+    arrays = {"a": np.arange(100000, dtype=np.float32), "b": np.arange(50000, dtype=np.float64)}
+    info = [bench.write_dump(str(tmp_path / d), dict(arrays), limit=300000) for d in ("x", "y")]
+    assert info[0]["bytes"] <= 300000 and info[0]["arrays"]["a"]["sampled"]["elements"] < 100000
+    for n in ("a", "b"):
+        x, y = np.load(str(tmp_path / "x" / (n + ".npy"))), np.load(str(tmp_path / "y" / (n + ".npy")))
+        assert x.dtype == arrays[n].dtype and np.array_equal(x, y) and np.all(np.diff(x) > 0)

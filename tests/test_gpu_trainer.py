@@ -260,7 +260,7 @@ def test_rccl_at_world_size_one_bench_and_trainer(tmp_path):
         e.pop("SPRK_DIST_BACKEND", None)
         return e
 
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--infer-size", "0",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--infer-size", "0",
                         "--infer-large", "0", "--no-cpu-baseline", "--also-dtype", "none", "--sustain-seconds", "0",
                         "--batch16", "off", "--event-steps", "1"], env=env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
