@@ -122,13 +122,23 @@ def train_and_eval(ds, work, dtype, args, eval_ds=None):
     from spr_pick_amd.params import ConfigValue
     runs = os.path.join(work, "runs_" + dtype)
     os.environ["SPRK_CONV_DTYPE"] = dtype
+    # loss scaling applies to the f16 runs only: the fp32 / bf16 runs beside them stay the unscaled baselines
+    scaled = args.loss_scale if dtype in ("f16", "fp16") else "off"
     argv = ("train start -a ssdn -n gaussian --noise_value var -t %s -l %s -ap %s -tau %s -iter %d --train_batch_size %d "
             "--nms 18 --bb 24 --runs_dir %s --print_interval %d --checkpoint_interval %d --eval_interval %d" % (
                 ds["images"], ds["labels"], args.alpha, args.tau, args.iterations, args.batch, runs,
                 args.print_interval, args.iterations, args.iterations)).split()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    trainer = cli.start(argv)
+    old = os.environ.get("SPRK_LOSS_SCALE")
+    os.environ["SPRK_LOSS_SCALE"] = scaled
+    try:
+        trainer = cli.start(argv)
+    finally:
+        if old is None:
+            os.environ.pop("SPRK_LOSS_SCALE", None)
+        else:
+            os.environ["SPRK_LOSS_SCALE"] = old
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
     run = trainer.run_dir_path
@@ -145,6 +155,8 @@ def train_and_eval(ds, work, dtype, args, eval_ds=None):
         "loss_last": {k: v[-1][1] for k, v in curve.items() if k.startswith("train/") and "rate" not in k},
         "loss_curve": [(it, round(v, 5)) for it, v in curve.get("train/loss", [])][::max(1, len(curve.get("train/loss", [])) // 24)],
         "detect_loss_curve": [(it, round(v, 5)) for it, v in curve.get("train/detect_loss", [])][::max(1, len(curve.get("train/detect_loss", [])) // 24)],
+        "loss_scale": scaled,
+        "noise_std_last": curve["train/noise_std"][-1][1] if curve.get("train/noise_std") else None,
     }}
     del trainer
     torch.cuda.empty_cache()
@@ -197,11 +209,19 @@ def main(argv=None, quiet=False):
     ap.add_argument("--agreement", default="f16",
                     help="evaluate the fp32-trained checkpoint once more with these MFMA operands and report the agreement of "
                          "the two pick sets (none = skip)")
+    ap.add_argument("--loss-scale", default="off",
+                    help="off | dynamic | a power of two: loss scaling of the f16 training runs (SPRK_LOSS_SCALE); other "
+                         "operand types train unscaled")
     ap.add_argument("--print-interval", type=int, default=3200)
     ap.add_argument("--match-radius", type=float, default=12.0, help="--bb / 2")
     ap.add_argument("--work", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    from spr_pick_amd import graph_step
+    try:
+        graph_step.parse_loss_scale(args.loss_scale)
+    except ValueError as e:
+        ap.error(str(e))
     work = args.work or tempfile.mkdtemp(prefix="sprk_full_")
     from spr_pick_amd import synthetic
     t0 = time.perf_counter()

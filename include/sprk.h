@@ -108,7 +108,7 @@ typedef struct sprk_conv_epilogue {
  * entry points exist).  A binding must refuse a library whose sprk_version() differs from the header it was
  * written against, and may compare sprk_struct_bytes(0 | 1 | 2) with its own sizeof(sprk_conv_geom |
  * sprk_conv_epilogue | sprk_reduce_item). */
-#define SPRK_ABI_VERSION 410
+#define SPRK_ABI_VERSION 420
 const char *sprk_last_error(void);
 int sprk_version(void);
 size_t sprk_struct_bytes(int which);
@@ -345,6 +345,24 @@ typedef struct sprk_adam_item {
 int sprk_adam_multi(const sprk_adam_item *items, const int *start, int n_items, int n_blocks,
                     const float *lr, const float *step_in, float *step_out,
                     float beta1, float beta2, float eps, void *stream);
+/* sprk_adam_multi for a loss-scaled step: skip = the device flag of sprk_unscale_check.  skip[0] != 0: p, m, v are not
+ * touched and step_out[0] = step_in[0]; skip[0] == 0: exactly sprk_adam_multi. */
+int sprk_adam_multi_skip(const sprk_adam_item *items, const int *start, int n_items, int n_blocks,
+                         const float *lr, const float *step_in, float *step_out,
+                         float beta1, float beta2, float eps, const int *skip, void *stream);
+
+/* ---- dynamic loss scaling (torch.amp.GradScaler's rule, every value in device memory) ------------------------------
+ * sprk_unscale_check: x[0 .. n) *= inv_scale[0] in place (any length, any 4-byte alignment); found_nonfinite[0] is
+ * set to 1 (never cleared) when a result is +-inf or NaN.
+ * sprk_loss_scale_update: reads found_nonfinite[0] (one thread):
+ *   set:   scale *= backoff, growth_tracker = 0, skipped += 1
+ *   clear: growth_tracker += 1; when it reaches `interval`: scale *= growth (if finite), growth_tracker = 0
+ * then inv_scale = 1 / scale and next_found[0] = 0 (the flag of the next step: the flag is double-buffered, so no
+ * launch both reads and clears the same flag; next_found != found_nonfinite). */
+int sprk_unscale_check(float *x, long n, const float *inv_scale, int *found_nonfinite, void *stream);
+int sprk_loss_scale_update(float *scale, float *inv_scale, int *growth_tracker, int *skipped,
+                           const int *found_nonfinite, int *next_found, float growth, float backoff, int interval,
+                           void *stream);
 /* SSDN likelihood + posterior mean (denoiser_v2.py:405-424 noise model, :449-462 likelihood, :514 mean):
  *   var_x = A^2, var_y = var_x + var_n
  *   style SPRK_NOISE_GAUSSIAN: s = noise_std[b],                       var_n = s^2

@@ -97,6 +97,9 @@ _SIGS = {
     "sprk_reparam_fwd": (c_i, [c_f, c_f, c_f, c_i, c_i, c_vp]),
     "sprk_reparam_bwd": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_vp]),
     "sprk_adam_multi": (c_i, [c_vp, c_vp, c_i, c_i, c_f, c_f, c_f, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp]),
+    "sprk_adam_multi_skip": (c_i, [c_vp, c_vp, c_i, c_i, c_f, c_f, c_f, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp, c_vp]),
+    "sprk_unscale_check": (c_i, [c_f, ctypes.c_long, c_f, c_vp, c_vp]),
+    "sprk_loss_scale_update": (c_i, [c_f, c_f, c_vp, c_vp, c_vp, c_vp, ctypes.c_float, ctypes.c_float, c_i, c_vp]),
     "sprk_pu_loss": (c_i, [c_f, c_f, c_f, c_i, ctypes.c_float, c_f, c_f, c_vp]),
     "sprk_sigmoid_clamp_fwd": (c_i, [c_f, c_f, ctypes.c_long, c_vp]),
     "sprk_sigmoid_clamp_bwd": (c_i, [c_f, c_f, c_f, ctypes.c_long, c_vp]),
@@ -113,7 +116,7 @@ _SIGS = {
 }
 
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 410          # SPRK_ABI_VERSION of the include/sprk.h these signatures were written against
+ABI_VERSION = 420          # SPRK_ABI_VERSION of the include/sprk.h these signatures were written against
 _lib = None
 
 

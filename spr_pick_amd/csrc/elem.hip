@@ -738,12 +738,20 @@ int ssdn_nblk(int HW) { return HW <= 16384 ? 1 : std::min(64, sprk::cdiv(HW, kSs
 
 
 // ---- Adam over many parameter tensors in one launch --------------------------------------------------------------
+// kSkip: the loss-scaled variant (sprk_adam_multi_skip): a set device flag (a non-finite gradient, scale.hip) leaves
+// p, m, v and the step count as they are; otherwise the update is the plain one, instruction for instruction.
+template <bool kSkip>
 __global__ __launch_bounds__(256) void adam_multi_kernel(const sprk_adam_item *__restrict__ items,
                                                          const int *__restrict__ start, int n_items,
                                                          const float *__restrict__ lr, const float *__restrict__ step_in,
-                                                         float *__restrict__ step_out, float b1, float b2, float eps) {
-    // workgroup -> item: binary search in the start table (wave-uniform)
+                                                         float *__restrict__ step_out, float b1, float b2, float eps,
+                                                         const int *__restrict__ skip) {
     const int b = blockIdx.x;
+    if (kSkip && skip[0] != 0) {
+        if (b == 0 && threadIdx.x == 0) step_out[0] = step_in[0];     // the step count is double-buffered: carry it
+        return;
+    }
+    // workgroup -> item: binary search in the start table (wave-uniform)
     int lo = 0, hi = n_items - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -919,9 +927,19 @@ int sprk_adam_multi(const sprk_adam_item *items, const int *start, int n_items, 
                     const float *step_in, float *step_out, float beta1, float beta2, float eps, void *stream) {
     SPRK_REQUIRE(items && start && n_items > 0 && n_blocks > 0 && lr && step_in && step_out && step_in != step_out,
                  "adam_multi: bad arguments");
-    hipLaunchKernelGGL(adam_multi_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, items, start, n_items, lr,
-                       step_in, step_out, beta1, beta2, eps);
+    hipLaunchKernelGGL(adam_multi_kernel<false>, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, items, start, n_items,
+                       lr, step_in, step_out, beta1, beta2, eps, nullptr);
     return sprk::check_launch("adam_multi");
+}
+
+int sprk_adam_multi_skip(const sprk_adam_item *items, const int *start, int n_items, int n_blocks, const float *lr,
+                         const float *step_in, float *step_out, float beta1, float beta2, float eps,
+                         const int *skip, void *stream) {
+    SPRK_REQUIRE(items && start && n_items > 0 && n_blocks > 0 && lr && step_in && step_out && step_in != step_out && skip,
+                 "adam_multi_skip: bad arguments");
+    hipLaunchKernelGGL(adam_multi_kernel<true>, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, items, start, n_items,
+                       lr, step_in, step_out, beta1, beta2, eps, skip);
+    return sprk::check_launch("adam_multi_skip");
 }
 
 int sprk_pu_loss(const float *p, const float *y, const float *log_binom, int B, float slack, float *loss, float *gp,

@@ -18,6 +18,7 @@ The all-reduce and the Adam update stay outside the graphs (eager): Adam is ONE 
 (``MultiAdam`` / ``sprk_adam_multi``) with the step count and the learning rate in device scalars, so the ramp
 needs no re-capture and no host sync.
 """
+import math
 import os
 
 import numpy as np
@@ -190,7 +191,9 @@ class MultiAdam:
         self._table = (raw.to(self.dev), torch.from_numpy(start).to(self.dev), len(live), int(start[-1]))
         self._started.update(live)
 
-    def step(self):
+    def step(self, scaler=None):
+        """scaler: a ``LossScaler`` whose ``unscale_`` ran on this step's gradients — the update is skipped on the
+        device (parameters, moments and step count untouched) when its flag says a gradient is not finite."""
         live = [i for i, p in enumerate(self.params) if p.grad is not None]
         if not live:
             return
@@ -200,9 +203,16 @@ class MultiAdam:
             self._key = key
         items, start, n, blocks = self._table
         src, dst = self._steps[self._cur], self._steps[1 - self._cur]
-        _lib.check(_lib.lib().sprk_adam_multi(items.data_ptr(), start.data_ptr(), n, blocks, self.lr.data_ptr(), src.data_ptr(),
-                                              dst.data_ptr(), self.betas[0], self.betas[1], self.eps,
-                                              torch.cuda.current_stream(self.dev).cuda_stream), "sprk_adam_multi")
+        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        if scaler is None:
+            _lib.check(_lib.lib().sprk_adam_multi(items.data_ptr(), start.data_ptr(), n, blocks, self.lr.data_ptr(),
+                                                  src.data_ptr(), dst.data_ptr(), self.betas[0], self.betas[1], self.eps,
+                                                  stream), "sprk_adam_multi")
+        else:
+            _lib.check(_lib.lib().sprk_adam_multi_skip(items.data_ptr(), start.data_ptr(), n, blocks, self.lr.data_ptr(),
+                                                       src.data_ptr(), dst.data_ptr(), self.betas[0], self.betas[1],
+                                                       self.eps, scaler.found_nonfinite.data_ptr(), stream),
+                       "sprk_adam_multi_skip")
         self._cur = 1 - self._cur
 
     def zero_grad(self, set_to_none=True):
@@ -241,6 +251,126 @@ class MultiAdam:
             raise ValueError("MultiAdam: parameters with different step counts (%s)" % sorted(steps))
         self._steps[self._cur].fill_(steps.pop() if steps else 0.0)
         self._key = None
+
+
+LOSS_SCALE_ENV = "SPRK_LOSS_SCALE"
+
+
+def parse_loss_scale(spec):
+    """``SPRK_LOSS_SCALE`` / ``--loss-scale``: "off" (or empty / None) -> None, "dynamic" -> "dynamic", a positive
+    power of two ("65536", "2**16", "0.5") -> that float (a static scale).  Anything else raises ValueError: a scale
+    that is not a power of two would change the gradients' rounding, not only their range."""
+    if spec is None:
+        return None
+    if not isinstance(spec, str):
+        spec = repr(spec)
+    t = spec.strip().lower()
+    if t in ("", "off", "none", "0"):
+        return None
+    if t == "dynamic":
+        return "dynamic"
+    try:
+        v = float(2.0 ** float(t[3:])) if t.startswith("2**") else float(t)
+    except (ValueError, OverflowError):
+        raise ValueError("loss scale %r: expected off, dynamic or a power of two" % spec) from None
+    if not (math.isfinite(v) and v > 0 and math.frexp(v)[0] == 0.5):
+        raise ValueError("loss scale %r: a static scale must be a positive, finite power of two" % spec)
+    return v
+
+
+class LossScaler:
+    """Dynamic loss scaling with torch.amp.GradScaler's rule, kept entirely on the device so that the step needs no
+    host sync and the forward + backward stay one replayed graph.
+
+    The loss is multiplied by ``scale`` (a device scalar read by the captured pass, ``GraphedTrainStep(scaler=)``).
+    After the all-reduce, three launches: ``unscale_`` multiplies the flat gradient by ``1 / scale`` and raises a
+    device flag on inf / NaN (``sprk_unscale_check``); ``MultiAdam.step(scaler)`` skips the update when the flag is
+    up (``sprk_adam_multi_skip``); ``update`` applies the schedule — backoff and restart on a skipped step, growth
+    after ``growth_interval`` clean steps — counts skipped steps and clears the flag of the next step
+    (``sprk_loss_scale_update``; the flag is double-buffered like MultiAdam's step count).
+
+    ``dynamic=False``: a static scale (a power of two) that never changes; overflowing steps are still skipped and
+    counted.  ``state_dict()`` uses GradScaler's key names (plus ``skipped_steps`` and ``dynamic``)."""
+
+    def __init__(self, device, init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000,
+                 dynamic=True):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("LossScaler runs on the GPU only")
+        if parse_loss_scale(float(init_scale)) is None:
+            raise ValueError("LossScaler: init_scale %r is not a positive power of two" % (init_scale,))
+        if int(growth_interval) <= 0:
+            raise ValueError("LossScaler: growth_interval must be positive")
+        self.dev, self.dynamic = dev, bool(dynamic)
+        self.growth_factor, self.backoff_factor = float(growth_factor), float(backoff_factor)
+        self.growth_interval = int(growth_interval)
+        self.scale = torch.full((1,), float(init_scale), dtype=torch.float32, device=dev)
+        self.inv_scale = torch.full((1,), 1.0 / float(init_scale), dtype=torch.float32, device=dev)
+        self.growth_tracker = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.skipped = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._found = torch.zeros(2, dtype=torch.int32, device=dev)
+        self._cur = 0                 # half of the flag buffer that belongs to the current step
+
+    @classmethod
+    def from_spec(cls, spec, device):
+        """A scaler for ``parse_loss_scale(spec)``, or None when scaling is off."""
+        v = parse_loss_scale(spec)
+        if v is None:
+            return None
+        return cls(device) if v == "dynamic" else cls(device, init_scale=v, dynamic=False)
+
+    @property
+    def found_nonfinite(self):
+        """Device int32 [1]: nonzero when this step's unscaled gradient holds an inf or NaN."""
+        return self._found[self._cur:self._cur + 1]
+
+    def unscale_(self, grads):
+        """grads: a ``FlatGrads`` (its live prefix) or a contiguous fp32 device tensor, unscaled in place."""
+        flat = grads.flat[:grads.live_numel] if isinstance(grads, FlatGrads) else grads
+        if not (flat.is_cuda and flat.dtype == torch.float32 and flat.is_contiguous()):
+            raise _lib.SprkError("LossScaler.unscale_: needs a contiguous fp32 device tensor")
+        if flat.numel() == 0:
+            return
+        _lib.check(_lib.lib().sprk_unscale_check(flat.data_ptr(), flat.numel(), self.inv_scale.data_ptr(),
+                                                 self.found_nonfinite.data_ptr(),
+                                                 torch.cuda.current_stream(self.dev).cuda_stream), "sprk_unscale_check")
+
+    def update(self):
+        growth, backoff = (self.growth_factor, self.backoff_factor) if self.dynamic else (1.0, 1.0)
+        nxt = 1 - self._cur
+        _lib.check(_lib.lib().sprk_loss_scale_update(self.scale.data_ptr(), self.inv_scale.data_ptr(),
+                                                     self.growth_tracker.data_ptr(), self.skipped.data_ptr(),
+                                                     self.found_nonfinite.data_ptr(), self._found[nxt:nxt + 1].data_ptr(),
+                                                     growth, backoff, self.growth_interval,
+                                                     torch.cuda.current_stream(self.dev).cuda_stream),
+                   "sprk_loss_scale_update")
+        self._cur = nxt
+
+    def get_scale(self):
+        """The current scale as a Python float (synchronises: logging only)."""
+        return float(self.scale)
+
+    def skipped_steps(self):
+        return int(self.skipped)
+
+    def state_dict(self):
+        return {"scale": self.get_scale(), "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor,
+                "growth_interval": self.growth_interval, "_growth_tracker": int(self.growth_tracker),
+                "skipped_steps": self.skipped_steps(), "dynamic": self.dynamic}
+
+    def load_state_dict(self, sd):
+        if not sd:
+            raise ValueError("LossScaler: empty state dict")
+        self.growth_factor = float(sd.get("growth_factor", self.growth_factor))
+        self.backoff_factor = float(sd.get("backoff_factor", self.backoff_factor))
+        self.growth_interval = int(sd.get("growth_interval", self.growth_interval))
+        self.dynamic = bool(sd.get("dynamic", self.dynamic))
+        sc = float(sd["scale"])
+        self.scale.fill_(sc)
+        self.inv_scale.fill_(1.0 / sc)
+        self.growth_tracker.fill_(int(sd.get("_growth_tracker", 0)))
+        self.skipped.fill_(int(sd.get("skipped_steps", 0)))
+        self._found.zero_()
 
 
 def make_adam(params, lr=1e-4, betas=(0.9, 0.99)):
@@ -306,8 +436,9 @@ class GraphedTrainStep:
     same flat gradients) — the path the roofline leg of bench.py brackets with events."""
 
     def __init__(self, denoiser, batch, patch, alpha, tau, world=1, mode="joint", graph=True, eager_warmup=2,
-                 draw_eps=True):
+                 draw_eps=True, scaler=None):
         self.den = denoiser
+        self.scaler = scaler          # LossScaler: the pass multiplies the loss by its device scale
         self.dev = denoiser.device
         self.alpha, self.tau, self.world, self.mode = alpha, tau, world, mode
         self.use_graph = graph
@@ -354,6 +485,8 @@ class GraphedTrainStep:
         loss = torch.mean(o[PipelineOutput.LOSS])
         if self.world > 1:
             loss = loss / self.world
+        if self.scaler is not None:
+            loss = loss * self.scaler.scale.reshape(())     # read at replay time: the schedule needs no re-capture
         loss.backward()
         self.grads.adopt_strays()
         return o

@@ -60,7 +60,7 @@ tensor_to_png = outputs_mod.tensor_to_png      # save_tensor_image (utils/data.p
 
 class DenoiserTrainer:
     def __init__(self, cfg, mode, state=None, runs_dir=cfg_mod.DEFAULT_RUN_DIR, run_dir=None, alpha=0.5, tau=0.01,
-                 bb=32, device=None, seed=0, graph=True):
+                 bb=32, device=None, seed=0, graph=True, loss_scale=None):
         self.runs_dir = os.path.abspath(runs_dir)
         self._run_dir = run_dir
         self.cfg = cfg
@@ -78,6 +78,11 @@ class DenoiserTrainer:
         self._optimizer = None
         self._stepper = None
         self.graph = graph and os.environ.get("SPRK_GRAPH", "1") != "0"
+        # loss scaling (off | dynamic | a power of two): like SPRK_CONV_DTYPE not a flag of the reference's CLI, so the
+        # drop-in command line stays as it is and the choice travels in the environment (SPRK_LOSS_SCALE)
+        self.loss_scale = graph_step.parse_loss_scale(
+            loss_scale if loss_scale is not None else os.environ.get(graph_step.LOSS_SCALE_ENV, "off"))
+        self.scaler = None
         self._metrics_file = None
         self._eval_modes_logged = set()
         self.trainfeed, self.testfeed = None, None
@@ -107,6 +112,9 @@ class DenoiserTrainer:
         params = [p for p in self.denoiser.parameters() if p.requires_grad]
         # Adam(beta = (0.9, 0.99)) as train.py:128-140, fused + capturable (state and learning rate on the device)
         self._optimizer = graph_step.make_adam(params, lr=BASE_LR, betas=(0.9, 0.99))
+        self.scaler = None
+        if self.loss_scale is not None:
+            self.scaler = graph_step.LossScaler.from_spec(self.loss_scale, self.device)
         self._stepper = None      # built at the first training step (needs the per-rank batch shape)
 
     def new_target(self):
@@ -169,6 +177,12 @@ class DenoiserTrainer:
         logger.info(separator())
         logger.info("TRAINING STARTED")
         logger.info(separator())
+        if os.environ.get("SPRK_CONV_DTYPE", "f32").rstrip("!") in ("f16", "fp16") and self.scaler is None:
+            logger.warning("f16 training without loss scaling: gradients below fp16's range are lost and the noise "
+                           "estimator collapses (DESIGN.md 4.10); set SPRK_LOSS_SCALE=dynamic")
+        elif self.scaler is not None:
+            logger.info("loss scaling: %s", "dynamic, initial scale %g" % self.scaler.get_scale() if self.scaler.dynamic
+                        else "static %g" % self.scaler.get_scale())
 
         c = self.cfg
         history = self.state[StateValue.HISTORY]
@@ -209,12 +223,21 @@ class DenoiserTrainer:
             if self._stepper is None:
                 inp0 = data[DetectionDataset.INPUT]
                 self._stepper = graph_step.GraphedTrainStep(denoiser, inp0.shape[0], inp0.shape[-1], self.alpha, self.tau,
-                                                            world=self.world, mode=self.mode, graph=self.graph)
+                                                            world=self.world, mode=self.mode, graph=self.graph,
+                                                            scaler=self.scaler)
             # zero_grad + forward + mean(loss).backward(): replayed from a HIP graph (graph_step.py), the gradients
             # land in one flat buffer; then the in-place all-reduce over the ranks and the Adam update
             outputs = self._stepper(data[DetectionDataset.INPUT], data[DetectionDataset.TARGET])
             self._stepper.grads.all_reduce(self.world)
-            optimizer.step()
+            if self.scaler is None:
+                optimizer.step()
+            else:
+                # unscale + inf/NaN check, skip-aware Adam, schedule: three launches, no host sync.  The ranks agree
+                # without a collective of their own: an inf or NaN on any rank survives the SUM all-reduce above, so
+                # every rank finds it, skips the same step and moves its scale the same way.
+                self.scaler.unscale_(self._stepper.grads)
+                optimizer.step(scaler=self.scaler)
+                self.scaler.update()
 
             with torch.no_grad():
                 train_history["n"] += image_count
@@ -435,8 +458,11 @@ class DenoiserTrainer:
                                                             "model_{:08d}.training".format(iteration)))
 
     def state_dict(self):
-        return {"denoiser": self.denoiser.state_dict(), "state": self.state,
-                "optimizer": self.optimizer.state_dict(), "rng": torch.get_rng_state()}
+        sd = {"denoiser": self.denoiser.state_dict(), "state": self.state,
+              "optimizer": self.optimizer.state_dict(), "rng": torch.get_rng_state()}
+        if self.scaler is not None:
+            sd["scaler"] = self.scaler.state_dict()
+        return sd
 
     def load_state_dict(self, state_dict, restore_optimizer=True):
         if isinstance(state_dict, str):
@@ -450,6 +476,12 @@ class DenoiserTrainer:
                 self._optimizer.load_state_dict(state_dict["optimizer"])
             except ValueError as e:
                 logger.warning("optimizer state not restored: %s", e)
+        if state_dict.get("scaler"):
+            # a loss-scaled run continues loss-scaled, with the scale and growth count it had reached
+            if self.scaler is None:
+                self.loss_scale = "dynamic" if state_dict["scaler"].get("dynamic", True) else float(state_dict["scaler"]["scale"])
+                self.scaler = graph_step.LossScaler(self.device)
+            self.scaler.load_state_dict(state_dict["scaler"])
         torch.set_rng_state(state_dict["rng"])
         self.seed_streams()       # device + NumPy streams (and the patch sampler below) continue, not replay
 
@@ -479,6 +511,9 @@ class DenoiserTrainer:
                     rows.append((prefix + "/" + name, it, float(torch.as_tensor(metric.accumulated()).mean())))
             if prefix == "train":
                 rows.append(("train/learning_rate", it, self.learning_rate))
+                if self.scaler is not None:
+                    rows.append(("train/loss_scale", it, self.scaler.get_scale()))
+                    rows.append(("train/skipped_steps", it, self.scaler.skipped_steps()))
         with open(os.path.join(self.run_dir_path, "metrics.tsv"), "a") as f:
             for tag, i, v in rows:
                 f.write("%s\t%d\t%.9g\n" % (tag, i, v))
@@ -498,6 +533,8 @@ class DenoiserTrainer:
         eta_str = "???" if not isinstance(eta, int) else ("<1s" if eta < 1 else seconds_to_dhms(eta))
         summary = "[{:08d}] {:>5} | ".format(self.state[StateValue.ITERATION], "TRAIN")
         strs = self._metric_strs(history[HistoryValue.TRAIN])
+        if self.scaler is not None:      # device scalars: read at print intervals only
+            strs.append("loss_scale={:g}, skipped_steps={:d}".format(self.scaler.get_scale(), self.scaler.skipped_steps()))
         summary += ", ".join(strs)
         if strs:
             summary += " | "
