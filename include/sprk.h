@@ -108,7 +108,7 @@ typedef struct sprk_conv_epilogue {
  * entry points exist).  A binding must refuse a library whose sprk_version() differs from the header it was
  * written against, and may compare sprk_struct_bytes(0 | 1 | 2) with its own sizeof(sprk_conv_geom |
  * sprk_conv_epilogue | sprk_reduce_item). */
-#define SPRK_ABI_VERSION 420
+#define SPRK_ABI_VERSION 430   /* 430: sprk_contam_* */
 const char *sprk_last_error(void);
 int sprk_version(void);
 size_t sprk_struct_bytes(int which);
@@ -411,6 +411,27 @@ size_t sprk_nms2d_ws_bytes(int H, int W, int max_out);
 int sprk_nms2d(const float *scores, int H, int W, int r, float threshold,
                float *out_scores, int32_t *out_xy, int32_t *out_count, int max_out,
                int rounds, int resume, void *ws, size_t ws_bytes, void *stream);
+
+/* ---- contamination mask ----------------------------------------------------------------
+ * replaces find_contamination(out_img) — utils/algorithms.py:24-57 (the reference never calls it:
+ * train.py:583 passes contam = set() to the NMS).  img [H,W] fp32 device: the un-padded denoised
+ * micrograph.  The reference's constants are the defaults: crop 3, ksize 5, k_low 1.5, k_high 2.0,
+ * radius 15.  Min-max normalisation to uint8, ksize x ksize box blur of img[crop:H-crop, crop:W-crop]
+ * (reflect-101 inside the crop), seeds = blurred pixels below mean - k_low*std or above
+ * mean + k_high*std of the whole uint8 image, each seed's clipped disk of `radius` added as the flat
+ * index clip(i+di,0,Hb)*Wb + clip(j+dj,0,Wb)  (Hb = H-2crop, Wb = W-2crop): the set C.
+ *   mask_out [H,W] uint8 device: 1 at (f / Wb + crop, f % Wb + crop) for every f in C — the score
+ *       map's frame (the reference would read f in a W-wide frame; this is the deviation);
+ *   set_bitmap_out (nullable) uint8[(Hb+1)*Wb + 1] device: 1 at every f in C (the reference's frame);
+ *   stats_out double[8] device: min, max (finite pixels; NaN if there is none), mean, std of the
+ *       uint8 image, the two thresholds, the number of seeds, the number of mask pixels.
+ * Constraints: crop >= 2, H, W >= 2*crop+1, ksize odd <= 15, 0 <= radius <= 31.  Non-finite pixels:
+ * NaN -> 0, +-inf -> 255 / 0 after normalisation by the finite range.  Several launches on `stream`,
+ * no host synchronisation. */
+size_t sprk_contam_ws_bytes(int H, int W);
+int sprk_contam_mask(const float *img, int H, int W, int crop, int ksize, double k_low, double k_high, int radius,
+                     uint8_t *mask_out, uint8_t *set_bitmap_out, double *stats_out, void *ws, size_t ws_bytes,
+                     void *stream);
 
 /* ---- in-library kernel timing (bench.py's roofline leg) --------------------------------
  * sprk_prof_enable(mask): bit k set = every launch of kernel class k is bracketed by HIP events

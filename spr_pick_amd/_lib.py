@@ -108,6 +108,9 @@ _SIGS = {
     "sprk_ssdn_bwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
     "sprk_nms2d_ws_bytes": (c_sz, [c_i, c_i, c_i]),
     "sprk_nms2d": (c_i, [c_f, c_i, c_i, c_i, ctypes.c_float, c_f, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
+    "sprk_contam_ws_bytes": (c_sz, [c_i, c_i]),
+    "sprk_contam_mask": (c_i, [c_f, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_vp, c_vp, c_vp, c_vp, c_sz,
+                               c_vp]),
     "sprk_gather_patches": (c_i, [c_vp, c_i, c_vp, c_vp, c_vp, c_f, c_i, c_i, c_i, c_vp]),
     "sprk_prof_enable": (None, [c_i]),
     "sprk_prof_collect": (c_i, [c_i, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
@@ -116,7 +119,7 @@ _SIGS = {
 }
 
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 420          # SPRK_ABI_VERSION of the include/sprk.h these signatures were written against
+ABI_VERSION = 430          # SPRK_ABI_VERSION of the include/sprk.h these signatures were written against
 _lib = None
 
 

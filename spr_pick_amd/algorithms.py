@@ -1,10 +1,10 @@
-"""Drop-in for ``spr_pick.utils.algorithms.non_maximum_suppression`` (utils/algorithms.py:59-103)
-running on the GPU (libsprk.so: sprk_nms2d)."""
+"""Drop-ins for ``spr_pick.utils.algorithms.non_maximum_suppression`` (utils/algorithms.py:59-103) and
+``find_contamination`` (utils/algorithms.py:24-57) running on the GPU (libsprk.so: sprk_nms2d, sprk_contam_mask)."""
 import numpy as np
 import torch
 
 from . import _lib
-from . import torch_ops  # noqa: F401  (registers torch.ops.sprk.nms2d)
+from . import torch_ops  # noqa: F401  (registers torch.ops.sprk.nms2d / contam_mask)
 
 ROUNDS_PER_CALL = 12
 
@@ -83,3 +83,52 @@ def non_maximum_suppression(x, r, contam=None, threshold=-np.inf):
         xc = np.clip(c[:, 0:1].astype(np.int64) + dj[None, :], 0, W)
         contam.update(np.unique(yc * W + xc).tolist())
     return s, c
+
+
+# find_contamination's constants (utils/algorithms.py:28-37): crop of the blurred region, blur size, the two seed
+# thresholds in standard deviations, disk radius
+CONTAM_PARAMS = dict(crop=3, ksize=5, k_low=1.5, k_high=2.0, radius=15)
+CONTAM_STATS = ("min", "max", "mean", "std", "thr_low", "thr_high", "seeds", "masked")
+
+
+def _contam(img, set_bitmap, params):
+    p = dict(CONTAM_PARAMS)
+    unknown = set(params) - set(p)
+    if unknown:
+        raise TypeError("unknown contamination parameter(s): %s" % ", ".join(sorted(unknown)))
+    p.update(params)
+    if isinstance(img, np.ndarray):
+        img = torch.from_numpy(np.ascontiguousarray(img, dtype=np.float32)).cuda()
+    if not img.is_cuda or img.dtype != torch.float32:
+        raise _lib.SprkError("contamination_mask expects a float32 CUDA tensor (or a NumPy array)")
+    while img.dim() > 2 and img.shape[0] == 1:
+        img = img[0]
+    if img.dim() != 2:
+        raise _lib.SprkError("contamination_mask expects a 2-D map, got shape %s" % (tuple(img.shape),))
+    img = img.contiguous()
+    H, W = img.shape
+    if set_bitmap is not None:
+        Hb, Wb = H - 2 * p["crop"], W - 2 * p["crop"]
+        set_bitmap = torch.empty((Hb + 1) * Wb + 1, dtype=torch.uint8, device=img.device)
+    stats = torch.empty(len(CONTAM_STATS), dtype=torch.float64, device=img.device)
+    mask = torch.ops.sprk.contam_mask(img, p["crop"], p["ksize"], p["k_low"], p["k_high"], p["radius"], set_bitmap, stats)
+    return mask, set_bitmap, stats
+
+
+def contamination_mask(img, stats=False, **params):
+    """Contamination mask of a denoised micrograph ``img`` ([H,W] float32, CUDA tensor or NumPy array) in the frame of
+    the score map that shares img's frame: bool CUDA tensor [H,W], True where the reference's find_contamination
+    (run on img) would suppress picks, the index set placed as DESIGN §4 states.  ``params`` override CONTAM_PARAMS.
+    No host synchronisation.  stats=True also returns a float64 CUDA tensor of CONTAM_STATS."""
+    mask, _, st = _contam(img, None, params)
+    mask = mask.view(torch.bool)
+    return (mask, st) if stats else mask
+
+
+def find_contamination(out_img, **params):
+    """Drop-in for the reference's find_contamination(out_img): the set of flat indices it returns, in its own frame
+    (row-major over the blurred crop, Wb = W - 6 wide, clip bounds Hb / Wb; largest index (Hb+1)*Wb).  Handing this
+    set to non_maximum_suppression reproduces the reference's own (frame-skewed) use; the evaluation path uses
+    contamination_mask instead."""
+    _, bitmap, _ = _contam(out_img, True, params)
+    return set(torch.nonzero(bitmap).view(-1).cpu().tolist())

@@ -63,6 +63,9 @@ def build_parser():
     ev.add_argument("--gt_dataset", "-g", help="ground truth image")
     ev.add_argument("--nms", "-nms", type=int, help="non maximum suppression radius")
     ev.add_argument("--num", "-num", type=int, default=10, help="Number of micrographs to evaluate")
+    ev.add_argument("--contamination", action="store_true",
+                    help="exclude picks on ice contamination, carbon edges and holes (the reference's find_contamination, "
+                         "computed on the GPU); writes {name}_contam.png")
     return parser
 
 
@@ -110,7 +113,7 @@ def run_train(args, parser):
 
 def run_eval(args):
     from .eval import DenoiserEvaluator
-    evaluator = DenoiserEvaluator(args["model"], runs_dir=args["runs_dir"])
+    evaluator = DenoiserEvaluator(args["model"], runs_dir=args["runs_dir"], contamination=args.get("contamination", False))
     for flag, key in (("batch_size", ConfigValue.TEST_MINIBATCH_SIZE), ("nms", ConfigValue.NMS),
                       ("num", ConfigValue.NUM_EVAL)):
         if args.get(flag) is not None:

@@ -1,7 +1,9 @@
 """``DenoiserEvaluator`` — ``joint eval`` (eval.py:29-144 of the reference): load a ``.training`` or
 ``.wt`` file, run every requested micrograph through the filled network and write, per micrograph,
 the image outputs and ``{name}_scores.txt`` into ``<runs_dir>/%05d-eval-<cfg>/eval_imgs``.
-With WORLD_SIZE > 1 micrograph i is processed by rank i % world; there is no collective."""
+With WORLD_SIZE > 1 micrograph i is processed by rank i % world; there is no collective.
+``contamination=True`` (``--contamination``) masks each micrograph's contamination before its NMS and writes
+``{name}_contam.png``."""
 import logging
 import os
 
@@ -17,8 +19,8 @@ logger = logging.getLogger("joint.eval")
 
 
 class DenoiserEvaluator(DenoiserTrainer):
-    def __init__(self, target_path, runs_dir=cfg_mod.DEFAULT_RUN_DIR, run_dir=None, device=None):
-        super().__init__({}, "joint", runs_dir=runs_dir, run_dir=run_dir, device=device)
+    def __init__(self, target_path, runs_dir=cfg_mod.DEFAULT_RUN_DIR, run_dir=None, device=None, contamination=False):
+        super().__init__({}, "joint", runs_dir=runs_dir, run_dir=run_dir, device=device, contamination=contamination)
         state_dict = checkpoint.load(target_path)
         if "denoiser" in state_dict:
             self.load_state_dict(state_dict, restore_optimizer=False)

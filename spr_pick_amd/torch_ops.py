@@ -495,6 +495,22 @@ _register("nms2d", "(Tensor score, int r, float threshold, Tensor(a!) out_s, Ten
                    "int rounds, int resume, Tensor(d!) ws) -> ()", _nms2d, lambda *a: None)
 
 
+# ---- contamination mask (algorithms.contamination_mask / find_contamination) -----------------------------------------------
+def _contam_mask(img, crop, ksize, k_low, k_high, radius, set_bitmap, stats):
+    L = _lib.lib()
+    H, W = img.shape
+    mask = torch.empty((H, W), dtype=torch.uint8, device=img.device)
+    ws = _ws(L.sprk_contam_ws_bytes(H, W), img)
+    check(L.sprk_contam_mask(_p(img), H, W, int(crop), int(ksize), float(k_low), float(k_high), int(radius), _p(mask),
+                             _p(set_bitmap), _p(stats), _p(ws), ws.numel(), _stream(img)), "sprk_contam_mask")
+    return mask
+
+
+_register("contam_mask", "(Tensor img, int crop, int ksize, float k_low, float k_high, int radius, Tensor(a!)? set_bitmap, "
+                         "Tensor(b!) stats) -> Tensor", _contam_mask,
+          lambda img, *a: img.new_empty(tuple(img.shape), dtype=torch.uint8))
+
+
 def registered():
     """Names of the operators under torch.ops.sprk (tests)."""
     return tuple(_NAMES)

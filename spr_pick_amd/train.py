@@ -32,7 +32,7 @@ import torch
 
 from . import cfg as cfg_mod
 from . import checkpoint, distributed, feed as feed_mod, graph_step, outputs as outputs_mod, picks
-from .algorithms import nms_device
+from .algorithms import CONTAM_STATS, contamination_mask, nms_device
 from .datasets import DetectionDataset
 from .denoiser import Denoiser
 from .params import ConfigValue, DatasetType, HistoryValue, Pipeline, PipelineOutput, StateValue
@@ -60,7 +60,7 @@ tensor_to_png = outputs_mod.tensor_to_png      # save_tensor_image (utils/data.p
 
 class DenoiserTrainer:
     def __init__(self, cfg, mode, state=None, runs_dir=cfg_mod.DEFAULT_RUN_DIR, run_dir=None, alpha=0.5, tau=0.01,
-                 bb=32, device=None, seed=0, graph=True, loss_scale=None):
+                 bb=32, device=None, seed=0, graph=True, loss_scale=None, contamination=False):
         self.runs_dir = os.path.abspath(runs_dir)
         self._run_dir = run_dir
         self.cfg = cfg
@@ -83,6 +83,9 @@ class DenoiserTrainer:
         self.loss_scale = graph_step.parse_loss_scale(
             loss_scale if loss_scale is not None else os.environ.get(graph_step.LOSS_SCALE_ENV, "off"))
         self.scaler = None
+        # contamination-aware picking (joint eval --contamination): a run option like the loss scale, never stored in
+        # cfg or a checkpoint (params.py stays pickle-compatible with the reference)
+        self.contamination = bool(contamination)
         self._metrics_file = None
         self._eval_modes_logged = set()
         self.trainfeed, self.testfeed = None, None
@@ -436,9 +439,26 @@ class DenoiserTrainer:
             self.writer.png(unpad(t), path(fileformat, desc))
         if PipelineOutput.DETECT in outputs and scoreformat is not None:
             score_map = unpad(outputs[PipelineOutput.DETECT])[0].contiguous()
+            contam = None
+            if self.contamination:
+                # find_contamination on the un-padded denoised map (the reference computes and drops it, train.py:583):
+                # masked pixels leave the NMS as -inf, which the walk never reaches before the threshold stops it
+                if PipelineOutput.IMG_DENOISED not in outputs:
+                    raise RuntimeError("contamination-aware picking needs the denoised image (IMG_DENOISED)")
+                den = unpad(outputs[PipelineOutput.IMG_DENOISED])[0]
+                if tuple(den.shape) != tuple(score_map.shape):
+                    raise RuntimeError("denoised image %s and score map %s do not share a frame"
+                                       % (tuple(den.shape), tuple(score_map.shape)))
+                mask, contam = contamination_mask(den.to(torch.float32), stats=True)
+                score_map = score_map.masked_fill(mask, float("-inf"))
+                self.writer.png(mask[None].to(torch.float32), path(fileformat, "contam"))
             scores, coords = nms_device(score_map, self.cfg[ConfigValue.NMS], NMS_THRESHOLD)
             self.writer.call(picks.write_scores, path(scoreformat, "scores"), name, scores.cpu().numpy(),
                              coords.cpu().numpy(), tuple(score_map.shape))
+            if contam is not None:
+                st = dict(zip(CONTAM_STATS, contam.tolist()))
+                logger.info("%s: contamination mask excludes %.3f%% of the score map (%d seeds)", name,
+                            100.0 * st["masked"] / score_map.numel(), int(st["seeds"]))
 
     # ---- checkpoints ---------------------------------------------------------------------------
     def snapshot(self, output_name=None, subdir=None, model_only=False):
