@@ -68,22 +68,13 @@ def loss_curve(run_dir):
     return rows
 
 
-def patch_level_detection(wt, ds, dtype, n_per_class=256, seed=0):
-    """Does the DETECTOR itself separate particles from background?  Unfilled eval-mode forward (running BatchNorm
-    statistics, the training geometry: 64x64 patches) on patches centred on planted particles and on background positions
-    of the evaluation set: AUC of the scores + recall / false-positive rate at the exporter's threshold 0.13.  Independent
-    of how the blind-spot U-Net's output level carries over from 64x64 training patches to whole micrographs, which the
-    pick-level figures depend on as well (DESIGN.md, full pipeline)."""
-    import torch
-    from spr_pick_amd import DetectionDataset, checkpoint, micrograph_io
-    from spr_pick_amd.denoiser import Denoiser
-    from spr_pick_amd.params import PipelineOutput as P
+def detection_patches(ds, n_per_class=256, seed=0):
+    """The 64x64 patches patch_level_detection scores: centred on planted particles and on background positions (no
+    planted centre within 24 px) of the first 8 micrographs of ``ds``, n_per_class / 8 of each per micrograph.
+    -> (pos, neg): lists of float32 arrays, transposed as the tensors enter the network (row = x)."""
+    from spr_pick_amd import micrograph_io
     truth = read_truth(ds["truth"])
     rows = micrograph_io.read_image_table(ds["images"])[:8]
-    den = Denoiser.from_state_dict(checkpoint.load(wt), mode="joint", device="cuda:0")
-    if dtype != "f32":
-        den.set_conv_dtype(dtype)
-    den.eval(); den.unfill()
     rng = np.random.default_rng(seed)
     pos, neg = [], []
     for _, name, path in rows:
@@ -96,6 +87,24 @@ def patch_level_detection(wt, ds, dtype, n_per_class=256, seed=0):
             x, y = rng.integers(80, img.shape[0] - 80, size=2)
             if ((cen - (x, y)) ** 2).sum(axis=1).min() > 24 ** 2:
                 neg.append(img[x - 31:x + 33, y - 31:y + 33]); k += 1
+    return pos, neg
+
+
+def patch_level_detection(wt, ds, dtype, n_per_class=256, seed=0):
+    """Does the DETECTOR itself separate particles from background?  Unfilled eval-mode forward (running BatchNorm
+    statistics, the training geometry: 64x64 patches) on patches centred on planted particles and on background positions
+    of the evaluation set: AUC of the scores + recall / false-positive rate at the exporter's threshold 0.13.  Independent
+    of how the blind-spot U-Net's output level carries over from 64x64 training patches to whole micrographs, which the
+    pick-level figures depend on as well (DESIGN.md, full pipeline)."""
+    import torch
+    from spr_pick_amd import DetectionDataset, checkpoint
+    from spr_pick_amd.denoiser import Denoiser
+    from spr_pick_amd.params import PipelineOutput as P
+    pos, neg = detection_patches(ds, n_per_class, seed)
+    den = Denoiser.from_state_dict(checkpoint.load(wt), mode="joint", device="cuda:0")
+    if dtype != "f32":
+        den.set_conv_dtype(dtype)
+    den.eval(); den.unfill()
     scores = []
     gen = torch.Generator(device="cuda:0").manual_seed(1)
     with torch.no_grad():

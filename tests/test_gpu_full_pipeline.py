@@ -14,15 +14,32 @@ a BatchNorm on a signal of variance 6e-4 sits behind it); runs are deterministic
 only when the arithmetic does — it did in round 4: the 6 000-step configuration pinned until then stopped writing picks
 in fp32 when the small-plane convolutions changed their summation order, 8 000 and 10 000 steps give AP 0.92 in fp32 and
 mixed16 (scratch/r4/fp_variants.sh).  The patch-level figures below are the robust statement."""
+import glob
+import os
+
+import numpy as np
 import pytest
+import torch
+
+import oracle_parity
 
 pytestmark = pytest.mark.gpu
 
 
-def test_trained_model_recovers_the_planted_particles(tmp_path):
+@pytest.fixture(scope="module")
+def trained(tmp_path_factory):
+    """The one training run of this module: full_pipeline.main's output, its work dir, the fp32 run's final weights."""
     import full_pipeline
+    work = tmp_path_factory.mktemp("full_pipeline")
     out = full_pipeline.main(["--micrographs", "16", "--iterations", "160000", "--batch", "16", "--dtypes", "f32",
-                              "--agreement", "f16", "--print-interval", "16000", "--work", str(tmp_path)])
+                              "--agreement", "f16", "--print-interval", "16000", "--work", str(work)])
+    wts = glob.glob(os.path.join(str(work), "runs_f32", "**", "final-*.wt"), recursive=True)
+    assert len(wts) == 1, wts
+    return out, str(work), wts[0]
+
+
+def test_trained_model_recovers_the_planted_particles(trained):
+    out, _, _ = trained
     run = out["runs"]["f32"]
     train, ev = run["train"], run["eval"]
     # the trainer's loop ran the graph-replayed step (no silent eager fallback) and learnt
@@ -50,3 +67,258 @@ def test_trained_model_recovers_the_planted_particles(tmp_path):
     assert agree["0.13"]["jaccard"] >= 0.95 and agree["0.5"]["jaccard"] >= 0.95, agree
     m16 = out["fp32_checkpoint_evaluated_with_f16_operands"]["picks_vs_planted_centres"]
     assert abs(m16["average_precision"] - m["average_precision"]) <= 0.01, (m16["average_precision"], m["average_precision"])
+
+
+# ---- HIP against the fp64 oracle at the TRAINED weights (independent of the pick-level outcome above) ----------------
+# The trajectory test stays near the initial weights; a trained checkpoint is another regime (detector.m
+# normalises a signal of running variance ~6e-4, sigma-net outputs at their floor, saturated scores).  Every comparison
+# below is ONE forward (+ backward) pass on the same parameters and inputs, a local statement: the fp64 oracle is the
+# reference, the fp32 oracle's own deviation from it the yardstick of tests/oracle_parity.py where a tensor is that
+# ill-conditioned.
+
+TRAIN_KEYS = ("LOSS", "DENOISE_LOSS", "DETECT_LOSS", "AUG_LOSS", "DETECT", "IMG_MU", "NOISE_STD_DEV")
+EVAL_KEYS = ("IMG_MU", "IMG_DENOISED", "DETECT", "MODEL_STD_DEV", "NOISE_STD_DEV", "LOSS")
+
+
+def _checkpoint(wt):
+    from spr_pick_amd import checkpoint
+    ck = checkpoint.load(wt)
+    sd = {k[len("models."):]: v for k, v in ck.items() if k.startswith("models.") and torch.is_tensor(v)}
+    return ck, sd
+
+
+def _oracle_state(sd, dt, grad=False):
+    out = {k: (v.detach().clone().to(dt) if v.is_floating_point() else v.clone()) for k, v in sd.items()}
+    if grad:
+        for k, v in out.items():
+            if v.is_floating_point() and "running" not in k:
+                v.requires_grad_(True)
+    return out
+
+
+def _micrograph(work, k):
+    from spr_pick_amd import micrograph_io
+    import full_pipeline
+    root = os.path.join(work, "set")
+    _, name, path = micrograph_io.read_image_table(os.path.join(root, "images.txt"))[k]
+    img = micrograph_io.to_unit_float(micrograph_io.load_image(path)).T      # tensors enter transposed: row = x
+    return name, np.ascontiguousarray(img), full_pipeline.read_truth(os.path.join(root, "truth.txt"))[name], \
+        full_pipeline.read_truth(os.path.join(root, "labels.txt")).get(name, np.zeros((0, 2), np.int64))
+
+
+def _lazy(fn):
+    """fn() evaluated once, on first use: the fp32 oracle is only needed where the base rule fails."""
+    memo = []
+    return lambda: memo[0] if memo else (memo.append(fn()) or memo[0])
+
+
+def _fmt(r):
+    return "%.1e" % r["err"] + ("" if r["err32"] is None else " (fp32 oracle %.1e)" % r["err32"])
+
+
+def _outputs_against(got, ref, ref32, keys, rel, what, bad):
+    """ref32: a callable returning the fp32 oracle's dict.  -> (report rows, number of outputs on the yardstick branch);
+    a failing output is appended to ``bad``."""
+    rows, n_yard = {}, 0
+    for k in keys:
+        r = oracle_parity.output_report(got[k], ref[k], lambda k=k: ref32()[k], rel=rel.get(k, 1e-4))
+        rows[k] = r
+        if not r["ok"]:
+            bad.append("%s %s: %s of max|value|" % (what, k, _fmt(r)))
+        n_yard += r["yardstick"]
+    return rows, n_yard
+
+
+def test_trained_train_step_matches_the_fp64_oracle(trained):
+    """One joint train step per flip axis at the trained checkpoint, replayed through GraphedTrainStep (the production
+    path) and once eagerly, against oracle.pipeline.joint_pipeline in fp64: the losses and outputs at the golden
+    train-step budgets, EVERY parameter gradient through tests/oracle_parity.py, the BatchNorm running buffers after the
+    step; replay and eager bit for bit."""
+    from oracle import pipeline as opipe
+    from spr_pick_amd import graph_step
+    from spr_pick_amd.denoiser import Denoiser
+    from spr_pick_amd.params import PipelineOutput as P
+    _, work, wt = trained
+    ck, sd = _checkpoint(wt)
+    name, img, centres, labelled = _micrograph(work, 0)
+    S = img.shape[0]
+    inside = lambda c: [(int(x), int(y)) for x, y in c if 31 <= x <= S - 33 and 31 <= y <= S - 33]
+    lab = inside(labelled)
+    unl = [c for c in inside(centres) if c not in set(lab)]
+    rng = np.random.default_rng(2)
+    while True:                                                    # a background position, no planted centre within 24 px
+        bg = tuple(int(v) for v in rng.integers(80, S - 80, size=2))
+        if ((centres - bg) ** 2).sum(axis=1).min() > 24 ** 2:
+            break
+    at = [lab[0], lab[1], unl[0], bg]
+    B = len(at)
+    inp = torch.from_numpy(np.stack([img[x - 31:x + 33, y - 31:y + 33] for x, y in at])[:, None].copy())
+    tgt = torch.tensor([[1.0], [1.0], [-1.0], [-1.0]])               # two labelled positives, two unlabelled
+    g = torch.Generator().manual_seed(17)
+    eps, epf = torch.randn(B, 1, 64, 64, generator=g), torch.randn(B, 1, 64, 64, generator=g)
+
+    den = Denoiser.from_state_dict(ck, mode="joint", device="cuda:0")
+    den.train(); den.unfill()
+    reload = {k: v for k, v in ck.items() if k != "cfg"}
+    st = graph_step.GraphedTrainStep(den, B, 64, 0.75, 0.01, draw_eps=False, eager_warmup=1)
+    st.prepare(inp.cuda(), tgt, eps.cuda(), epf.cuda())
+    assert set(st._graphs) == {"w", "h"} and st.fallback_reason is None
+
+    def run(flip, eager):
+        den.load_state_dict(reload, strict=False)                  # every pass advances the BatchNorm running buffers
+        o = st(inp.cuda(), tgt, flip_p=flip, eps=eps.cuda(), eps_flip=epf.cuda(), eager=eager)
+        out = {k: o[getattr(P, k)].detach().clone() for k in TRAIN_KEYS}
+        grads = {n: (None if p.grad is None else p.grad.detach().clone()) for n, p in den.models.named_parameters()}
+        bufs = {k[len("models."):]: v.detach().clone() for k, v in den.state_dict().items()
+                if torch.is_tensor(v) and k.startswith("models.") and "running_" in k}
+        return out, grads, bufs
+
+    def oracle(flip, dt):
+        s = _oracle_state(sd, dt, grad=True)
+        r = opipe.joint_pipeline(s, inp.to(dt), tgt.to(dt), 0.75, 0.01, True, eps.to(dt), epf.to(dt), flip)
+        r["LOSS"].mean().backward()
+        grads = {k: (None if v.grad is None else v.grad.detach()) for k, v in s.items()
+                 if v.is_floating_point() and "running" not in k}
+        return ({k: r[k].detach() for k in TRAIN_KEYS}, grads,
+                {k: v.detach() for k, v in s.items() if "running_" in k})
+
+    n_grad_yard = n_out_yard = 0
+    bad = []
+    for flip in (0.3, 0.7):
+        out, grads, bufs = run(flip, eager=False)
+        out_e, grads_e, bufs_e = run(flip, eager=True)
+        for k in TRAIN_KEYS:
+            assert torch.equal(out[k], out_e[k]), "flip %.1f: replayed %s != eager" % (flip, k)
+        for n in grads:
+            assert (grads[n] is None) == (grads_e[n] is None) and (grads[n] is None or torch.equal(grads[n], grads_e[n])), \
+                "flip %.1f: replayed gradient of %s != eager" % (flip, n)
+        for n in bufs:
+            assert torch.equal(bufs[n], bufs_e[n]), "flip %.1f: BatchNorm buffer %s: replay != eager" % (flip, n)
+        ref, ref_g, ref_b = oracle(flip, torch.float64)
+        ref32 = _lazy(lambda: oracle(flip, torch.float32))
+        rows, ny = _outputs_against(out, ref, lambda: ref32()[0], TRAIN_KEYS, {"AUG_LOSS": 1e-3}, "flip %.1f" % flip, bad)
+        n_out_yard += ny
+        rep = oracle_parity.grad_report(grads, ref_g, lambda: ref32()[1])
+        print("trained train step, flip %.1f: outputs %s" % (flip, {k: _fmt(r) for k, r in rows.items()}))
+        print("  gradients: " + oracle_parity.summary(rep))
+        bad += ["flip %.1f: %s" % (flip, f) for f in rep["failures"]]
+        n_grad_yard = max(n_grad_yard, len(rep["yardstick"]))
+        brows, ny = _outputs_against(bufs, ref_b, lambda: ref32()[2], sorted(ref_b), {}, "flip %.1f BatchNorm" % flip, bad)
+        n_out_yard += ny
+        print("  BatchNorm buffers: worst %.1e" % max(r["err"] for r in brows.values()))
+    assert not bad, "; ".join(bad)
+    # measured on MI355X at this checkpoint: no tensor and no output needs the fp32 yardstick.  Outputs within 8.1e-6 of
+    # max|value| (DETECT; AUG_LOSS 7.5e-5 against its 1e-3), BatchNorm buffers within 1.0e-5; gradients: 0 of 2 106 950
+    # elements beyond 1e-3 of max|g|, worst tensors at 4.9e-5 of max|g| (encode_block_1.0) apart from detector.m, the
+    # BatchNorm before a BatchNorm whose true gradient is zero (1.1e-2 of a max|g| near 0, inside the 1e-4 floor)
+    assert n_grad_yard == 0, n_grad_yard
+    assert n_out_yard == 0, n_out_yard
+
+
+def _filled(den):
+    den.eval(); den.fill()
+    return den
+
+
+def test_trained_inference_matches_the_fp64_oracle(trained):
+    """(a) filled eval of a 512^2 crop of a training micrograph: every output against the fp64 oracle; (b) the unfilled
+    eval-mode scores of 32 particle-centred and 32 background patches (as patch_level_detection picks them); (c) the HIP
+    NMS on the HIP map equals the C oracle on that map bit for bit, and the picks on the HIP map differ from those on the
+    oracle's map only where tests/pickdiff.py finds a near-tie or threshold cause."""
+    import full_pipeline
+    import pickdiff
+    from oracle import nms as onms
+    from oracle import pipeline as opipe
+    from spr_pick_amd import DetectionDataset, nms_device
+    from spr_pick_amd.denoiser import Denoiser
+    from spr_pick_amd.params import PipelineOutput as P
+    _, work, wt = trained
+    ck, sd = _checkpoint(wt)
+    den = _filled(Denoiser.from_state_dict(ck, mode="joint", device="cuda:0"))
+    _, img, _, _ = _micrograph(work, 1)
+    crop = torch.from_numpy(img[256:768, 256:768].copy())[None, None]
+    eps = torch.randn(crop.shape, generator=torch.Generator().manual_seed(5))
+    with torch.no_grad():
+        o = den.run_pipeline(DetectionDataset.make_batch(crop.cuda(), torch.zeros(1, 1)), train=False, eps=eps.cuda())
+        got = {k: o[getattr(P, k)].detach().clone() for k in EVAL_KEYS}
+        ref = opipe.joint_pipeline(_oracle_state(sd, torch.float64), crop.double(), None, 0, 0, False, eps.double())
+    ref32 = _lazy(lambda: opipe.joint_pipeline(_oracle_state(sd, torch.float32), crop, None, 0, 0, False, eps))
+    bad = []
+    with torch.no_grad():
+        rows, n_yard = _outputs_against(got, ref, ref32, EVAL_KEYS, {}, "filled 512^2", bad)
+    print("trained filled eval 512^2: %s" % {k: _fmt(r) for k, r in rows.items()})
+
+    # (b) the detector in its training geometry, eval mode (running statistics)
+    ds = {"truth": os.path.join(work, "set", "truth.txt"), "images": os.path.join(work, "set", "images.txt")}
+    pos, neg = full_pipeline.detection_patches(ds, n_per_class=32, seed=0)
+    assert len(pos) == len(neg) == 32
+    x = torch.from_numpy(np.stack(pos + neg)[:, None].astype(np.float32))
+    e2 = torch.randn(x.shape, generator=torch.Generator().manual_seed(6))
+    den.unfill()
+    with torch.no_grad():
+        o2 = den.run_pipeline(DetectionDataset.make_batch(x.cuda(), torch.zeros(len(x), 1)), train=False, eps=e2.cuda())
+        p_hip = o2[P.DETECT].detach().reshape(-1).clone()
+        want = lambda dt: opipe.joint_pipeline(_oracle_state(sd, dt), x.to(dt), None, 0, 0, False, e2.to(dt),
+                                               filled=False)["DETECT"].reshape(-1)
+        want64 = want(torch.float64)
+        r2 = oracle_parity.output_report(p_hip, want64, lambda: want(torch.float32))
+    sp, sn = want64[:32].numpy(), want64[32:].numpy()
+    print("trained unfilled patches: %s of max|score|; oracle medians particle %.3f background %.3f" % (
+        _fmt(r2), np.median(sp), np.median(sn)))
+    if not r2["ok"]:
+        bad.append("unfilled patch scores: %s" % r2)
+    n_yard += r2["yardstick"]
+
+    # (c) picks
+    m = got["DETECT"][0, 0].contiguous()
+    want_map = ref["DETECT"][0, 0].float().numpy()
+    s, c = nms_device(m, 18, 0.02)
+    s_c, c_c = onms.nms_c(m.cpu().numpy(), 18, 0.02)
+    assert len(s_c) > 0, "the trained model gives no picks on the 512^2 crop: nothing to compare"
+    assert np.array_equal(c.cpu().numpy(), c_c) and np.array_equal(s.cpu().numpy(), s_c)
+    s_ref, c_ref = onms.nms_c(want_map, 18, 0.02)
+    e = pickdiff.explain(want_map, m.cpu().numpy(), c_ref, c_c, 18, 0.02)
+    jac = e["jaccard"] if len(c_ref) or len(c_c) else 1.0
+    print("trained 512^2 picks: %d (oracle map %d); %d + %d differ, causes %s; agreement %.4f; max |score diff| %.2e" % (
+        len(s_c), len(s_ref), len(e["a_only"]), len(e["b_only"]), e["roots"][:4], jac, e["delta"]))
+    assert not bad, "; ".join(bad)
+    assert jac >= 0.98
+    # measured on MI355X at this checkpoint: filled outputs within 4.2e-6 of max|value| (MODEL_STD_DEV; fp32 oracle 2.5e-6),
+    # DETECT 3.0e-6 (fp32 oracle 2.8e-6); unfilled patch scores 2.0e-6 (1.2e-6); 114 picks, identical to the picks on the
+    # oracle's map: no output needs the fp32 yardstick
+    assert n_yard == 0, n_yard
+
+
+def test_trained_score_map_nms_with_resumed_calls(trained, monkeypatch):
+    """One full 1024^2 score map of the trained model: the device NMS with one round per call (every round after the
+    first is a resumed, re-sorting call) and with the default ROUNDS_PER_CALL both equal the C oracle bit for bit."""
+    from oracle import nms as onms
+    from spr_pick_amd import DetectionDataset, _lib, algorithms, nms_device
+    from spr_pick_amd.denoiser import Denoiser
+    from spr_pick_amd.params import PipelineOutput as P
+    _, work, wt = trained
+    ck, _ = _checkpoint(wt)
+    den = _filled(Denoiser.from_state_dict(ck, mode="joint", device="cuda:0"))
+    _, img, _, _ = _micrograph(work, 2)
+    x = torch.from_numpy(img)[None, None].cuda()
+    eps = torch.randn(x.shape, device="cuda", generator=torch.Generator(device="cuda").manual_seed(7))
+    with torch.no_grad():
+        m = den.run_pipeline(DetectionDataset.make_batch(x, torch.zeros(1, 1)), train=False, eps=eps)[P.DETECT][0, 0].clone()
+    den.unfill()
+    s_c, c_c = onms.nms_c(m.cpu().numpy(), 18, 0.02)
+    assert len(s_c) > 0, "the trained model gives no picks on the 1024^2 map: nothing to compare"
+    # the map needs resumed calls: one round leaves pixels undecided (same workspace and call as nms_device's first)
+    L, cap = _lib.lib(), algorithms._max_picks(*m.shape, 18)
+    out_s = torch.empty(cap, dtype=torch.float32, device=m.device)
+    out_xy = torch.empty((cap, 2), dtype=torch.int32, device=m.device)
+    cnt = torch.zeros(2, dtype=torch.int32, device=m.device)
+    ws = torch.empty(L.sprk_nms2d_ws_bytes(*m.shape, cap), dtype=torch.uint8, device=m.device)
+    torch.ops.sprk.nms2d(m, 18, 0.02, out_s, out_xy, cnt, 1, 0, ws)
+    n1, undecided = cnt.tolist()
+    assert 0 < n1 <= len(s_c) and undecided > 0, (n1, undecided, len(s_c))
+    for rounds in (algorithms.ROUNDS_PER_CALL, 1):
+        monkeypatch.setattr(algorithms, "ROUNDS_PER_CALL", rounds)
+        s, c = nms_device(m, 18, 0.02)
+        assert np.array_equal(c.cpu().numpy(), c_c) and np.array_equal(s.cpu().numpy(), s_c), rounds
+    print("trained 1024^2 map: %d picks (%d decided in the first round, %d pixels left undecided), identical to the C "
+          "oracle with 12 and with 1 round(s) per call" % (len(s_c), n1, undecided))

