@@ -35,6 +35,13 @@ inline int check_launch(const char *what) {
     return SPRK_OK;
 }
 
+// SPRK_EWORKSPACE (and the error text) when the caller's workspace is missing or shorter than `need`
+inline int check_ws(const char *who, const void *ws, size_t ws_bytes, size_t need) {
+    if (ws && ws_bytes >= need) return SPRK_OK;
+    set_error("%s: workspace %zu < %zu", who, ws_bytes, need);
+    return SPRK_EWORKSPACE;
+}
+
 // second-stage sums (sprk_reduce_items); item == nullptr in the callers below means "finish now"
 int reduce_items(const sprk_reduce_item *items, int n, hipStream_t s);
 inline int finish_or_defer(const sprk_reduce_item &it, sprk_reduce_item *out, hipStream_t s) {
@@ -74,6 +81,11 @@ inline int ew_blocks(long n, int threads = 256) {
     return (int)b;
 }
 
+// algorithmic (direct-convolution) FLOPs of a layer: the same for its forward, backward-data and backward-weight call
+inline double conv_flops(const sprk_conv_geom &g) {
+    return 2.0 * g.N * g.Hout * g.Wout * (double)g.Cout * (g.C1 + g.C2) * g.KH * g.KW;
+}
+
 }  // namespace sprk
 
 // XCD-aware start slot of a persistent workgroup.  Workgroups are dispatched round-robin over the 8 XCDs (id % 8), each
@@ -85,20 +97,25 @@ __device__ __forceinline__ int xcd_slot(int id, int nwg, int on) {
     return (id & 7) * (nwg >> 3) + (id >> 3);
 }
 namespace sprk {
-// Timing experiments that switch phases of a kernel OFF (the results are then wrong on purpose: SPRK_WG_DIAG,
-// SPRK_C16_DIAG, SPRK_NMS_DIAG, SPRK_WINO_DIAG).  They exist only in a library built with -DSPRK_DIAG
-// (make DIAG=1); the shipped libsprk.so ignores the variables, so an inherited environment cannot corrupt a run.
-inline int diag_env(const char *name) {
+// Every environment variable the library reads goes through these two, and both are alive only in a library built with
+// -DSPRK_DIAG (make DIAG=1); the shipped libsprk.so ignores the variables, so an inherited environment cannot corrupt a
+// run.
+// Selection and sweep knobs (SPRK_WINO, SPRK_CONV16, SPRK_FWD_NTBLK, SPRK_XCD, ...): which kernel takes a call and how
+// it is tiled, hence the summation order of the result.
+inline int knob_env(const char *name, int dflt) {
 #ifdef SPRK_DIAG
     const char *v = getenv(name);
-    return v ? atoi(v) : 0;
+    return v ? atoi(v) : dflt;
 #else
     (void)name;
-    return 0;
+    return dflt;
 #endif
 }
+// Timing experiments that switch phases of a kernel OFF (the results are then wrong on purpose: SPRK_WG_DIAG,
+// SPRK_C16_DIAG, SPRK_NMS_DIAG, SPRK_WINO_DIAG).
+inline int diag_env(const char *name) { return knob_env(name, 0); }
 inline int xcd_on() {
-    static const int on = getenv("SPRK_XCD") ? atoi(getenv("SPRK_XCD")) : 1;   // debug: 0 = plain round-robin order
+    static const int on = knob_env("SPRK_XCD", 1);   // 0 = plain round-robin order
     return on;
 }
 }  // namespace sprk

@@ -33,9 +33,6 @@ namespace {
 // per-call switch: SPRK_DT_NAIVE in sprk_conv_geom.dtype routes the call to the plain (non-MFMA) kernels
 inline bool naive_of(const sprk_conv_geom *g) { return (g->dtype & SPRK_DT_NAIVE) != 0; }
 
-constexpr int kClass16 = 5;   // profiling class of the 16-bit-operand forward / backward-data kernel (conv16.hip)
-constexpr int kClass16W = 6;  // ... of the 16-bit-operand backward-weight kernel (wgrad16.hip)
-
 // ------------------------------------------------------------------------------------------
 // weight transform:  W[Cout][Cin][KHW]  ->  Wt[nblk][rows][ldw]   (rows = k in chunked order)
 //   mode 0 (forward):        GEMM-k channel = cin,  n = cout, tap as is
@@ -1030,11 +1027,6 @@ __global__ void concat_up_bwd_kernel(const float *__restrict__ gin, float *__res
 // ------------------------------------------------------------------------------------------
 constexpr size_t kLdsLimit = 160 * 1024;
 
-int dbg_int(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 struct FwdPlan {
     int MT, NT, lgTC, lgTR, tilesX, tilesY, imgGroups, nblkN;
     int CK, R4, rows;
@@ -1062,8 +1054,9 @@ int pick_nt(int ntile) {
 }
 
 // Ck: channels along GEMM-k; Nn: GEMM-n extent; output spatial dims Ho x Wo over Nimg images
-bool plan_fwd(int Nimg, int Ck, int Nn, int Ho, int Wo, int KH, int KW, int stride, int dil, int padL, int up1,
-              int hasC2, int WinSrc, FwdPlan *p) {
+bool plan_fwd(const sprk::Corr &c, FwdPlan *p) {
+    const int Nimg = c.N, Ck = c.C1 + c.C2, Nn = c.Cout, Ho = c.Hout, Wo = c.Wout, KH = c.KH, KW = c.KW;
+    const int stride = c.stride, dil = c.dil, padL = c.padL, up1 = c.up1, hasC2 = c.C2 > 0, WinSrc = c.Win;
     const int KHW = KH * KW;
     const int ntile = sprk::cdiv(Nn, 16);
     int NT = pick_nt(ntile);
@@ -1097,7 +1090,7 @@ bool plan_fwd(int Nimg, int Ck, int Nn, int Ho, int Wo, int KH, int KW, int stri
         MT >>= 1;
         blocks = geometry(MT, NT);
     }
-    static const int kNtBlocks = dbg_int("SPRK_FWD_NTBLK", 512);   // debug knob (sweeps)
+    static const int kNtBlocks = sprk::knob_env("SPRK_FWD_NTBLK", 512);   // sweeps
     while (blocks < kNtBlocks && NT > 1) {
         NT = (NT == 6) ? 3 : (NT == 4) ? 2 : 1;
         blocks = geometry(MT, NT);
@@ -1199,11 +1192,26 @@ int launch_fwd(const ConvArgs &a, const FwdPlan &p, hipStream_t s) {
 }
 
 bool aligned16(const void *p) {
-    static const bool novec = getenv("SPRK_NOVEC") != nullptr;  // debug: force the 4-byte DMA path
+    static const bool novec = sprk::knob_env("SPRK_NOVEC", 0) != 0;  // 1 = force the 4-byte DMA path
     return !novec && (((uintptr_t)p) & 15) == 0;
 }
 
-void fill_args(ConvArgs &a, const FwdPlan &p) {
+// conv_mfma_kernel's argument block for correlation c under plan p; wsf: the call's workspace (zero block, then the
+// transformed weights)
+ConvArgs conv_args(const sprk::Corr &c, const FwdPlan &p, const float *x, const float *x2, float *wsf, float *y) {
+    ConvArgs a{};
+    a.x = x; a.x2 = x2; a.zeros = wsf; a.wT = wsf + kZeroFloats;
+    a.bias = c.ep.bias; a.scale = c.ep.scale; a.shift = c.ep.shift; a.res = c.ep.res;
+    a.y = y;
+    a.N = c.N; a.C1 = c.C1; a.C2 = c.C2; a.Hin = c.Hin; a.Win = c.Win; a.up1 = c.up1;
+    a.H1 = c.up1 ? c.Hin / 2 : c.Hin;
+    a.W1 = c.up1 ? c.Win / 2 : c.Win;
+    a.Cout = c.Cout; a.Hout = c.Hout; a.Wout = c.Wout;
+    a.KH = c.KH; a.KW = c.KW; a.stride = c.stride; a.dil = c.dil; a.padT = c.padT; a.padL = c.padL;
+    a.act = c.ep.act;
+    a.resH = c.ep.res_h; a.resW = c.ep.res_w; a.resOff = c.ep.res_off;
+    a.up2 = c.ep.up2;
+    a.vec4 = (c.Wout % 4 == 0) && (p.lgTC >= 2) && (((uintptr_t)y & 15) == 0);
     a.lgTC = p.lgTC;
     a.lgTR = p.lgTR;
     a.tilesX = p.tilesX;
@@ -1230,11 +1238,12 @@ void fill_args(ConvArgs &a, const FwdPlan &p) {
     const long NIm1 = p.NI - 1;
     const bool small1 = (NIm1 * a.C1 + 1) * a.H1 * a.W1 < (1L << 29) && (long)a.CK * a.H1 * a.W1 < (1L << 29);
     const bool small2 = (NIm1 * a.C2 + 1) * a.Hin * a.Win < (1L << 29) && (long)a.CK * a.Hin * a.Win < (1L << 29);
-    static const int tabmode = dbg_int("SPRK_XTAB", 2);   // debug: 0 = pointer-arithmetic staging, 1 = not for 1x1
+    static const int tabmode = sprk::knob_env("SPRK_XTAB", 2);   // 0 = pointer-arithmetic staging, 1 = not for 1x1
     const bool want = tabmode == 2 || (tabmode == 1 && a.KH * a.KW > 1);
     a.xtab = (p.xtab && want && small1 && small2 && (a.up1 || a.vec1) && (a.C2 == 0 || a.vec2)) ? 1 : 0;
     a.nG1 = p.nG1;
     a.nG2 = p.nG2;
+    return a;
 }
 
 int transform_weights(const float *w, float *ws, int Cout, int Cin, int KHW, int mode, const FwdPlan &p,
@@ -1319,7 +1328,7 @@ bool plan_wgrad(const sprk_conv_geom *g, WgPlan *p) {
     // tiles that is proportional to chunks x k-tiles, the total work; with few tiles (the U-Net levels <= 16x16: every
     // workgroup has one tile whatever the split) it is the k-tiles alone, so small planes are cut into more, shorter
     // chunks on more CUs (96->96 at 64x8x8: 2 chunks of 7 k-tiles per wave -> 4 of 4).
-    static const int kWgKnob = dbg_int("SPRK_WG_BLOCKS", 0);   // debug knob (sweeps); default: one workgroup per CU
+    static const int kWgKnob = sprk::knob_env("SPRK_WG_BLOCKS", 0);   // sweeps; default: one workgroup per CU
     const int kWgBlocks = kWgKnob > 0 ? kWgKnob : sprk::num_cus();
     int CKW = 0;
     long bestCost = 1L << 60;
@@ -1390,64 +1399,12 @@ int launch_wg(const WgArgs &a, const WgPlan &p, dim3 grid, hipStream_t s) {
     return SPRK_EINVAL;
 }
 
-// Winograd path (wino.hip): geometry of the forward layer / of its backward-data correlation
-sprk::WinoGeom wino_geom_fwd(const sprk_conv_geom *g, const sprk_conv_epilogue *ep) {
-    return sprk::WinoGeom{g->N, g->C1, g->C2, g->Cout, g->Hin, g->Win, g->Hout, g->Wout, g->KH, g->KW, g->stride, g->dil,
-                          g->pad_top, g->pad_left, g->up1, ep ? ep->up2 : 0, (ep && ep->res) ? 1 : 0, (g->dtype & SPRK_DT_PIN) ? 1 : 0};
+// the calls whose activation tensors are 16-bit tensors (SPRK_DT_X16 / SPRK_DT_Y16) end here when no 16-bit kernel took them
+int check_storage32(const char *who, int dtype) {
+    SPRK_REQUIRE(!(dtype & (SPRK_DT_X16 | SPRK_DT_Y16)),
+                 "%s: no kernel takes this geometry with 16-bit activation tensors (ask sprk_conv2d_storage16 first)", who);
+    return SPRK_OK;
 }
-sprk::WinoGeom wino_geom_bwd(const sprk_conv_geom *g) {
-    return sprk::WinoGeom{g->N, g->Cout, 0, g->C1 + g->C2, g->Hout, g->Wout, g->Hin, g->Win, g->KH, g->KW, g->stride, g->dil,
-                          (g->KH - 1) * g->dil - g->pad_top, (g->KW - 1) * g->dil - g->pad_left, g->up1, 0, 0, (g->dtype & SPRK_DT_PIN) ? 1 : 0};
-}
-// the 16-bit-operand kernels' view of a forward call / of a backward-data call (a forward-shaped convolution of gy
-// with the flipped, channel-transposed taps and mirrored padding)
-sprk::Conv16Call call16_fwd(const sprk_conv_geom *g, const sprk_conv_epilogue *ep) {
-    sprk::Conv16Call c{};
-    c.dtype = g->dtype; c.mode = 0;
-    c.x16 = (g->dtype & SPRK_DT_X16) ? 1 : 0; c.y16 = (g->dtype & SPRK_DT_Y16) ? 1 : 0;
-    c.N = g->N; c.C1 = g->C1; c.C2 = g->C2; c.Hin = g->Hin; c.Win = g->Win; c.Cout = g->Cout; c.Hout = g->Hout;
-    c.Wout = g->Wout; c.KH = g->KH; c.KW = g->KW; c.stride = g->stride; c.dil = g->dil; c.padT = g->pad_top;
-    c.padL = g->pad_left; c.up1 = g->up1;
-    if (ep) {
-        c.up2 = ep->up2; c.res = ep->res != nullptr; c.act = ep->act; c.bias = ep->bias; c.scale = ep->scale;
-        c.shift = ep->shift;
-    }
-    c.kclass = kClass16;
-    c.flops = 2.0 * g->N * g->Hout * g->Wout * (double)g->Cout * (g->C1 + g->C2) * g->KH * g->KW;
-    return c;
-}
-sprk::Conv16Call call16_bwd(const sprk_conv_geom *g) {
-    sprk::Conv16Call c{};
-    c.dtype = g->dtype; c.mode = 1;
-    c.x16 = (g->dtype & SPRK_DT_X16) ? 1 : 0; c.y16 = (g->dtype & SPRK_DT_Y16) ? 1 : 0;    // gy / gin
-    c.N = g->N; c.C1 = g->Cout; c.C2 = 0; c.Hin = g->Hout; c.Win = g->Wout; c.Cout = g->C1 + g->C2; c.Hout = g->Hin;
-    c.Wout = g->Win; c.KH = g->KH; c.KW = g->KW; c.stride = g->stride; c.dil = g->dil;
-    c.padT = (g->KH - 1) * g->dil - g->pad_top; c.padL = (g->KW - 1) * g->dil - g->pad_left; c.up1 = g->up1;
-    c.act = SPRK_ACT_NONE;
-    c.kclass = kClass16;
-    c.flops = 2.0 * g->N * g->Hout * g->Wout * (double)g->Cout * (g->C1 + g->C2) * g->KH * g->KW;
-    return c;
-}
-
-sprk::Wgrad16Call call16_wgrad(const sprk_conv_geom *g) {
-    sprk::Wgrad16Call c{};
-    c.dtype = g->dtype;
-    c.x16 = (g->dtype & SPRK_DT_X16) ? 1 : 0;
-    c.N = g->N; c.C1 = g->C1; c.C2 = g->C2; c.H = g->Hin; c.W = g->Win; c.Cout = g->Cout; c.Hout = g->Hout;
-    c.Wout = g->Wout; c.KH = g->KH; c.KW = g->KW; c.stride = g->stride; c.dil = g->dil; c.padT = g->pad_top;
-    c.padL = g->pad_left; c.up1 = g->up1;
-    c.kclass = kClass16W;
-    c.flops = 2.0 * g->N * g->Hout * g->Wout * (double)g->Cout * (g->C1 + g->C2) * g->KH * g->KW;
-    return c;
-}
-
-size_t wino_ws_fwd(const sprk_conv_geom *g) {
-    return sprk::wino_eligible(wino_geom_fwd(g, nullptr)) ? sprk::wino_ws_bytes(g->C1, g->C2, g->Cout) : 0;
-}
-size_t wino_ws_bwd(const sprk_conv_geom *g) {
-    return sprk::wino_eligible(wino_geom_bwd(g)) ? sprk::wino_ws_bytes(g->Cout, 0, g->C1 + g->C2) : 0;
-}
-constexpr int kClassWino = 3;   // profiling class of the 96-channel Winograd kernel
 
 }  // namespace
 
@@ -1473,128 +1430,39 @@ int sprk_conv2d_storage16(const sprk_conv_geom *g, const sprk_conv_epilogue *ep)
     sprk_conv_geom q = *g;
     q.dtype = (g->dtype & ~(SPRK_DT_WPREP | SPRK_DT_WPREP_KIND(7))) | SPRK_DT_X16 | SPRK_DT_Y16;
     int r = 0;
-    if (sprk::conv16_kind(call16_fwd(&q, ep)) >= 2) r |= 1;
-    if (!g->up1 && sprk::conv16_kind(call16_bwd(&q)) >= 2) r |= 2;
-    if (sprk::wgrad16_eligible(call16_wgrad(&q))) r |= 4;
+    if (sprk::conv16_kind(sprk::Corr(q, ep)) >= 2) r |= 1;
+    if (sprk::conv16_kind(sprk::Corr(q)) >= 2) r |= 2;   // (never for an up1 layer: Corr::mfma_only)
+    if (sprk::wgrad16_eligible(q)) r |= 4;
     return r;
+}
+
+// What a dispatch of c can ask for: the maximum over the stages of conv_dispatch that could take it (0: the MFMA plan
+// does not fit LDS).  ops.WeightPrep keeps workspaces of this size for the life of a stepper.
+static size_t corr_ws_bytes(const sprk::Corr &c) {
+    FwdPlan p;
+    if (!plan_fwd(c, &p)) return 0;
+    size_t need = p.wsBytes;
+    if (sprk::wino_eligible(c)) need = std::max(need, sprk::wino_ws_bytes(c));
+    if (c.dt() != SPRK_DT_F32) need = std::max(need, sprk::conv16_ws_bytes(c));
+    return need;
 }
 
 size_t sprk_conv2d_fwd_ws_bytes(const sprk_conv_geom *g) {
     if (!g) return 0;
-    FwdPlan p;
-    if (!plan_fwd(g->N, g->C1 + g->C2, g->Cout, g->Hout, g->Wout, g->KH, g->KW, g->stride, g->dil, g->pad_left, g->up1,
-                  g->C2 > 0, g->Win, &p)) return 0;
-    size_t need = std::max(p.wsBytes, wino_ws_fwd(g));
-    if ((g->dtype & SPRK_DT_MASK) != SPRK_DT_F32) {
-        // the query does not know the epilogue the call will carry: the maximum over the 16-bit plans it can select
-        // (fused up-sampling and a residual exclude some kernels, and the remaining one may need more)
-        for (int v = 0; v < 4; ++v) {
-            sprk_conv_epilogue e = {nullptr, nullptr, nullptr, (v & 2) ? (const float *)g : nullptr, 0, 0, 0, SPRK_ACT_NONE, v & 1};
-            need = std::max(need, sprk::conv16_ws_bytes(call16_fwd(g, &e)));
-        }
+    // the query does not know the epilogue the call will carry (fused up-sampling and a residual exclude some kernels,
+    // and the remaining one may need more): the maximum over the four cases
+    size_t need = 0;
+    for (int v = 0; v < 4; ++v) {
+        sprk_conv_epilogue e = sprk::kNoEpilogue;
+        e.up2 = v & 1;
+        e.res = (v & 2) ? (const float *)g : nullptr;   // any non-null pointer: never read
+        need = std::max(need, corr_ws_bytes(sprk::Corr(*g, &e)));
     }
     return need;
-}
-
-static int conv2d_fwd_impl(const float *x, const float *x2, const float *w, float *y, const sprk_conv_geom *g,
-                           const sprk_conv_epilogue *ep, void *ws, size_t ws_bytes, void *stream);
-
-int sprk_conv2d_fwd(const float *x, const float *x2, const float *w, float *y, const sprk_conv_geom *g,
-                    const sprk_conv_epilogue *ep, void *ws, size_t ws_bytes, void *stream) {
-    sprk::WprepScope scope(nullptr, g ? g->dtype : 0);
-    return scope.verify(conv2d_fwd_impl(x, x2, w, y, g, ep, ws, ws_bytes, stream));
-}
-
-int sprk_conv2d_fwd_wprep(const float *w, const sprk_conv_geom *g, const sprk_conv_epilogue *ep, void *ws,
-                          size_t ws_bytes, sprk_wprep_item *item) {
-    SPRK_REQUIRE(item && w && ws, "conv2d_fwd_wprep: null argument");
-    *item = sprk_wprep_item{};
-    sprk::WprepScope scope(item, 0);
-    // the tensors are never touched in describe mode: the call ends at its weight-transform site
-    const float *dummy = (const float *)ws;
-    const int rc = conv2d_fwd_impl(dummy, g && g->C2 ? dummy : nullptr, w, (float *)ws, g, ep, ws, ws_bytes, nullptr);
-    return rc == sprk::kWprepDescribed ? (int)SPRK_OK : rc;
-}
-
-static int conv2d_fwd_impl(const float *x, const float *x2, const float *w, float *y, const sprk_conv_geom *g,
-                           const sprk_conv_epilogue *ep, void *ws, size_t ws_bytes, void *stream) {
-    if (int rc = check_geom(g)) return rc;
-    SPRK_REQUIRE(x && w && y, "conv2d_fwd: null tensor");
-    SPRK_REQUIRE(g->C2 == 0 || x2, "conv2d_fwd: C2 > 0 but x2 is null");
-    hipStream_t s = (hipStream_t)stream;
-    sprk_conv_epilogue e0 = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0, SPRK_ACT_NONE, 0};
-    if (!ep) ep = &e0;
-    SPRK_REQUIRE(!ep->scale || ep->shift, "conv2d_fwd: scale without shift");
-    if (naive_of(g)) {
-        if (sprk::wprep_describing()) return SPRK_OK;   // no weight transform on this path
-        DirectArgs a{x, x2, w, nullptr, y, *g, *ep};
-        const long total = (long)g->N * g->Cout * g->Hout * g->Wout;
-        hipLaunchKernelGGL(conv_fwd_direct_kernel, dim3(sprk::ew_blocks(total)), dim3(256), 0, s, a);
-        return sprk::check_launch("conv_fwd_direct");
-    }
-    if ((g->dtype & SPRK_DT_MASK) != SPRK_DT_F32 && !naive_of(g)) {
-        const sprk::Conv16Call c16 = call16_fwd(g, ep);
-        if (sprk::conv16_eligible(c16)) return sprk::conv16_run(c16, x, x2, w, y, ws, ws_bytes, s);
-    }
-    SPRK_REQUIRE(!(g->dtype & (SPRK_DT_X16 | SPRK_DT_Y16)),
-                 "conv2d_fwd: no kernel takes this geometry with 16-bit activation tensors (ask sprk_conv2d_storage16 first)");
-    if (sprk::wino_eligible(wino_geom_fwd(g, ep)) && !ep->res) {
-        const size_t need = sprk::wino_ws_bytes(g->C1, g->C2, g->Cout);
-        if (ws_bytes < need || !ws) {
-            sprk::set_error("conv2d_fwd: workspace %zu < %zu", ws_bytes, need);
-            return SPRK_EWORKSPACE;
-        }
-        sprk::WinoArgs wa{x, x2, w, ep->bias, ep->scale, ep->shift, y, (float *)ws, g->N, g->C1, g->C2, g->Hin, g->Win,
-                          g->Cout, g->pad_top, g->pad_left, ep->act, 0, g->Cout > 48 ? kClassWino : 2,
-                          2.0 * g->N * g->Hout * g->Wout * (double)g->Cout * (g->C1 + g->C2) * 9, ep->up2 ? 1 : 0};
-        if (int rc = sprk::wino_conv(wa, s)) return rc;
-        return sprk::check_launch("wino_conv");
-    }
-    FwdPlan p;
-    SPRK_REQUIRE(plan_fwd(g->N, g->C1 + g->C2, g->Cout, g->Hout, g->Wout, g->KH, g->KW, g->stride, g->dil, g->pad_left, g->up1,
-                  g->C2 > 0, g->Win, &p),
-                 "conv2d_fwd: geometry does not fit LDS");
-    if (ws_bytes < p.wsBytes || !ws) {
-        sprk::set_error("conv2d_fwd: workspace %zu < %zu", ws_bytes, p.wsBytes);
-        return SPRK_EWORKSPACE;
-    }
-    float *wsf = (float *)ws;
-    if (int rc = transform_weights(w, wsf, g->Cout, g->C1 + g->C2, g->KH * g->KW, 0, p, s)) return rc;
-    ConvArgs a{};
-    a.x = x; a.x2 = x2; a.zeros = wsf; a.wT = wsf + kZeroFloats;
-    a.bias = ep->bias; a.scale = ep->scale; a.shift = ep->shift; a.res = ep->res;
-    a.y = y;
-    a.N = g->N; a.C1 = g->C1; a.C2 = g->C2; a.Hin = g->Hin; a.Win = g->Win; a.up1 = g->up1;
-    a.H1 = g->up1 ? g->Hin / 2 : g->Hin;
-    a.W1 = g->up1 ? g->Win / 2 : g->Win;
-    a.Cout = g->Cout; a.Hout = g->Hout; a.Wout = g->Wout;
-    a.KH = g->KH; a.KW = g->KW; a.stride = g->stride; a.dil = g->dil; a.padT = g->pad_top; a.padL = g->pad_left;
-    a.act = ep->act;
-    a.resH = ep->res_h; a.resW = ep->res_w; a.resOff = ep->res_off;
-    a.up2 = ep->up2;
-    fill_args(a, p);
-    a.vec4 = (g->Wout % 4 == 0) && (p.lgTC >= 2) && (((uintptr_t)y & 15) == 0);
-    const double flops = 2.0 * g->N * g->Hout * g->Wout * (double)g->Cout * (g->C1 + g->C2) * g->KH * g->KW;
-    const int kclass = (p.MT == 4 && p.NT == 6) ? 0 : 2;   // 0: the dominant instantiation conv_mfma_kernel<4, 6>
-    sprk::prof_begin(kclass, flops, s);
-    if (int rc = launch_fwd(a, p, s)) return rc;
-    sprk::prof_end(kclass, s);
-    return sprk::check_launch("conv_mfma");
 }
 
 size_t sprk_conv2d_bwd_data_ws_bytes(const sprk_conv_geom *g) {
-    if (!g || g->stride != 1) return 0;
-    FwdPlan p;
-    if (!plan_fwd(g->N, g->Cout, g->C1 + g->C2, g->Hin, g->Win, g->KH, g->KW, 1, g->dil, (g->KW - 1) * g->dil - g->pad_left, 0, 0,
-                  g->Wout, &p)) return 0;
-    size_t need = std::max(p.wsBytes, wino_ws_bwd(g));
-    if ((g->dtype & SPRK_DT_MASK) != SPRK_DT_F32) need = std::max(need, sprk::conv16_ws_bytes(call16_bwd(g)));
-    return need;
-}
-
-int sprk_conv2d_bwd_data(const float *gy, const float *w, float *gin, const sprk_conv_geom *g, void *ws,
-                         size_t ws_bytes, void *stream) {
-    return sprk_conv2d_bwd_data_masked(gy, w, gin, g, nullptr, SPRK_ACT_NONE, ws, ws_bytes, stream);
+    return (g && g->stride == 1) ? corr_ws_bytes(sprk::Corr(*g)) : 0;
 }
 
 // in-place mask of a finished gradient (the layers whose backward-data kernel has no masked epilogue)
@@ -1605,103 +1473,113 @@ static int mask_in_place(float *gin, const float *mask_y, int mask_act, const sp
                         nullptr, 0, s);
 }
 
-static int conv2d_bwd_data_impl(const float *gy, const float *w, float *gin, const sprk_conv_geom *g,
-                                const float *mask_y, int mask_act, void *ws, size_t ws_bytes, void *stream);
+// The one place where a forward or (bwd) backward-data call meets its kernel; a new convolution kernel is plugged in
+// here ("The convolution dispatcher").  g / ep: the layer as the caller gave it; for backward-data x = gy,
+// x2 = null, y = gin, and mask_y / mask_act the optional mask of sprk_conv2d_bwd_data_masked.  The stages, in order:
+//   direct kernels (SPRK_DT_NAIVE; strided backward-data) -> 16-bit operands -> storage guard -> Winograd -> MFMA
+static int conv_dispatch(bool bwd, const float *x, const float *x2, const float *w, float *y, const sprk_conv_geom *g,
+                         const sprk_conv_epilogue *ep, const float *mask_y, int mask_act, void *ws, size_t ws_bytes,
+                         void *stream) {
+    const char *who = bwd ? "conv2d_bwd_data" : "conv2d_fwd";
+    if (int rc = check_geom(g)) return rc;
+    SPRK_REQUIRE(x && w && y, "%s: null tensor", who);
+    if (bwd) {
+        SPRK_REQUIRE(mask_act == SPRK_ACT_NONE || (mask_y && !g->up1), "conv2d_bwd_data: mask needs the saved input, no upsampling");
+        if (mask_act == SPRK_ACT_NONE) mask_y = nullptr;
+    } else {
+        SPRK_REQUIRE(g->C2 == 0 || x2, "conv2d_fwd: C2 > 0 but x2 is null");
+        SPRK_REQUIRE(!ep || !ep->scale || ep->shift, "conv2d_fwd: scale without shift");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // the kernels without a masked epilogue: the mask is an in-place pass over the finished gradient
+    auto masked = [&](int rc) { return (rc || !mask_y) ? rc : mask_in_place(y, mask_y, mask_act, g, s); };
+
+    if (naive_of(g) || (bwd && g->stride != 1)) {
+        if (sprk::wprep_describing()) return SPRK_OK;   // no weight transform on this path
+        if (bwd) {
+            DirectArgs a{nullptr, nullptr, w, x, y, *g, sprk::kNoEpilogue};
+            const long total = (long)g->N * (g->C1 + g->C2) * g->Hin * g->Win;
+            hipLaunchKernelGGL(conv_bwd_data_direct_kernel, dim3(sprk::ew_blocks(total)), dim3(256), 0, s, a);
+            return masked(sprk::check_launch("conv_bwd_data_direct"));
+        }
+        DirectArgs a{x, x2, w, nullptr, y, *g, ep ? *ep : sprk::kNoEpilogue};
+        const long total = (long)g->N * g->Cout * g->Hout * g->Wout;
+        hipLaunchKernelGGL(conv_fwd_direct_kernel, dim3(sprk::ew_blocks(total)), dim3(256), 0, s, a);
+        return sprk::check_launch("conv_fwd_direct");
+    }
+    const sprk::Corr c = bwd ? sprk::Corr(*g) : sprk::Corr(*g, ep);
+
+    // (a masked epilogue in conv16_tile_kernel<6> takes it from 231 to 256 VGPRs + 92 bytes of scratch — the next
+    // tile's fetch is in flight during the stores — and the bf16 step from 11.22 to 11.27 ms: in-place pass)
+    if (c.dt() != SPRK_DT_F32 && sprk::conv16_eligible(c)) return masked(sprk::conv16_run(c, x, x2, w, y, ws, ws_bytes, s));
+    if (int rc = check_storage32(who, c.dtype)) return rc;
+
+    if (sprk::wino_eligible(c)) {
+        if (int rc = sprk::check_ws(who, ws, ws_bytes, sprk::wino_ws_bytes(c))) return rc;
+        // the mask is d act / d y of the layer that produced this conv's input, applied in the output transform: gin
+        // leaves the kernel as that layer's pre-activation gradient
+        if (int rc = sprk::wino_conv(c, x, x2, w, y, (float *)ws, mask_y, mask_act, s)) return rc;
+        return sprk::check_launch(bwd ? "wino_conv(bwd_data)" : "wino_conv");
+    }
+
+    FwdPlan p;
+    SPRK_REQUIRE(plan_fwd(c, &p), "%s: geometry does not fit LDS", who);
+    if (int rc = sprk::check_ws(who, ws, ws_bytes, p.wsBytes)) return rc;
+    float *wsf = (float *)ws;
+    if (int rc = transform_weights(w, wsf, g->Cout, g->C1 + g->C2, g->KH * g->KW, c.taps, p, s)) return rc;
+    const ConvArgs a = conv_args(c, p, x, x2, wsf, y);
+    // (a masked epilogue in this kernel costs 26 VGPRs — 160 -> 186, two workgroups per CU instead of three — for
+    // every call, masked or not: measured in round 1 and again in round 3; the mask is applied by an in-place pass)
+    const int kclass = (p.MT == 4 && p.NT == 6) ? 0 : 2;   // 0: the dominant instantiation conv_mfma_kernel<4, 6>
+    sprk::prof_begin(kclass, c.flops, s);
+    if (int rc = launch_fwd(a, p, s)) return rc;
+    sprk::prof_end(kclass, s);
+    return masked(sprk::check_launch(bwd ? "conv_mfma(bwd_data)" : "conv_mfma"));
+}
+
+int sprk_conv2d_fwd(const float *x, const float *x2, const float *w, float *y, const sprk_conv_geom *g,
+                    const sprk_conv_epilogue *ep, void *ws, size_t ws_bytes, void *stream) {
+    sprk::WprepScope scope(nullptr, g ? g->dtype : 0);
+    return scope.verify(conv_dispatch(false, x, x2, w, y, g, ep, nullptr, SPRK_ACT_NONE, ws, ws_bytes, stream));
+}
+
+int sprk_conv2d_fwd_wprep(const float *w, const sprk_conv_geom *g, const sprk_conv_epilogue *ep, void *ws,
+                          size_t ws_bytes, sprk_wprep_item *item) {
+    SPRK_REQUIRE(item && w && ws, "conv2d_fwd_wprep: null argument");
+    *item = sprk_wprep_item{};
+    sprk::WprepScope scope(item, 0);
+    // the tensors are never touched in describe mode: the call ends at its weight-transform site
+    const float *dummy = (const float *)ws;
+    const int rc = conv_dispatch(false, dummy, g && g->C2 ? dummy : nullptr, w, (float *)ws, g, ep, nullptr, SPRK_ACT_NONE,
+                                 ws, ws_bytes, nullptr);
+    return rc == sprk::kWprepDescribed ? (int)SPRK_OK : rc;
+}
+
+int sprk_conv2d_bwd_data(const float *gy, const float *w, float *gin, const sprk_conv_geom *g, void *ws,
+                         size_t ws_bytes, void *stream) {
+    return sprk_conv2d_bwd_data_masked(gy, w, gin, g, nullptr, SPRK_ACT_NONE, ws, ws_bytes, stream);
+}
 
 int sprk_conv2d_bwd_data_masked(const float *gy, const float *w, float *gin, const sprk_conv_geom *g,
                                 const float *mask_y, int mask_act, void *ws, size_t ws_bytes, void *stream) {
     sprk::WprepScope scope(nullptr, g ? g->dtype : 0);
-    return scope.verify(conv2d_bwd_data_impl(gy, w, gin, g, mask_y, mask_act, ws, ws_bytes, stream));
+    return scope.verify(conv_dispatch(true, gy, nullptr, w, gin, g, nullptr, mask_y, mask_act, ws, ws_bytes, stream));
 }
 
 int sprk_conv2d_bwd_data_wprep(const float *w, const sprk_conv_geom *g, void *ws, size_t ws_bytes, sprk_wprep_item *item) {
     SPRK_REQUIRE(item && w && ws, "conv2d_bwd_data_wprep: null argument");
     *item = sprk_wprep_item{};
     sprk::WprepScope scope(item, 0);
-    const int rc = conv2d_bwd_data_impl((const float *)ws, w, (float *)ws, g, nullptr, SPRK_ACT_NONE, ws, ws_bytes, nullptr);
+    const int rc = conv_dispatch(true, (const float *)ws, nullptr, w, (float *)ws, g, nullptr, nullptr, SPRK_ACT_NONE, ws,
+                                 ws_bytes, nullptr);
     return rc == sprk::kWprepDescribed ? (int)SPRK_OK : rc;
-}
-
-static int conv2d_bwd_data_impl(const float *gy, const float *w, float *gin, const sprk_conv_geom *g,
-                                const float *mask_y, int mask_act, void *ws, size_t ws_bytes, void *stream) {
-    if (int rc = check_geom(g)) return rc;
-    SPRK_REQUIRE(gy && w && gin, "conv2d_bwd_data: null tensor");
-    SPRK_REQUIRE(mask_act == SPRK_ACT_NONE || (mask_y && !g->up1), "conv2d_bwd_data: mask needs the saved input, no upsampling");
-    if (mask_act == SPRK_ACT_NONE) mask_y = nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    const int Cin = g->C1 + g->C2;
-    if (naive_of(g) || g->stride != 1) {
-        if (sprk::wprep_describing()) return SPRK_OK;   // no weight transform on this path
-        sprk_conv_epilogue e0 = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0, SPRK_ACT_NONE, 0};
-        DirectArgs a{nullptr, nullptr, w, gy, gin, *g, e0};
-        const long total = (long)g->N * Cin * g->Hin * g->Win;
-        hipLaunchKernelGGL(conv_bwd_data_direct_kernel, dim3(sprk::ew_blocks(total)), dim3(256), 0, s, a);
-        if (int rc = sprk::check_launch("conv_bwd_data_direct")) return rc;
-        return mask_y ? mask_in_place(gin, mask_y, mask_act, g, s) : (int)SPRK_OK;
-    }
-    // gin = correlation of gy with the flipped, channel-transposed kernel
-    if ((g->dtype & SPRK_DT_MASK) != SPRK_DT_F32 && !naive_of(g)) {
-        const sprk::Conv16Call c16 = call16_bwd(g);
-        if (sprk::conv16_eligible(c16)) {
-            // (a masked epilogue in conv16_tile_kernel<6> takes it from 231 to 256 VGPRs + 92 bytes of scratch — the next
-            // tile's fetch is in flight during the stores — and the bf16 step from 11.22 to 11.27 ms: in-place pass)
-            if (int rc = sprk::conv16_run(c16, gy, nullptr, w, gin, ws, ws_bytes, s)) return rc;
-            return mask_y ? mask_in_place(gin, mask_y, mask_act, g, s) : (int)SPRK_OK;
-        }
-    }
-    SPRK_REQUIRE(!(g->dtype & (SPRK_DT_X16 | SPRK_DT_Y16)),
-                 "conv2d_bwd_data: no kernel takes this geometry with 16-bit activation tensors (ask sprk_conv2d_storage16 first)");
-    if (sprk::wino_eligible(wino_geom_bwd(g))) {
-        const size_t need = sprk::wino_ws_bytes(g->Cout, 0, Cin);
-        if (ws_bytes < need || !ws) {
-            sprk::set_error("conv2d_bwd_data: workspace %zu < %zu", ws_bytes, need);
-            return SPRK_EWORKSPACE;
-        }
-        sprk::WinoArgs wa{gy, nullptr, w, nullptr, nullptr, nullptr, gin, (float *)ws, g->N, g->Cout, 0, g->Hout, g->Wout,
-                          Cin, (g->KH - 1) * g->dil - g->pad_top, (g->KW - 1) * g->dil - g->pad_left, SPRK_ACT_NONE, 1,
-                          Cin > 48 ? kClassWino : 2, 2.0 * g->N * g->Hout * g->Wout * (double)g->Cout * Cin * 9};
-        wa.mask = mask_y;          // d act / d y of the layer that produced this conv's input, applied in the output
-        wa.mask_act = mask_act;    // transform: gin leaves the kernel as that layer's pre-activation gradient
-        if (int rc = sprk::wino_conv(wa, s)) return rc;
-        return sprk::check_launch("wino_conv(bwd_data)");
-    }
-    FwdPlan p;
-    SPRK_REQUIRE(plan_fwd(g->N, g->Cout, Cin, g->Hin, g->Win, g->KH, g->KW, 1, g->dil, (g->KW - 1) * g->dil - g->pad_left, 0, 0,
-                          g->Wout, &p),
-                 "conv2d_bwd_data: geometry does not fit LDS");
-    if (ws_bytes < p.wsBytes || !ws) {
-        sprk::set_error("conv2d_bwd_data: workspace %zu < %zu", ws_bytes, p.wsBytes);
-        return SPRK_EWORKSPACE;
-    }
-    float *wsf = (float *)ws;
-    if (int rc = transform_weights(w, wsf, g->Cout, Cin, g->KH * g->KW, 1, p, s)) return rc;
-    ConvArgs a{};
-    a.x = gy; a.x2 = nullptr; a.zeros = wsf; a.wT = wsf + kZeroFloats; a.y = gin;
-    a.N = g->N; a.C1 = g->Cout; a.C2 = 0; a.Hin = g->Hout; a.Win = g->Wout; a.up1 = 0;
-    a.H1 = g->Hout; a.W1 = g->Wout;
-    a.Cout = Cin; a.Hout = g->Hin; a.Wout = g->Win;
-    a.KH = g->KH; a.KW = g->KW; a.stride = 1; a.dil = g->dil;
-    a.padT = (g->KH - 1) * g->dil - g->pad_top;
-    a.padL = (g->KW - 1) * g->dil - g->pad_left;
-    a.act = SPRK_ACT_NONE;
-    fill_args(a, p);
-    a.vec4 = (g->Win % 4 == 0) && (p.lgTC >= 2) && (((uintptr_t)gin & 15) == 0);
-    // (a masked epilogue in this kernel costs 26 VGPRs — 160 -> 186, two workgroups per CU instead of three — for
-    // every call, masked or not: measured in round 1 and again in round 3; the mask is applied by an in-place pass)
-    const double flops = 2.0 * g->N * g->Hout * g->Wout * (double)g->Cout * Cin * g->KH * g->KW;
-    const int kclass = (p.MT == 4 && p.NT == 6) ? 0 : 2;
-    sprk::prof_begin(kclass, flops, s);
-    if (int rc = launch_fwd(a, p, s)) return rc;
-    sprk::prof_end(kclass, s);
-    if (int rc = sprk::check_launch("conv_mfma(bwd_data)")) return rc;
-    return mask_y ? mask_in_place(gin, mask_y, mask_act, g, s) : (int)SPRK_OK;
 }
 
 size_t sprk_conv2d_bwd_weight_ws_bytes(const sprk_conv_geom *g) {
     if (!g) return 0;
-    const size_t wino = sprk::wino_wgrad_eligible(wino_geom_fwd(g, nullptr))
+    const size_t wino = sprk::wino_wgrad_eligible(*g)
                             ? sprk::wino_wgrad_ws_bytes(g->C1, g->C2, g->Cout) : 0;
-    const size_t w16 = (g->dtype & SPRK_DT_MASK) != SPRK_DT_F32 ? sprk::wgrad16_ws_bytes(call16_wgrad(g)) : 0;
+    const size_t w16 = (g->dtype & SPRK_DT_MASK) != SPRK_DT_F32 ? sprk::wgrad16_ws_bytes(*g) : 0;
     WgPlan p;
     if (!plan_wgrad(g, &p)) return std::max(wino, w16);
     return std::max(std::max(p.wsBytes, wino), w16);
@@ -1721,34 +1599,24 @@ int sprk_conv2d_bwd_weight_partial(const float *x, const float *x2, const float 
     SPRK_REQUIRE(g->C2 == 0 || x2, "conv2d_bwd_weight: C2 > 0 but x2 is null");
     hipStream_t s = (hipStream_t)stream;
     const int Cin = g->C1 + g->C2;
-    if ((g->dtype & SPRK_DT_MASK) != SPRK_DT_F32 && !naive_of(g)) {
-        const sprk::Wgrad16Call c16 = call16_wgrad(g);
-        if (sprk::wgrad16_eligible(c16)) return sprk::wgrad16_run(c16, x, x2, gy, gw, ws, ws_bytes, item, s);
-    }
-    SPRK_REQUIRE(!(g->dtype & (SPRK_DT_X16 | SPRK_DT_Y16)),
-                 "conv2d_bwd_weight: no kernel takes this geometry with 16-bit activation tensors (ask sprk_conv2d_storage16 first)");
-    if (!naive_of(g) && sprk::wino_wgrad_eligible(wino_geom_fwd(g, nullptr))) {
-        const size_t need = sprk::wino_wgrad_ws_bytes(g->C1, g->C2, g->Cout);
-        if (ws_bytes < need || !ws) {
-            sprk::set_error("conv2d_bwd_weight: workspace %zu < %zu", ws_bytes, need);
-            return SPRK_EWORKSPACE;
-        }
+    const char *who = "conv2d_bwd_weight";
+    if ((g->dtype & SPRK_DT_MASK) != SPRK_DT_F32 && !naive_of(g) && sprk::wgrad16_eligible(*g))
+        return sprk::wgrad16_run(*g, x, x2, gy, gw, ws, ws_bytes, item, s);
+    if (int rc = check_storage32(who, g->dtype)) return rc;
+    if (!naive_of(g) && sprk::wino_wgrad_eligible(*g)) {
+        if (int rc = sprk::check_ws(who, ws, ws_bytes, sprk::wino_wgrad_ws_bytes(g->C1, g->C2, g->Cout))) return rc;
         sprk::WinoWgArgs wa{x, x2, gy, gw, (float *)ws, g->N, g->C1, g->C2, g->Hin, g->Win, g->Cout, g->pad_top, g->pad_left, 4,
-                            2.0 * g->N * g->Hout * g->Wout * (double)g->Cout * Cin * 9};   // profiling class 4
+                            sprk::conv_flops(*g)};   // profiling class 4
         return sprk::wino_wgrad(wa, s);
     }
     WgPlan p;
     const bool ok = plan_wgrad(g, &p);
     if (naive_of(g) || !ok) {
-        sprk_conv_epilogue e0 = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0, SPRK_ACT_NONE, 0};
-        DirectArgs a{x, x2, nullptr, gy, gw, *g, e0};
+        DirectArgs a{x, x2, nullptr, gy, gw, *g, sprk::kNoEpilogue};
         hipLaunchKernelGGL(conv_bwd_weight_direct_kernel, dim3(g->Cout * Cin), dim3(256), 0, s, a);
         return sprk::check_launch("conv_bwd_weight_direct");
     }
-    if (ws_bytes < p.wsBytes || !ws) {
-        sprk::set_error("conv2d_bwd_weight: workspace %zu < %zu", ws_bytes, p.wsBytes);
-        return SPRK_EWORKSPACE;
-    }
+    if (int rc = sprk::check_ws(who, ws, ws_bytes, p.wsBytes)) return rc;
     float *wsf = (float *)ws;
     const float *zeros = nullptr;  // device-resident, never written: no per-call memset
     if (hipGetSymbolAddress((void **)&zeros, HIP_SYMBOL(g_zero_block)) != hipSuccess || !zeros) {
@@ -1782,7 +1650,7 @@ int sprk_conv2d_bwd_weight_partial(const float *x, const float *x2, const float 
     const int NIw = 64 >> (p.lgTC + p.lgTR);
     const bool fits = (long)NIw * Cin * planeI < (1L << 28) && (long)NIw * g->Cout * planeO < (1L << 28) &&
                       (long)p.CKW * planeI < (1L << 28) && (long)p.NT * 16 * planeO < (1L << 28);
-    static const int rowbuf = dbg_int("SPRK_WG_ROWBUF", 1);
+    static const int rowbuf = sprk::knob_env("SPRK_WG_ROWBUF", 1);
     const bool fast = rowbuf && fits && a.g4;
     a.xtab = fast ? 1 : 0;
     if (a.xrow && (!fast || (((uintptr_t)x & 15) != 0))) {
@@ -1797,8 +1665,7 @@ int sprk_conv2d_bwd_weight_partial(const float *x, const float *x2, const float 
     a.nG1 = p.nG1;
     a.nG2 = p.nG2;
     dim3 grid(p.groups, p.nChunks, p.nblkN);
-    const double flops = 2.0 * g->N * g->Hout * g->Wout * (double)g->Cout * Cin * g->KH * g->KW;
-    sprk::prof_begin(1, flops, s);
+    sprk::prof_begin(1, sprk::conv_flops(*g), s);
     const int rc = mode == 1 ? launch_wg<1>(a, p, grid, s) : mode == 2 ? launch_wg<2>(a, p, grid, s) : launch_wg<0>(a, p, grid, s);
     if (rc) return rc;
     sprk::prof_end(1, s);

@@ -66,10 +66,10 @@ struct Conv16Args {
 };
 
 // ---- weights: fp32 [Cout][Cin][KHW] -> 16-bit slabs: a prepared-weight item (wprep_dev.h: wprep_16) ----------------
-static int transform16(const sprk::Conv16Call &c, const float *w, void *ws, long total, int wCout, int wCin, int KHW,
+static int transform16(const sprk::Corr &c, const float *w, void *ws, long total, int wCout, int wCin, int KHW,
                        int CK, int G4, int NT16, int nblk, int nchunks, hipStream_t s) {
     const int kind = (c.dtype & SPRK_DT_MASK) == SPRK_DT_BF16 ? sprk::WPREP_BF16 : sprk::WPREP_F16;
-    return sprk::wprep_site(sprk::wprep_item(kind, w, ws, total, {wCout, wCin, KHW, c.mode, CK, G4, NT16, nblk, nchunks}), s);
+    return sprk::wprep_site(sprk::wprep_item(kind, w, ws, total, {wCout, wCin, KHW, c.taps, CK, G4, NT16, nblk, nchunks}), s);
 }
 
 // ---- one staged chunk: nks k-steps of 32 ---------------------------------------------------------------------
@@ -1012,7 +1012,7 @@ template <typename T, bool X16, bool Y16>
 int launch_tile(const Tile16Args &k, const PlanT &p, hipStream_t s) {
     // persistent workgroups: one per CU (8 waves at 159-225 VGPRs fill it), shared among the output-channel blocks
     const int ntiles = p.imgGroups * p.tilesX * p.tilesY;
-    static const int persist = getenv("SPRK_C16_PERSIST") ? atoi(getenv("SPRK_C16_PERSIST")) : 1;   // debug: 0 = one tile each
+    static const int persist = sprk::knob_env("SPRK_C16_PERSIST", 1);   // 0 = one tile each
     const int slots = std::max(1, sprk::num_cus() / p.nblkN);
     dim3 grid(persist ? std::min(ntiles, slots) : ntiles, p.nblkN);
     auto go = [&](auto kernel) {
@@ -1036,29 +1036,31 @@ int launch_tile_io(const Tile16Args &k, const PlanT &p, int x16, int y16, hipStr
 
 namespace sprk {
 
+constexpr int kClass16 = 5;   // profiling class of the 16-bit-operand forward / backward-data kernels
+
 // head kernel shape of a call: CQ = 4 (97..384 outputs) or 1 (<= 96); CK = 64 where the input channels allow, else 32
-static void head_shape(const Conv16Call &c, int *cq, int *ck) {
+static void head_shape(const Corr &c, int *cq, int *ck) {
     *cq = c.Cout > 96 ? 4 : 1;
     *ck = (*cq == 4 && c.C1 % 64 == 0) ? 64 : 32;
 }
-static size_t head_ws_bytes(const Conv16Call &c) {
+static size_t head_ws_bytes(const Corr &c) {
     int cq, ck;
     head_shape(c, &cq, &ck);
     return (size_t)(c.C1 / ck) * (ck / 8) * 96 * cq * 16;
 }
 
 // which 16-bit kernel (if any) takes this call: 2 = conv16_tile_kernel (3x3), 1 = conv16_mfma_kernel (1x1), 0 = none
-static int plan_of(const Conv16Call &c, Plan16 *p, PlanT *pt) {
+static int plan_of(const Corr &c, Plan16 *p, PlanT *pt) {
     const int dt = c.dtype & SPRK_DT_MASK;
     if (dt != SPRK_DT_BF16 && dt != SPRK_DT_F16) return 0;
-    static const int on = getenv("SPRK_CONV16") ? atoi(getenv("SPRK_CONV16")) : 1;   // debug: 0 = always fp32
+    static const int on = knob_env("SPRK_CONV16", 1);   // 0 = always fp32
     if (!on) return 0;
-    if (c.stride != 1 || c.dil != 1 || c.up1 || c.res) return 0;
+    if (c.stride != 1 || c.dil != 1 || c.up1 || c.mfma_only || c.ep.res) return 0;
     if (c.Hout != c.Hin || c.Wout != c.Win) return 0;                 // same-size layers (U-Net body)
     if (c.padL < 0 || c.padL > 4 || c.padT < 0) return 0;
-    if (c.KH == 1 && c.KW == 1 && !c.C2 && !c.up2 && c.padT == 0 && c.padL == 0) {
+    if (c.KH == 1 && c.KW == 1 && !c.C2 && !c.ep.up2 && c.padT == 0 && c.padL == 0) {
         // conv16_head_kernel: 33..384 output channels, input channels a multiple of 32, planes of 4k pixels
-        static const int head_on = getenv("SPRK_CONV16_HEAD") ? atoi(getenv("SPRK_CONV16_HEAD")) : 1;   // debug
+        static const int head_on = knob_env("SPRK_CONV16_HEAD", 1);
         const long HW = (long)c.Hin * c.Win;
         const int pxt = c.Cout > 96 ? 128 : 512;
         if (head_on && c.Cout >= 33 && c.Cout <= 384 && c.C1 % 32 == 0 && HW % 4 == 0 && 8 * HW * 4 < (1L << 31) &&
@@ -1066,14 +1068,14 @@ static int plan_of(const Conv16Call &c, Plan16 *p, PlanT *pt) {
             return 3;
     }
     if (c.KH == 3 && c.KW == 3) {
-        static const int tile_on = getenv("SPRK_CONV16_TILE") ? atoi(getenv("SPRK_CONV16_TILE")) : 1;   // debug
-        if (tile_on && plan_tile(c.N, c.C1 + c.C2, c.Cout, c.Hout, c.Wout, c.x16, c.padL, pt)) {
+        static const int tile_on = knob_env("SPRK_CONV16_TILE", 1);
+        if (tile_on && plan_tile(c.N, c.C1 + c.C2, c.Cout, c.Hout, c.Wout, c.x16(), c.padL, pt)) {
             // 32-bit byte offsets: an image group's span and 16 channel planes
             const long HW = (long)c.Hin * c.Win, cmax = std::max(c.C1, c.C2);
             if (((pt->NI - 1) * cmax + 1) * HW * 4 < (1L << 31) && 16 * HW * 4 < (1L << 31)) return 2;
         }
     }
-    if (c.x16 || c.y16) return 0;       // 16-bit activation storage: conv16_tile_kernel / conv16_head_kernel only
+    if (c.x16() || c.y16()) return 0;       // 16-bit activation storage: conv16_tile_kernel / conv16_head_kernel only
     // Where the fp32 Winograd kernel is the faster one (measured on MI355X, scratch/convbench.py): on the wide 3x3
     // layers at 64x64 and up the 256-pixel-tile kernel is bound by moving fp32 tiles through LDS-DMA (96->96 at
     // 128x64^2: 455 us fp32 Winograd, 570 us here).  Without SPRK_DT_FORCE those layers stay fp32.
@@ -1086,14 +1088,14 @@ static int plan_of(const Conv16Call &c, Plan16 *p, PlanT *pt) {
     return 1;
 }
 
-bool conv16_eligible(const Conv16Call &c) { return conv16_kind(c) != 0; }
-int conv16_kind(const Conv16Call &c) {
+bool conv16_eligible(const Corr &c) { return conv16_kind(c) != 0; }
+int conv16_kind(const Corr &c) {
     Plan16 p;
     PlanT pt;
     return plan_of(c, &p, &pt);
 }
 
-size_t conv16_ws_bytes(const Conv16Call &c) {
+size_t conv16_ws_bytes(const Corr &c) {
     Plan16 p;
     PlanT pt;
     const int which = plan_of(c, &p, &pt);
@@ -1103,12 +1105,9 @@ size_t conv16_ws_bytes(const Conv16Call &c) {
 
 long conv16_launches() { return g_conv16_launches.load(); }
 
-static int run_tile(const Conv16Call &c, const PlanT &p, const void *x, const void *x2, const float *w, void *y,
+static int run_tile(const Corr &c, const PlanT &p, const void *x, const void *x2, const float *w, void *y,
                     void *ws, size_t ws_bytes, hipStream_t s) {
-    if (ws_bytes < p.wsBytes || !ws) {
-        set_error("conv16: workspace too small (%zu < %zu)", ws_bytes, p.wsBytes);
-        return SPRK_EWORKSPACE;
-    }
+    if (int rc = check_ws("conv16", ws, ws_bytes, p.wsBytes)) return rc;
     if ((((uintptr_t)x | (uintptr_t)x2 | (uintptr_t)y | (uintptr_t)ws) & 15) != 0) {
         set_error("conv16: tensors must be 16-byte aligned");
         return SPRK_EINVAL;
@@ -1116,17 +1115,17 @@ static int run_tile(const Conv16Call &c, const PlanT &p, const void *x, const vo
     const int Cin = c.C1 + c.C2;
     const int dt = c.dtype & SPRK_DT_MASK;
     const long total = (long)p.nblkN * p.nchunks * p.G4 * p.NT * 16 * 8;
-    const int wCout = c.mode == 0 ? c.Cout : Cin, wCin = c.mode == 0 ? Cin : c.Cout;
+    const int wCout = c.taps == 0 ? c.Cout : Cin, wCin = c.taps == 0 ? Cin : c.Cout;
     if (int rc = transform16(c, w, ws, total, wCout, wCin, 9, kTileCK, p.G4, p.NT * 16, p.nblkN, p.nchunks, s)) return rc;
     Tile16Args k{};
     ConvArgs &a = k.c;
-    a.x = (const float *)x; a.x2 = (const float *)x2; a.bias = c.bias; a.scale = c.scale; a.shift = c.shift; a.res = nullptr;
+    a.x = (const float *)x; a.x2 = (const float *)x2; a.bias = c.ep.bias; a.scale = c.ep.scale; a.shift = c.ep.shift; a.res = nullptr;
     a.y = (float *)y;
     a.N = c.N; a.C1 = c.C1; a.C2 = c.C2; a.Hin = c.Hin; a.Win = c.Win; a.H1 = c.Hin; a.W1 = c.Win;
     a.Cout = c.Cout; a.Hout = c.Hout; a.Wout = c.Wout; a.KH = 3; a.KW = 3; a.stride = 1; a.dil = 1;
-    a.padT = c.padT; a.padL = c.padL; a.act = c.act;
+    a.padT = c.padT; a.padL = c.padL; a.act = c.ep.act;
     a.lgTC = p.lgTC; a.lgTR = p.lgTR; a.tilesX = p.tilesX; a.tilesY = p.tilesY;
-    a.vec4 = 1; a.up2 = c.up2; a.xcdRemap = xcd_on();
+    a.vec4 = 1; a.up2 = c.ep.up2; a.xcdRemap = xcd_on();
     k.w16 = ws;
     k.G4 = p.G4; k.nchunks = p.nchunks;
     k.ngFull = 18;
@@ -1137,13 +1136,13 @@ static int run_tile(const Conv16Call &c, const PlanT &p, const void *x, const vo
     k.ntiles = p.imgGroups * p.tilesX * p.tilesY;
     static const int diag = sprk::diag_env("SPRK_C16_DIAG");
     k.diag = diag;
-    prof_begin(c.kclass, c.flops, s);
-    prof_bytes(c.N * ((c.x16 ? 2.0 : 4.0) * (c.C1 + c.C2) * c.Hin * c.Win +
-                      (c.y16 ? 2.0 : 4.0) * c.Cout * c.Hout * c.Wout * (c.up2 ? 4 : 1)));
-    const int rc = dt == SPRK_DT_BF16 ? launch_tile_io<__bf16>(k, p, c.x16, c.y16, s)
-                                      : launch_tile_io<_Float16>(k, p, c.x16, c.y16, s);
+    prof_begin(kClass16, c.flops, s);
+    prof_bytes(c.N * ((c.x16() ? 2.0 : 4.0) * (c.C1 + c.C2) * c.Hin * c.Win +
+                      (c.y16() ? 2.0 : 4.0) * c.Cout * c.Hout * c.Wout * (c.ep.up2 ? 4 : 1)));
+    const int rc = dt == SPRK_DT_BF16 ? launch_tile_io<__bf16>(k, p, c.x16(), c.y16(), s)
+                                      : launch_tile_io<_Float16>(k, p, c.x16(), c.y16(), s);
     if (rc) return rc;
-    prof_end(c.kclass, s);
+    prof_end(kClass16, s);
     g_conv16_launches.fetch_add(1, std::memory_order_relaxed);
     return check_launch("conv16_tile");
 }
@@ -1164,43 +1163,40 @@ static int launch_head(const Head16Args &a, int x16, int y16, hipStream_t s) {
     return y16 ? go(conv16_head_kernel<T, CQ, CK, false, true>) : go(conv16_head_kernel<T, CQ, CK, false, false>);
 }
 
-static int run_head(const Conv16Call &c, const void *x, const float *w, void *y, void *ws, size_t ws_bytes,
+static int run_head(const Corr &c, const void *x, const float *w, void *y, void *ws, size_t ws_bytes,
                     hipStream_t s) {
     int cq, ck;
     head_shape(c, &cq, &ck);
     const int nchunks = c.C1 / ck, gc = ck / 8, coutp = 96 * cq, pxt = 64 * (8 / cq);
     const size_t need = head_ws_bytes(c);
-    if (ws_bytes < need || !ws) {
-        set_error("conv16: workspace too small (%zu < %zu)", ws_bytes, need);
-        return SPRK_EWORKSPACE;
-    }
+    if (int rc = check_ws("conv16", ws, ws_bytes, need)) return rc;
     if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)ws) & 15) != 0) {
         set_error("conv16: tensors must be 16-byte aligned");
         return SPRK_EINVAL;
     }
     const int dt = c.dtype & SPRK_DT_MASK;
     const long total = (long)nchunks * gc * coutp * 8;
-    const int wCout = c.mode == 0 ? c.Cout : c.C1, wCin = c.mode == 0 ? c.C1 : c.Cout;
+    const int wCout = c.taps == 0 ? c.Cout : c.C1, wCin = c.taps == 0 ? c.C1 : c.Cout;
     if (int rc = transform16(c, w, ws, total, wCout, wCin, 1, ck, gc, coutp, 1, nchunks, s)) return rc;
     Head16Args a{};
-    a.x = x; a.w16 = ws; a.bias = c.bias; a.scale = c.scale; a.shift = c.shift; a.y = y;
-    a.N = c.N; a.Cin = c.C1; a.Cout = c.Cout; a.HW = c.Hin * c.Win; a.act = c.act; a.nchunks = nchunks;
+    a.x = x; a.w16 = ws; a.bias = c.ep.bias; a.scale = c.ep.scale; a.shift = c.ep.shift; a.y = y;
+    a.N = c.N; a.Cin = c.C1; a.Cout = c.Cout; a.HW = c.Hin * c.Win; a.act = c.ep.act; a.nchunks = nchunks;
     a.tilesPerImage = cdiv(a.HW, pxt);
-    prof_begin(c.kclass, c.flops, s);
-    prof_bytes(c.N * ((c.x16 ? 2.0 : 4.0) * c.C1 * c.Hin * c.Win + (c.y16 ? 2.0 : 4.0) * c.Cout * c.Hout * c.Wout));
+    prof_begin(kClass16, c.flops, s);
+    prof_bytes(c.N * ((c.x16() ? 2.0 : 4.0) * c.C1 * c.Hin * c.Win + (c.y16() ? 2.0 : 4.0) * c.Cout * c.Hout * c.Wout));
     auto pick = [&](auto tag) {
         using T = decltype(tag);
-        if (cq == 4) return ck == 64 ? launch_head<T, 4, 64>(a, c.x16, c.y16, s) : launch_head<T, 4, 32>(a, c.x16, c.y16, s);
-        return launch_head<T, 1, 32>(a, c.x16, c.y16, s);
+        if (cq == 4) return ck == 64 ? launch_head<T, 4, 64>(a, c.x16(), c.y16(), s) : launch_head<T, 4, 32>(a, c.x16(), c.y16(), s);
+        return launch_head<T, 1, 32>(a, c.x16(), c.y16(), s);
     };
     const int rc = dt == SPRK_DT_BF16 ? pick(__bf16{}) : pick(_Float16{});
     if (rc) return rc;
-    prof_end(c.kclass, s);
+    prof_end(kClass16, s);
     g_conv16_launches.fetch_add(1, std::memory_order_relaxed);
     return check_launch("conv16_head");
 }
 
-int conv16_run(const Conv16Call &c, const void *xv, const void *x2v, const float *w, void *yv, void *ws, size_t ws_bytes,
+int conv16_run(const Corr &c, const void *xv, const void *x2v, const float *w, void *yv, void *ws, size_t ws_bytes,
                hipStream_t s) {
     Plan16 p;
     PlanT pt;
@@ -1208,15 +1204,12 @@ int conv16_run(const Conv16Call &c, const void *xv, const void *x2v, const float
     if (which == 3) return run_head(c, xv, w, yv, ws, ws_bytes, s);
     if (which == 2) return run_tile(c, pt, xv, x2v, w, yv, ws, ws_bytes, s);
     if (which == 0) {
-        set_error("conv16: geometry not eligible%s", (c.x16 || c.y16) ? " for 16-bit activation storage" : "");
+        set_error("conv16: geometry not eligible%s", (c.x16() || c.y16()) ? " for 16-bit activation storage" : "");
         return SPRK_EINVAL;
     }
     const float *x = (const float *)xv, *x2 = (const float *)x2v;
     float *y = (float *)yv;
-    if (ws_bytes < p.wsBytes || !ws) {
-        set_error("conv16: workspace too small (%zu < %zu)", ws_bytes, p.wsBytes);
-        return SPRK_EWORKSPACE;
-    }
+    if (int rc = check_ws("conv16", ws, ws_bytes, p.wsBytes)) return rc;
     if ((((uintptr_t)x | (uintptr_t)x2 | (uintptr_t)y | (uintptr_t)ws) & 15) != 0) {
         set_error("conv16: tensors must be 16-byte aligned");
         return SPRK_EINVAL;
@@ -1225,22 +1218,22 @@ int conv16_run(const Conv16Call &c, const void *xv, const void *x2v, const float
     // GEMM view: forward k = input channels (w[cout][cin]); backward-data k = the forward layer's output channels
     // (x = gy), n = its input channels, taps flipped.  c.* describe the GEMM (C1 + C2 = k channels, Cout = n).
     const long total = (long)p.nblkN * p.nchunks * p.G4 * p.NT * 16 * 8;
-    const int wCout = c.mode == 0 ? c.Cout : Cin, wCin = c.mode == 0 ? Cin : c.Cout;
+    const int wCout = c.taps == 0 ? c.Cout : Cin, wCin = c.taps == 0 ? Cin : c.Cout;
     const int dt = c.dtype & SPRK_DT_MASK;
     if (int rc = transform16(c, w, ws, total, wCout, wCin, KHW, p.CK, p.G4, p.NT * 16, p.nblkN, p.nchunks, s)) return rc;
 
     Conv16Args k{};
     ConvArgs &a = k.c;
-    a.x = x; a.x2 = x2; a.wT = nullptr; a.zeros = nullptr; a.bias = c.bias; a.scale = c.scale; a.shift = c.shift;
+    a.x = x; a.x2 = x2; a.wT = nullptr; a.zeros = nullptr; a.bias = c.ep.bias; a.scale = c.ep.scale; a.shift = c.ep.shift;
     a.res = nullptr; a.y = y;
     a.N = c.N; a.C1 = c.C1; a.C2 = c.C2; a.Hin = c.Hin; a.Win = c.Win; a.up1 = 0; a.H1 = c.Hin; a.W1 = c.Win;
     a.Cout = c.Cout; a.Hout = c.Hout; a.Wout = c.Wout; a.KH = c.KH; a.KW = c.KW; a.stride = 1; a.dil = 1;
-    a.padT = c.padT; a.padL = c.padL; a.act = c.act;
+    a.padT = c.padT; a.padL = c.padL; a.act = c.ep.act;
     a.lgTC = p.lgTC; a.lgTR = p.lgTR; a.tilesX = p.tilesX; a.tilesY = p.tilesY;
     a.CK = p.CK; a.R4 = 0; a.rows = 0;
     a.inRows = p.inRows; a.inCols = p.inCols; a.pitch = p.pitch; a.cplane = p.cplane; a.colOff = p.colOff; a.ldw = 0;
     a.resH = a.resW = a.resOff = 0;
-    a.vec1 = 1; a.vec2 = c.C2 ? 1 : 0; a.vec4 = (c.Wout % 4 == 0) ? 1 : 0; a.up2 = c.up2; a.deal = 1; a.xcdRemap = 1;
+    a.vec1 = 1; a.vec2 = c.C2 ? 1 : 0; a.vec4 = (c.Wout % 4 == 0) ? 1 : 0; a.up2 = c.ep.up2; a.deal = 1; a.xcdRemap = 1;
     a.xtab = 1; a.nG1 = p.nG1; a.nG2 = p.nG2;
     a.invImg = 1.0f / (float)(p.inRows * p.pitch);
     a.invPitch = 1.0f / (float)p.pitch;
@@ -1254,11 +1247,11 @@ int conv16_run(const Conv16Call &c, const void *xv, const void *x2v, const float
     k.ngLast = KHW * k.c8Last;
     static const int diag = sprk::diag_env("SPRK_C16_DIAG");
     k.diag = diag;
-    prof_begin(c.kclass, c.flops, s);
-    prof_bytes(4.0 * c.N * ((double)(c.C1 + c.C2) * c.Hin * c.Win + (double)c.Cout * c.Hout * c.Wout * (c.up2 ? 4 : 1)));
+    prof_begin(kClass16, c.flops, s);
+    prof_bytes(4.0 * c.N * ((double)(c.C1 + c.C2) * c.Hin * c.Win + (double)c.Cout * c.Hout * c.Wout * (c.ep.up2 ? 4 : 1)));
     const int rc = dt == SPRK_DT_BF16 ? launch16<__bf16>(k, p, s) : launch16<_Float16>(k, p, s);
     if (rc) return rc;
-    prof_end(c.kclass, s);
+    prof_end(kClass16, s);
     g_conv16_launches.fetch_add(1, std::memory_order_relaxed);
     return check_launch("conv16_mfma");
 }

@@ -566,16 +566,18 @@ std::atomic<long> g_wgrad16_launches{0};
 
 namespace sprk {
 
-static bool plan_wg16(const Wgrad16Call &c, PlanW *p) {
+constexpr int kClass16W = 6;  // profiling class of the 16-bit-operand backward-weight kernels
+
+static bool plan_wg16(const sprk_conv_geom &c, PlanW *p) {
     const int dt = c.dtype & SPRK_DT_MASK;
     if (dt != SPRK_DT_BF16 && dt != SPRK_DT_F16) return false;
-    static const int on = getenv("SPRK_WGRAD16") ? atoi(getenv("SPRK_WGRAD16")) : 1;   // debug: 0 = fp32 kernels
+    static const int on = knob_env("SPRK_WGRAD16", 1);   // 0 = fp32 kernels
     if (!on) return false;
     if (c.KH != 3 || c.KW != 3 || c.stride != 1 || c.dil != 1 || c.up1) return false;
-    if (c.Hout != c.H || c.Wout != c.W) return false;
-    if (c.padL < 0 || c.padL > 4 || c.padT < 0 || c.padT > 4) return false;
+    if (c.Hout != c.Hin || c.Wout != c.Win) return false;
+    if (c.pad_left < 0 || c.pad_left > 4 || c.pad_top < 0 || c.pad_top > 4) return false;
     if (c.Cout < 33 || c.Cout > 96) return false;
-    const int W = c.W, H = c.H;
+    const int W = c.Win, H = c.Hin;
     int RW;
     if (W % 64 == 0) RW = 64;
     else if (W == 32 || W == 16) RW = W;
@@ -605,14 +607,14 @@ static bool plan_wg16(const Wgrad16Call &c, PlanW *p) {
     return true;
 }
 
-static bool plan_wg1x1(const Wgrad16Call &c, Plan1 *p) {
+static bool plan_wg1x1(const sprk_conv_geom &c, Plan1 *p) {
     const int dt = c.dtype & SPRK_DT_MASK;
     if (dt != SPRK_DT_BF16 && dt != SPRK_DT_F16) return false;
-    static const int on = getenv("SPRK_WGRAD16_1X1") ? atoi(getenv("SPRK_WGRAD16_1X1")) : 1;   // debug: 0 = fp32 kernel
+    static const int on = knob_env("SPRK_WGRAD16_1X1", 1);   // 0 = fp32 kernel
     if (!on) return false;
     if (c.KH != 1 || c.KW != 1 || c.stride != 1 || c.dil != 1 || c.up1 || c.C2 != 0) return false;
-    if (c.padL != 0 || c.padT != 0 || c.Hout != c.H || c.Wout != c.W) return false;
-    const int HW = c.H * c.W, Cin = c.C1;
+    if (c.pad_left != 0 || c.pad_top != 0 || c.Hout != c.Hin || c.Wout != c.Win) return false;
+    const int HW = c.Hin * c.Win, Cin = c.C1;
     if (HW % 64 || c.Cout < 33 || Cin < 97) return false;
     if ((long)std::max(Cin, c.Cout) * HW * 4 >= (1L << 31)) return false;       // 32-bit byte offsets inside an image
     p->regPerImg = HW / 64;
@@ -633,31 +635,29 @@ static bool plan_wg1x1(const Wgrad16Call &c, Plan1 *p) {
     return true;
 }
 
-bool wgrad16_eligible(const Wgrad16Call &c) {
+bool wgrad16_eligible(const sprk_conv_geom &c) {
     PlanW p;
     Plan1 p1;
     return plan_wg16(c, &p) || plan_wg1x1(c, &p1);
 }
 
-size_t wgrad16_ws_bytes(const Wgrad16Call &c) {
+size_t wgrad16_ws_bytes(const sprk_conv_geom &c) {
     PlanW p;
     Plan1 p1;
     return plan_wg16(c, &p) ? p.wsBytes : plan_wg1x1(c, &p1) ? p1.wsBytes : 0;
 }
 
-static int wgrad16_run_1x1(const Wgrad16Call &c, const Plan1 &p, const void *x, const void *gy, float *gw, void *ws,
+static int wgrad16_run_1x1(const sprk_conv_geom &c, const Plan1 &p, const void *x, const void *gy, float *gw, void *ws,
                            size_t ws_bytes, sprk_reduce_item *item, hipStream_t s) {
-    if (ws_bytes < p.wsBytes || !ws) {
-        set_error("wgrad16 (1x1): workspace too small (%zu < %zu)", ws_bytes, p.wsBytes);
-        return SPRK_EWORKSPACE;
-    }
+    if (int rc = check_ws("wgrad16 (1x1)", ws, ws_bytes, p.wsBytes)) return rc;
     if ((((uintptr_t)x | (uintptr_t)gy) & 15) != 0) {
         set_error("wgrad16 (1x1): tensors must be 16-byte aligned");
         return SPRK_EINVAL;
     }
+    const bool x16 = (c.dtype & SPRK_DT_X16) != 0;
     Wg1Args a{};
     a.x = x; a.gy = gy; a.partial = (float *)ws;
-    a.N = c.N; a.Cin = c.C1; a.Cout = c.Cout; a.HW = c.H * c.W;
+    a.N = c.N; a.Cin = c.C1; a.Cout = c.Cout; a.HW = c.Hin * c.Win;
     a.regPerImg = p.regPerImg; a.nRegions = p.nRegions; a.perPart = p.perPart;
     static const int diag = sprk::diag_env("SPRK_C16_DIAG");
     a.diag = diag;
@@ -673,14 +673,14 @@ static int wgrad16_run_1x1(const Wgrad16Call &c, const Plan1 &p, const void *x, 
     };
     auto pick = [&](auto tag) {
         using T = decltype(tag);
-        if (c.x16) return p.wide ? go(wgrad16_1x1_kernel<T, 4, 3, 6, true>) : go(wgrad16_1x1_kernel<T, 2, 3, 6, true>);
+        if (x16) return p.wide ? go(wgrad16_1x1_kernel<T, 4, 3, 6, true>) : go(wgrad16_1x1_kernel<T, 2, 3, 6, true>);
         return p.wide ? go(wgrad16_1x1_kernel<T, 4, 3, 6, false>) : go(wgrad16_1x1_kernel<T, 2, 3, 6, false>);
     };
-    prof_begin(c.kclass, c.flops, s);
-    prof_bytes((c.x16 ? 2.0 : 4.0) * c.N * ((double)(c.C1 + c.C2) * c.H * c.W + (double)c.Cout * c.Hout * c.Wout));
+    prof_begin(kClass16W, conv_flops(c), s);
+    prof_bytes((x16 ? 2.0 : 4.0) * c.N * ((double)(c.C1 + c.C2) * c.Hin * c.Win + (double)c.Cout * c.Hout * c.Wout));
     const int rc = (c.dtype & SPRK_DT_MASK) == SPRK_DT_BF16 ? pick(__bf16{}) : pick(_Float16{});
     if (rc) return rc;
-    prof_end(c.kclass, s);
+    prof_end(kClass16W, s);
     if (int rc2 = check_launch("wgrad16_1x1")) return rc2;
     g_wgrad16_launches.fetch_add(1, std::memory_order_relaxed);
     const sprk_reduce_item it{(const float *)ws, gw, SPRK_RED_ROWS, p.parts, c.Cout * c.C1, 0, 0, 0};
@@ -689,7 +689,7 @@ static int wgrad16_run_1x1(const Wgrad16Call &c, const Plan1 &p, const void *x, 
 
 long wgrad16_launches() { return g_wgrad16_launches.load(); }
 
-int wgrad16_run(const Wgrad16Call &c, const void *x, const void *x2, const void *gy, float *gw, void *ws,
+int wgrad16_run(const sprk_conv_geom &c, const void *x, const void *x2, const void *gy, float *gw, void *ws,
                 size_t ws_bytes, sprk_reduce_item *item, hipStream_t s) {
     PlanW p;
     if (!plan_wg16(c, &p)) {
@@ -698,13 +698,11 @@ int wgrad16_run(const Wgrad16Call &c, const void *x, const void *x2, const void 
         set_error("wgrad16: geometry not eligible");
         return SPRK_EINVAL;
     }
-    if (ws_bytes < p.wsBytes || !ws) {
-        set_error("wgrad16: workspace too small (%zu < %zu)", ws_bytes, p.wsBytes);
-        return SPRK_EWORKSPACE;
-    }
+    if (int rc = check_ws("wgrad16", ws, ws_bytes, p.wsBytes)) return rc;
+    const bool x16 = (c.dtype & SPRK_DT_X16) != 0;
     Wg16Args a{};
     a.x = x; a.x2 = x2; a.gy = gy; a.partial = (float *)ws;
-    a.N = c.N; a.C1 = c.C1; a.C2 = c.C2; a.H = c.H; a.W = c.W; a.Cout = c.Cout; a.padT = c.padT; a.padL = c.padL;
+    a.N = c.N; a.C1 = c.C1; a.C2 = c.C2; a.H = c.Hin; a.W = c.Win; a.Cout = c.Cout; a.padT = c.pad_top; a.padL = c.pad_left;
     a.regX = p.regX; a.regY = p.regY; a.seg = p.seg; a.segLen = p.segLen; a.nUnits = p.nUnits; a.xcs = p.xcs; a.tail = p.tail;
     static const int diag = sprk::diag_env("SPRK_C16_DIAG");
     a.diag = diag;
@@ -728,15 +726,15 @@ int wgrad16_run(const Wgrad16Call &c, const void *x, const void *x2, const void 
             if (p.lgRW == 5) return p.MC == 6 ? go(wgrad16_kernel<T, 6, 5, X, P1>) : go(wgrad16_kernel<T, 3, 5, X, P1>);
             return p.MC == 6 ? go(wgrad16_kernel<T, 6, 4, X, P1>) : go(wgrad16_kernel<T, 3, 4, X, P1>);
         };
-        const bool pl1 = c.padL == 1;
-        if (c.x16) return pl1 ? shape(std::true_type{}, std::true_type{}) : shape(std::true_type{}, std::false_type{});
+        const bool pl1 = c.pad_left == 1;
+        if (x16) return pl1 ? shape(std::true_type{}, std::true_type{}) : shape(std::true_type{}, std::false_type{});
         return pl1 ? shape(std::false_type{}, std::true_type{}) : shape(std::false_type{}, std::false_type{});
     };
-    prof_begin(c.kclass, c.flops, s);
-    prof_bytes((c.x16 ? 2.0 : 4.0) * c.N * ((double)(c.C1 + c.C2) * c.H * c.W + (double)c.Cout * c.Hout * c.Wout));
+    prof_begin(kClass16W, conv_flops(c), s);
+    prof_bytes((x16 ? 2.0 : 4.0) * c.N * ((double)(c.C1 + c.C2) * c.Hin * c.Win + (double)c.Cout * c.Hout * c.Wout));
     const int rc = dt == SPRK_DT_BF16 ? pick(__bf16{}) : pick(_Float16{});
     if (rc) return rc;
-    prof_end(c.kclass, s);
+    prof_end(kClass16W, s);
     if (int rc2 = check_launch("wgrad16")) return rc2;
     const long n = (long)c.Cout * (c.C1 + c.C2) * 9;
     g_wgrad16_launches.fetch_add(1, std::memory_order_relaxed);

@@ -2,26 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace sprk {
+#include "corr.h"
 
-struct WinoGeom {
-    int N, C1, C2, Cout, H, W, Hout, Wout, KH, KW, stride, dil, padT, padL, up1, up2, res;
-    int pin;   // SPRK_DT_PIN: the choice must not depend on the image count or the plane size
-};
-struct WinoArgs {
-    const float *x, *x2;   // sources [N,C1,H,W], [N,C2,H,W] (x2 may be null)
-    const float *w;        // taps in the layout of the forward layer, [CoutF][CinF][3][3]
-    const float *bias, *scale, *shift;
-    float *y;              // [N,Cout,H,W]
-    float *U;              // workspace of wino_ws_bytes()
-    int N, C1, C2, H, W, Cout, padT, padL, act;
-    int mode;              // 0: forward taps w[cout][cin]; 1: backward-data taps w[k][cout] flipped
-    int kclass;            // profiling class of the main kernel launch (sprk_prof_*)
-    double flops;          // algorithmic (direct-convolution) FLOPs of this call, for the same
-    int up2;               // 1: y is [N,Cout,2H,2W], every output written to its 2x2 block (fused nn.Upsample)
-    const float *mask = nullptr;   // [N,Cout,H,W] or null: y *= d act / d (mask) (backward-data: the saved conv input)
-    int mask_act = 0;              // SPRK_ACT_* of that mask
-};
+namespace sprk {
 
 struct WinoWgArgs {
     const float *x, *x2, *gy;   // sources [N,C1,H,W], [N,C2,H,W] (x2 may be null), output gradient [N,Cout,H,W]
@@ -32,11 +15,15 @@ struct WinoWgArgs {
     double flops;
 };
 
-bool wino_eligible(const WinoGeom &g);
-bool wino_wgrad_eligible(const WinoGeom &g);
+bool wino_eligible(const Corr &c);
+size_t wino_ws_bytes(const Corr &c);
+// x, x2: sources [N,C1,H,W], [N,C2,H,W] (x2 may be null); w: the forward layer's taps (c.taps); y: [N,Cout,H,W], or
+// [N,Cout,2H,2W] with c.ep.up2 (every output written to its 2x2 block); U: workspace of wino_ws_bytes().
+// mask: [N,Cout,H,W] or null: y *= d act / d (mask), act = mask_act (backward-data: the saved conv input)
+int wino_conv(const Corr &c, const float *x, const float *x2, const float *w, float *y, float *U, const float *mask,
+              int mask_act, hipStream_t s);
+bool wino_wgrad_eligible(const sprk_conv_geom &g);
 size_t wino_wgrad_ws_bytes(int C1, int C2, int Cout);
 int wino_wgrad(const WinoWgArgs &a, hipStream_t s);
-size_t wino_ws_bytes(int C1, int C2, int Cout);
-int wino_conv(const WinoArgs &a, hipStream_t s);
 
 }  // namespace sprk

@@ -811,12 +811,15 @@ int wino_square(int H, int W) {
 
 namespace sprk {
 
-bool wino_eligible(const WinoGeom &g) {
-    static const int on = getenv("SPRK_WINO") ? atoi(getenv("SPRK_WINO")) : 1;   // debug: 0 = direct kernels only
+constexpr int kClassWino = 3;   // profiling class of the 96-channel Winograd kernel (narrower calls: 2)
+
+bool wino_eligible(const Corr &g) {
+    static const int on = knob_env("SPRK_WINO", 1);   // 0 = direct kernels only
     if (!on) return false;
-    if (g.KH != 3 || g.KW != 3 || g.stride != 1 || g.dil != 1 || g.up1 || g.res) return false;
-    if (g.Hout != g.H || g.Wout != g.W) return false;
-    const int sq = wino_square(g.H, g.W);
+    if (g.KH != 3 || g.KW != 3 || g.stride != 1 || g.dil != 1 || g.up1 || g.mfma_only || g.ep.res) return false;
+    if (g.Hout != g.Hin || g.Wout != g.Win) return false;
+    const int H = g.Hin, W = g.Win;
+    const int sq = wino_square(H, W);
     if (sq < 0) return false;
     const int TR = sq ? Geo<1>::TR : Geo<0>::TR, TC = sq ? Geo<1>::TC : Geo<0>::TC;
     if (g.padL < 0 || g.padL > 4 || g.padT < 0) return false;
@@ -826,44 +829,46 @@ bool wino_eligible(const WinoGeom &g) {
     // too few workgroups for 256 CUs: the direct kernel spreads the same layer over all of them, this one does 4/9 of
     // the MFMA work on as many CUs as it has 256-pixel tiles — break-even near 256 x 4/9 = 114 (measured: 96->96 at
     // 128x16x16, 128 tiles, 68 us direct)
-    if (!g.pin && (long)g.N * (g.H / TR) * (g.W / TC) * groups < 128) return false;
-    if ((long)4 * g.H * g.W * 4 >= 0x7FFFFFFFL) return false;               // 4 planes inside one buffer range
+    if (!g.pin() && (long)g.N * (H / TR) * (W / TC) * groups < 128) return false;
+    if ((long)4 * H * W * 4 >= 0x7FFFFFFFL) return false;               // 4 planes inside one buffer range
     return true;
 }
 
-size_t wino_ws_bytes(int C1, int C2, int Cout) {
-    const int NT = nt_of(Cout), groups = cdiv(Cout, NT * 16), nch = cdiv(C1, CK) + cdiv(C2, CK);
+size_t wino_ws_bytes(const Corr &c) {
+    const int NT = nt_of(c.Cout), groups = cdiv(c.Cout, NT * 16), nch = cdiv(c.C1, CK) + cdiv(c.C2, CK);
     return (size_t)groups * nch * ufloats_of(NT) * sizeof(float);
 }
 
-int wino_conv(const WinoArgs &w, hipStream_t s) {
+int wino_conv(const Corr &w, const float *x, const float *x2, const float *taps, float *y, float *U, const float *mask,
+              int mask_act, hipStream_t s) {
     const int NT = nt_of(w.Cout), groups = cdiv(w.Cout, NT * 16);
+    const int kclass = w.Cout > 48 ? kClassWino : 2;
     KArgs a{};
-    a.x = w.x; a.x2 = w.x2; a.U = w.U; a.bias = w.bias; a.scale = w.scale; a.shift = w.shift; a.y = w.y;
-    a.N = w.N; a.C1 = w.C1; a.C2 = w.C2; a.H = w.H; a.W = w.W; a.Cout = w.Cout; a.padT = w.padT; a.padL = w.padL;
-    a.act = w.act;
-    a.up2 = w.up2;
-    a.mask = w.up2 ? nullptr : w.mask;
-    a.mact = w.mask_act;
+    a.x = x; a.x2 = x2; a.U = U; a.bias = w.ep.bias; a.scale = w.ep.scale; a.shift = w.ep.shift; a.y = y;
+    a.N = w.N; a.C1 = w.C1; a.C2 = w.C2; a.H = w.Hin; a.W = w.Win; a.Cout = w.Cout; a.padT = w.padT; a.padL = w.padL;
+    a.act = w.ep.act;
+    a.up2 = w.ep.up2 ? 1 : 0;
+    a.mask = a.up2 ? nullptr : mask;
+    a.mact = mask_act;
     a.xcd = xcd_on();
     static const int diag = sprk::diag_env("SPRK_WINO_DIAG");   // timing experiments only
     a.diag = diag;
-    const int sq = wino_square(w.H, w.W);
-    a.tilesX = w.W / (sq ? Geo<1>::TC : Geo<0>::TC); a.tilesY = w.H / (sq ? Geo<1>::TR : Geo<0>::TR);
+    const int sq = wino_square(a.H, a.W);
+    a.tilesX = a.W / (sq ? Geo<1>::TC : Geo<0>::TC); a.tilesY = a.H / (sq ? Geo<1>::TR : Geo<0>::TR);
     a.ntiles = a.tilesX * a.tilesY * w.N;
     a.nc1 = cdiv(w.C1, CK);
     a.nch = a.nc1 + cdiv(w.C2, CK);
-    if ((((uintptr_t)w.x | (uintptr_t)w.x2 | (uintptr_t)w.y | (uintptr_t)w.U) & 15) != 0) {
+    if ((((uintptr_t)x | (uintptr_t)x2 | (uintptr_t)y | (uintptr_t)U) & 15) != 0) {
         set_error("wino_conv: tensors must be 16-byte aligned");
         return SPRK_EINVAL;
     }
     const long total = (long)groups * a.nch * NT * CK * 16;
-    if (int rc = wprep_site(wprep_item(WPREP_WINO, w.w, w.U, total, {w.Cout, w.C1, w.C2, a.nc1, a.nch, NT, groups, w.mode}), s))
+    if (int rc = wprep_site(wprep_item(WPREP_WINO, taps, U, total, {w.Cout, w.C1, w.C2, a.nc1, a.nch, NT, groups, w.taps}), s))
         return rc;
     // persistent workgroups, one per CU: each walks tiles blockIdx.x, + gridDim.x, ... and starts the next tile's
     // loads under its output transform (same-box A/B: +5..7 % on the 48-channel layers with their short K loops,
     // +1.5 % on the 96-channel ones).  SPRK_WINO_PERSIST=0: one workgroup per tile.
-    static const int persist = getenv("SPRK_WINO_PERSIST") ? atoi(getenv("SPRK_WINO_PERSIST")) : 1;
+    static const int persist = knob_env("SPRK_WINO_PERSIST", 1);
     const dim3 grid(persist ? std::min(a.ntiles, std::max(1, num_cus() / groups)) : a.ntiles, groups);
     const size_t lds = lds_bytes_of(NT);
     auto launch = [&](auto kernel) {
@@ -877,11 +882,11 @@ int wino_conv(const WinoArgs &w, hipStream_t s) {
     if (!dbg) { hipMalloc(&dbg, 4 * 8 * 16 * 4); hipMemset(dbg, 0, 4 * 8 * 16 * 4); }
     a.dbg = dbg;
 #endif
-    prof_begin(w.kclass, w.flops, s);
+    prof_begin(kclass, w.flops, s);
     if (int rc = NT == 6 ? (sq ? launch(wino_conv_kernel<6, 1>) : launch(wino_conv_kernel<6, 0>))
                          : (sq ? launch(wino_conv_kernel<3, 1>) : launch(wino_conv_kernel<3, 0>)))
         return rc;
-    prof_end(w.kclass, s);
+    prof_end(kclass, s);
 #ifdef WINO_STAMP
     if (NT == 6 && !sq && ++dumped == 5 && getenv("SPRK_WINO_STAMP")) {
         hipDeviceSynchronize();
@@ -901,12 +906,13 @@ int wino_conv(const WinoArgs &w, hipStream_t s) {
     return SPRK_OK;
 }
 
-bool wino_wgrad_eligible(const WinoGeom &g) {
-    static const int on = getenv("SPRK_WINO_WGRAD") ? atoi(getenv("SPRK_WINO_WGRAD")) : 1;   // debug: 0 = direct kernel only
+bool wino_wgrad_eligible(const sprk_conv_geom &g) {
+    static const int on = knob_env("SPRK_WINO_WGRAD", 1);   // 0 = direct kernel only
     if (!on) return false;
     if (g.KH != 3 || g.KW != 3 || g.stride != 1 || g.dil != 1 || g.up1) return false;
-    if (g.Hout != g.H || g.Wout != g.W || g.H % WRH || g.W % WRW) return false;
-    if (g.padL < 0 || g.padL > 4 || g.padT < 0 || g.padT > 4) return false;   // padT <= 4: inner regions see no border
+    const int H = g.Hin, W = g.Win, padT = g.pad_top, padL = g.pad_left;
+    if (g.Hout != H || g.Wout != W || H % WRH || W % WRW) return false;
+    if (padL < 0 || padL > 4 || padT < 0 || padT > 4) return false;   // padT <= 4: inner regions see no border
     if (g.Cout < 81 || g.Cout > 96) return false;   // two halves of 3 channel tiles
     int g48, tail;
     if (g.C1 < 1 || !wg_split(g.C1, &g48, &tail)) return false;
@@ -917,11 +923,11 @@ bool wino_wgrad_eligible(const WinoGeom &g) {
     // 191 -> 178 us; 1024 regions (16^2 planes at 256 images, 32^2 at 64): 114 -> 132, 178 -> 247, 164 -> 242 us: slower.
     // A one-channel tail group (the raw image concatenated into decode_block_1) is a launch of its own that costs a
     // third of a full group whatever the size: 96+1->96 at 32 x 64^2 196 -> 236 us, so layers with a tail need 8192.
-    static const long min_regions = getenv("SPRK_WINO_WGRAD_MIN") ? atol(getenv("SPRK_WINO_WGRAD_MIN")) : 0;   // sweeps
+    static const long min_regions = knob_env("SPRK_WINO_WGRAD_MIN", 0);   // sweeps
     const bool has_tail = (g.C1 % 48) != 0 || (g.C2 % 48) != 0;
     const long need = min_regions > 0 ? min_regions : (has_tail ? 8192 : 2048);
-    if ((long)g.N * (g.H / WRH) * (g.W / WRW) < need) return false;
-    if ((long)48 * g.H * g.W * 4 >= 0x7FFFFFFFL || (long)g.Cout * g.H * g.W * 4 >= 0x7FFFFFFFL) return false;
+    if ((long)g.N * (H / WRH) * (W / WRW) < need) return false;
+    if ((long)48 * H * W * 4 >= 0x7FFFFFFFL || (long)g.Cout * H * W * 4 >= 0x7FFFFFFFL) return false;
     return true;
 }
 

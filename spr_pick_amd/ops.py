@@ -13,25 +13,9 @@ import torch
 from . import _lib
 from . import torch_ops  # noqa: F401  (registers torch.ops.sprk.*)
 from ._lib import ACT_LEAKY, ACT_NONE, ACT_RELU, ConvEpilogue, ConvGeom, check  # noqa: F401
-from .torch_ops import geom_list
+from .torch_ops import _p, _stream, _ws, geom_list
 
 _S = torch.ops.sprk
-
-
-def _stream(t):
-    """torch's current stream on the device that holds ``t`` (a kernel must be enqueued on a stream of the
-    device its pointers live on).  One process drives one GPU here; a tensor on another device than the
-    process's current one is a set-up error and raises instead of launching on the wrong card."""
-    dev = t.device
-    if dev.index is not None and dev.index != torch.cuda.current_device():
-        raise _lib.SprkError("tensor on %s but the current device is cuda:%d — call torch.cuda.set_device(%d) "
-                             "(Denoiser / DenoiserTrainer / DenoiserEvaluator do it for their own device)"
-                             % (dev, torch.cuda.current_device(), dev.index))
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _need_gpu(*ts):
@@ -83,10 +67,6 @@ def _grad_dest(w):
 
 def flush_reductions(like):
     _S.reduce_pending(like)
-
-
-def _ws(nbytes, like):
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=like.device)
 
 
 class WeightPrep:

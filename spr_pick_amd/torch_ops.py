@@ -22,6 +22,9 @@ _NAMES = []
 
 
 def _stream(t):
+    """torch's current stream on the device that holds ``t`` (a kernel must be enqueued on a stream of the
+    device its pointers live on).  One process drives one GPU here; a tensor on another device than the
+    process's current one is a set-up error and raises instead of launching on the wrong card."""
     dev = t.device
     if dev.index is not None and dev.index != torch.cuda.current_device():
         raise _lib.SprkError("tensor on %s but the current device is cuda:%d — call torch.cuda.set_device(%d) "

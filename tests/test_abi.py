@@ -93,3 +93,63 @@ def test_torch_library_registration_and_fake_shapes():
     from spr_pick_amd import _lib
     with pytest.raises(_lib.SprkError):
         ops.shift_maxpool2(torch.zeros(1, 1, 4, 4))
+
+
+# N, C1, C2, Hin, Win, up1, Cout, K, stride, dil, pad (top, bottom, left, right)
+SH, PL, P0 = (2, 0, 1, 1), (1, 1, 1, 1), (0, 0, 0, 0)      # blind-spot shift padding, plain "same" padding, valid
+WS_GEOMS = [
+    (8, 1, 0, 64, 64, 0, 48, 3, 1, 1, SH), (32, 48, 0, 64, 64, 0, 48, 3, 1, 1, SH), (8, 48, 0, 8, 8, 0, 48, 3, 1, 1, SH),
+    (8, 48, 0, 2, 2, 0, 48, 3, 1, 1, SH), (8, 48, 48, 4, 4, 1, 96, 3, 1, 1, SH), (64, 96, 48, 32, 32, 0, 96, 3, 1, 1, SH),
+    (256, 96, 48, 16, 16, 0, 96, 3, 1, 1, SH), (32, 96, 1, 64, 64, 0, 96, 3, 1, 1, SH), (4, 96, 1, 64, 64, 1, 96, 3, 1, 1, PL),
+    (128, 96, 0, 64, 64, 0, 96, 3, 1, 1, SH), (8, 96, 0, 16, 16, 0, 96, 3, 1, 1, SH), (1, 96, 0, 1024, 1024, 0, 96, 3, 1, 1, PL),
+    (64, 90, 0, 8, 96, 0, 70, 3, 1, 1, PL), (130, 48, 10, 16, 256, 0, 88, 3, 1, 1, (1, 1, 2, 0)),
+    (6, 40, 0, 24, 48, 0, 70, 3, 1, 1, (1, 1, 2, 0)),
+    (16, 384, 0, 64, 64, 0, 384, 1, 1, 1, P0), (16, 384, 0, 64, 64, 0, 96, 1, 1, 1, P0), (2, 96, 0, 64, 64, 0, 2, 1, 1, 1, P0),
+    (100, 128, 0, 20, 16, 0, 200, 1, 1, 1, P0), (16, 96, 0, 64, 64, 0, 96, 1, 1, 1, P0),
+    (4, 1, 0, 64, 64, 0, 32, 7, 2, 1, P0), (4, 32, 0, 29, 29, 0, 32, 3, 1, 1, P0), (4, 32, 0, 27, 27, 0, 32, 3, 1, 2, P0),
+    (4, 32, 0, 21, 21, 0, 64, 3, 2, 2, P0), (4, 32, 0, 17, 17, 0, 64, 1, 2, 1, P0), (4, 64, 0, 3, 3, 0, 128, 3, 1, 1, P0),
+    (1, 1, 0, 40, 56, 0, 32, 7, 1, 1, (31, 31, 31, 31)), (1, 64, 0, 48, 52, 0, 64, 3, 1, 8, P0),
+    (3, 5, 0, 13, 9, 0, 7, 3, 1, 1, (1, 2, 0, 1)),
+]
+
+
+def test_workspace_query_covers_the_dispatch():
+    """A describe-mode call handed exactly sprk_conv2d_fwd_ws_bytes (sprk_conv2d_bwd_data_ws_bytes) bytes never reports
+    SPRK_EWORKSPACE: the query and the dispatcher agree on every kernel the call can take, whatever its operand type,
+    flags and epilogue.  With fp32 activation tensors every one of these layers has a kernel, so the call succeeds;
+    with SPRK_DT_X16 / _Y16 it may be refused (SPRK_EINVAL: no 16-bit-storage kernel), never for its workspace.
+    Planning runs on the host (no launch in describe mode), so this needs no GPU."""
+    import ctypes
+    from spr_pick_amd import _lib
+    L = _lib.lib()
+    OK, EWORKSPACE = 0, -2
+    W, WS, AUX = 0x100000, 0x200000, 0x300000          # never dereferenced in describe mode; 16-byte aligned
+    store16 = _lib.DT_X16 | _lib.DT_Y16
+    flags = (0, _lib.DT_FORCE, _lib.DT_PIN, store16, _lib.DT_NAIVE)
+    calls = 0
+    for (N, C1, C2, H, Wd, up1, Cout, K, stride, dil, (pt, pb, pl, pr)) in WS_GEOMS:
+        Ho = (H + pt + pb - dil * (K - 1) - 1) // stride + 1
+        Wo = (Wd + pl + pr - dil * (K - 1) - 1) // stride + 1
+        for dt in [b | f for b in (_lib.DT_F32, _lib.DT_BF16, _lib.DT_F16) for f in flags]:
+            g = _lib.ConvGeom(N, C1, C2, H, Wd, up1, Cout, Ho, Wo, K, K, stride, dil, pt, pl, dt)
+            what = (tuple(getattr(g, f) for f, _ in g._fields_),)
+            need_f = L.sprk_conv2d_fwd_ws_bytes(ctypes.byref(g))
+            need_b = L.sprk_conv2d_bwd_data_ws_bytes(ctypes.byref(g))
+            eps = (None,
+                   _lib.ConvEpilogue(AUX, None, None, None, 0, 0, 0, _lib.ACT_LEAKY, 0),
+                   _lib.ConvEpilogue(AUX, None, None, None, 0, 0, 0, _lib.ACT_LEAKY, 1),
+                   _lib.ConvEpilogue(None, None, None, AUX, Ho, Wo, 0, _lib.ACT_RELU, 0),
+                   _lib.ConvEpilogue(None, AUX, AUX, None, 0, 0, 0, _lib.ACT_RELU, 0))
+            for ep in eps:
+                item = _lib.WprepItem()
+                rc = L.sprk_conv2d_fwd_wprep(W, ctypes.byref(g), None if ep is None else ctypes.byref(ep), WS, need_f,
+                                             ctypes.byref(item))
+                assert rc != EWORKSPACE, ("fwd", what, need_f, L.sprk_last_error())
+                assert rc == OK or (dt & store16), ("fwd", what, rc, L.sprk_last_error())
+                calls += 1
+            item = _lib.WprepItem()
+            rc = L.sprk_conv2d_bwd_data_wprep(W, ctypes.byref(g), WS, need_b, ctypes.byref(item))
+            assert rc != EWORKSPACE, ("bwd_data", what, need_b, L.sprk_last_error())
+            assert rc == OK or (dt & store16), ("bwd_data", what, rc, L.sprk_last_error())
+            calls += 1
+    assert calls == len(WS_GEOMS) * 15 * 6
