@@ -108,7 +108,8 @@ typedef struct sprk_conv_epilogue {
  * entry points exist).  A binding must refuse a library whose sprk_version() differs from the header it was
  * written against, and may compare sprk_struct_bytes(0 | 1 | 2) with its own sizeof(sprk_conv_geom |
  * sprk_conv_epilogue | sprk_reduce_item). */
-#define SPRK_ABI_VERSION 430   /* 430: sprk_contam_* */
+#define SPRK_ABI_VERSION 430   /* 430: sprk_contam_*; sprk_ingest_* joined it compatibly (no signature or struct changed:
+                                * a binding that needs them finds a library without them by the missing symbol) */
 const char *sprk_last_error(void);
 int sprk_version(void);
 size_t sprk_struct_bytes(int which);
@@ -432,6 +433,34 @@ size_t sprk_contam_ws_bytes(int H, int W);
 int sprk_contam_mask(const float *img, int H, int W, int crop, int ksize, double k_low, double k_high, int radius,
                      uint8_t *mask_out, uint8_t *set_bitmap_out, double *stats_out, void *ws, size_t ws_bytes,
                      void *stream);
+
+/* ---- micrograph ingest ------------------------------------------------------------------
+ * replaces the README's `newstack -bin N` step plus the host half of the evaluation feed
+ * (utils/loader.py:49-59 load_mrc, cv2.normalize, to_tensor, the transpose and the reflect padding of
+ * datasets/image_wrapper.py:197-249).  raw: the sample block of ONE 2-D MRC image as it sits in the file
+ * ([ny,nx] row-major, mode 0 int8 / 1 int16 / 2 float32 / 6 uint16), in a device buffer that starts 16-byte
+ * aligned.  Inputs are taken to be finite.
+ * sprk_ingest_bin: binned_out [by,bx] fp32 = the mean of every bin x bin block of the centred area
+ *   (by = ny/bin, bx = nx/bin, first sample (ny%bin)/2, (nx%bin)/2); integer modes: exact integer sum, one
+ *   correctly rounded fp32 division by float(bin*bin); float32: fp32 adds from 0.0f in row-major order within
+ *   the block, then that division; bin = 1: a conversion.  range_out float[2] device: min and max of binned_out.
+ * sprk_ingest_finish: q = uint8(trunc((x*scale + shift) * 255.0f)) with scale = 1/(max-min), shift = -min*scale
+ *   formed in double (0 when max-min <= DBL_EPSILON) and applied as separate fp32 operations, then
+ *   u8_out  (nullable) [by,bx] = q;
+ *   net_out (nullable) [S,S] fp32, net[a][b] = q[refl(b,by)][refl(a,bx)] / 255.0f — transposed, reflect-padded
+ *       (np.pad "reflect", folding as often as needed) to S, a multiple of 32 with S >= by, bx (unused when
+ *       net_out is null).  At least one of the two outputs.
+ * A few launches on `stream`, no host synchronisation. */
+#define SPRK_MRC_INT8 0
+#define SPRK_MRC_INT16 1
+#define SPRK_MRC_FLOAT32 2
+#define SPRK_MRC_UINT16 6
+#define SPRK_INGEST_MAX_BIN 16
+size_t sprk_ingest_ws_bytes(int ny, int nx, int bin);
+int sprk_ingest_bin(const void *raw, int mode, int ny, int nx, int bin, float *binned_out, float *range_out, void *ws,
+                    size_t ws_bytes, void *stream);
+int sprk_ingest_finish(const float *binned, int by, int bx, const float *range, uint8_t *u8_out, float *net_out, int S,
+                       void *stream);
 
 /* ---- in-library kernel timing (bench.py's roofline leg) --------------------------------
  * sprk_prof_enable(mask): bit k set = every launch of kernel class k is bracketed by HIP events

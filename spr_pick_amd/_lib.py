@@ -111,6 +111,9 @@ _SIGS = {
     "sprk_contam_ws_bytes": (c_sz, [c_i, c_i]),
     "sprk_contam_mask": (c_i, [c_f, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_vp, c_vp, c_vp, c_vp, c_sz,
                                c_vp]),
+    "sprk_ingest_ws_bytes": (c_sz, [c_i, c_i, c_i]),
+    "sprk_ingest_bin": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_f, c_f, c_vp, c_sz, c_vp]),
+    "sprk_ingest_finish": (c_i, [c_f, c_i, c_i, c_f, c_vp, c_f, c_i, c_vp]),
     "sprk_gather_patches": (c_i, [c_vp, c_i, c_vp, c_vp, c_vp, c_f, c_i, c_i, c_i, c_vp]),
     "sprk_prof_enable": (None, [c_i]),
     "sprk_prof_collect": (c_i, [c_i, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
@@ -136,7 +139,10 @@ def lib():
                             "or __graft_entry__.build(); spr_pick_amd has no fallback path" % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in _SIGS.items():
-            fn = getattr(L, name)
+            fn = getattr(L, name, None)
+            if fn is None:      # an older library of the same ABI version (entry points are added compatibly)
+                raise SprkError("libsprk.so at %s does not export %s — rebuild it (make -C spr_pick_amd/csrc)"
+                                % (LIB_PATH, name))
             fn.restype = res
             fn.argtypes = args
         # a stale library (or a newer one) would read past the geometry struct or misplace arguments silently

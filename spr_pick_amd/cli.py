@@ -1,6 +1,6 @@
 """``joint`` command line (cli/cli.py, cli/cmds/train.py:24-300, cli/cmds/eval.py:15-71 of the
 reference): ``joint train start|resume`` and ``joint eval`` with the same flags and the same
-flag -> configuration mapping.  Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
+flag -> configuration mapping, plus ``joint bin`` (the README's ``newstack -bin`` preparation, on the GPU).  Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
 under ``python -m torch.distributed.run --nproc-per-node N -m spr_pick_amd -- ...`` (keep the ``--``)."""
 import argparse
 
@@ -30,6 +30,18 @@ def _shared_train_args(p, start):
     p.add_argument("--validation_batch_size", type=int, help="Batch size to use for validation images.")
     p.add_argument("--patch_size", type=int, help="Patch size to use for training (square).")
     p.add_argument("--fraction", help="percent fraction of frames.")
+
+
+def _bin_factor(text):
+    """--bin N: an integer in 1..ingest.MAX_BIN (= SPRK_INGEST_MAX_BIN; imported here so that the parser alone stays light)."""
+    from .ingest import MAX_BIN
+    try:
+        n = int(text)
+    except ValueError:
+        n = 0
+    if not 1 <= n <= MAX_BIN:
+        raise argparse.ArgumentTypeError("bin factor must be an integer in 1..%d, got %r" % (MAX_BIN, text))
+    return n
 
 
 def build_parser():
@@ -66,6 +78,15 @@ def build_parser():
     ev.add_argument("--contamination", action="store_true",
                     help="exclude picks on ice contamination, carbon edges and holes (the reference's find_contamination, "
                          "computed on the GPU); writes {name}_contam.png")
+    ev.add_argument("--bin", type=_bin_factor, metavar="N",
+                    help="the dataset holds RAW micrographs (MRC mode 0/1/2/6): bin each N x N, normalise and pad it on "
+                         "the GPU instead of preparing binned copies; for N > 1 also writes {name}_scores_unbinned.txt")
+
+    bn = cmds.add_parser("bin", help="Bin raw micrographs N x N on the GPU (replaces the `newstack -bin N` preparation).")
+    bn.add_argument("--dataset", "-d", required=True, help="Table (image_name, path) or directory of raw MRC micrographs.")
+    bn.add_argument("--bin", type=_bin_factor, required=True, metavar="N", help="bin factor (at most 16, SPRK_INGEST_MAX_BIN)")
+    bn.add_argument("--out", "-o", required=True, help="Directory for {name}.mrc (float32), images.txt and labels.txt.")
+    bn.add_argument("--labels", "-l", help="Particle coordinates of the raw micrographs; written binned to labels.txt.")
     return parser
 
 
@@ -113,7 +134,8 @@ def run_train(args, parser):
 
 def run_eval(args):
     from .eval import DenoiserEvaluator
-    evaluator = DenoiserEvaluator(args["model"], runs_dir=args["runs_dir"], contamination=args.get("contamination", False))
+    evaluator = DenoiserEvaluator(args["model"], runs_dir=args["runs_dir"], contamination=args.get("contamination", False),
+                                  bin=args.get("bin"))
     for flag, key in (("batch_size", ConfigValue.TEST_MINIBATCH_SIZE), ("nms", ConfigValue.NMS),
                       ("num", ConfigValue.NUM_EVAL)):
         if args.get(flag) is not None:
@@ -122,6 +144,11 @@ def run_eval(args):
     evaluator.set_test_gt_data(args["gt_dataset"])
     evaluator.evaluate()
     return evaluator
+
+
+def run_bin(args):
+    from . import ingest
+    return ingest.bin_dataset(args["dataset"], args["bin"], args["out"], labels=args.get("labels"))
 
 
 def start(argv=None):
@@ -133,4 +160,6 @@ def start(argv=None):
     args = vars(parser.parse_args(argv))
     if args["command"] == "train":
         return run_train(args, parser)
+    if args["command"] == "bin":
+        return run_bin(args)
     return run_eval(args)

@@ -1,0 +1,257 @@
+"""Device-side micrograph ingest: raw aligned micrographs -> the network's input, without the
+``newstack -bin N`` copy of the dataset the upstream README starts with and without the host passes of
+``micrograph_io.load_image`` + ``MicrographFeed`` (min-max, quantise, /255, transpose, reflect-pad).
+
+The file's sample block is read straight into a pinned buffer, uploaded once (non-blocking) and decoded, binned,
+ranged, normalised and laid out by csrc/ingest.hip (``torch.ops.sprk.ingest_bin`` / ``ingest_finish``).  The result
+is bit for bit what the host path produces from the binned image: ``binned_uint8(path, N)`` equals ``load_image`` of
+the float32 MRC that ``joint bin --bin N`` writes, and ``ingest(path, 1)`` equals ``MicrographFeed``'s tensor.
+
+Coordinates: x runs along nx (columns), y along ny (rows) — the frame of the label tables and of ``*_scores.txt``.
+Bin factor N keeps the centred area: binned pixel (x, y) covers samples ox + N*x .. ox + N*x + N-1 (oy likewise)."""
+import logging
+import os
+
+import numpy as np
+import torch
+
+from . import micrograph_io, sampler as sampler_mod, torch_ops
+from .datasets import DetectionDataset
+
+MAX_BIN = torch_ops.INGEST_MAX_BIN
+logger = logging.getLogger("joint.ingest")
+_HEADER_BYTES = 1024
+
+
+def check_bin(N):
+    if not isinstance(N, (int, np.integer)) or not 1 <= N <= MAX_BIN:
+        raise ValueError("bin factor must be an integer in 1..%d, got %r" % (MAX_BIN, N))
+    return int(N)
+
+
+def binned_geometry(ny, nx, N):
+    """-> (by, bx, oy, ox): size of the binned image and the first sample of its first block."""
+    N = check_bin(N)
+    by, bx = ny // N, nx // N
+    if by < 1 or bx < 1:
+        raise ValueError("a %dx%d image has no %dx%d block" % (ny, nx, N, N))
+    return by, bx, (ny % N) // 2, (nx % N) // 2
+
+
+def to_unbinned(x, y, N, ox, oy):
+    """Binned pixel -> the sample at the centre of its block (the upper-left of the four central ones for even N)."""
+    return ox + N * x + N // 2, oy + N * y + N // 2
+
+
+def to_binned(x, y, N, ox, oy, bx, by):
+    """Sample -> (x, y of the binned pixel whose block holds it, inside); ``inside`` is False for samples in the margin
+    that binning drops (outside [0, bx) x [0, by)).  Inverse of ``to_unbinned``."""
+    xb, yb = (np.asarray(x) - ox) // N, (np.asarray(y) - oy) // N
+    return xb, yb, (xb >= 0) & (xb < bx) & (yb >= 0) & (yb < by)
+
+
+def require_mrc(path):
+    if os.path.splitext(path)[1] != ".mrc":
+        raise ValueError("%s: raw micrograph ingest (--bin) reads MRC files only; convert TIFF / PNG inputs, or "
+                         "evaluate them without --bin" % path)
+
+
+def read_header(path, f):
+    """The 1024-byte MRC header of an open file -> (MRCHeader, byte offset of the samples).  Refuses what
+    ``load_image`` refuses: unknown modes and stacks."""
+    head = f.read(_HEADER_BYTES)
+    if len(head) < _HEADER_BYTES:
+        raise ValueError("MRC file shorter than its 1024-byte header")
+    header = micrograph_io.MRCHeader._make(micrograph_io._HEADER.unpack(head))
+    if header.mode not in micrograph_io._MODES:
+        raise ValueError("Unsupported MRC mode: %d" % header.mode)
+    if header.nz != 1:
+        raise ValueError("%s: expected a single 2-D micrograph, got shape %s" % (path, (header.nz, header.ny, header.nx)))
+    if header.ny < 1 or header.nx < 1 or header.next < 0:
+        raise ValueError("%s: bad MRC header (nx %d, ny %d, next %d)" % (path, header.nx, header.ny, header.next))
+    return header, _HEADER_BYTES + header.next
+
+
+class RawReader:
+    """File -> device bytes through two pinned slots, each as large as the largest file seen so far and re-used only
+    after the copy that last read it has completed (its event) — ``feed.PinnedRing`` for buffers of varying size.  The
+    read of micrograph k+1 therefore overlaps the upload and the network pass of micrograph k without a second thread."""
+
+    SLOTS = 2
+
+    def __init__(self, device="cuda"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("micrograph ingest runs on the GPU only (device %s)" % self.device)
+        self._bufs = [None] * self.SLOTS
+        self._events = [None] * self.SLOTS
+        self._next = 0
+
+    def _slot(self, nbytes):
+        k = self._next
+        self._next = (k + 1) % self.SLOTS
+        if self._events[k] is not None:
+            self._events[k].synchronize()
+            self._events[k] = None
+        if self._bufs[k] is None or self._bufs[k].numel() < nbytes:
+            self._bufs[k] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        return k
+
+    def read(self, path):
+        """-> (uint8 CUDA tensor with the ny*nx samples as they sit in the file, MRCHeader).  The upload is in flight
+        on the current stream when this returns."""
+        require_mrc(path)
+        with open(path, "rb") as f:
+            header, start = read_header(path, f)
+            nbytes = header.ny * header.nx * np.dtype(micrograph_io._MODES[header.mode]).itemsize
+            k = self._slot(nbytes)
+            f.seek(start)
+            got = f.readinto(memoryview(self._bufs[k].numpy())[:nbytes])
+        if got != nbytes:
+            raise ValueError("%s: %d bytes of samples, the header promises %d" % (path, got, nbytes))
+        raw = torch.empty(nbytes, dtype=torch.uint8, device=self.device)     # the allocator aligns far beyond 16 bytes
+        raw.copy_(self._bufs[k][:nbytes], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._events[k] = ev
+        return raw, header
+
+
+_readers = {}
+
+
+def _reader(device):
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if device not in _readers:
+        _readers[device] = RawReader(device)
+    return _readers[device]
+
+
+def read_raw(path, device="cuda"):
+    """-> (raw uint8 CUDA tensor, MRCHeader) through the device's shared ``RawReader``."""
+    return _reader(device).read(path)
+
+
+def _bin(path, N, device):
+    N = check_bin(N)
+    raw, header = read_raw(path, device)
+    geometry = binned_geometry(header.ny, header.nx, N)
+    binned, rng = torch.ops.sprk.ingest_bin(raw, header.mode, header.ny, header.nx, N)
+    return binned, rng, geometry
+
+
+def binned(path, bin, device="cuda"):
+    """-> (float32 CUDA tensor [by, bx]: the N x N block means, geometry) — what ``joint bin`` writes."""
+    b, _, geometry = _bin(path, bin, device)
+    return b, geometry
+
+
+def binned_uint8(path, bin, device="cuda"):
+    """-> uint8 array [by, bx]: ``micrograph_io.load_image`` of the binned micrograph."""
+    b, rng, _ = _bin(path, bin, device)
+    u8, _ = torch.ops.sprk.ingest_finish(b, rng, True, False)
+    return u8.cpu().numpy()
+
+
+def ingest(path, bin, device="cuda"):
+    """-> (network input float32 CUDA [1, 1, S, S], (by, bx), (by, bx, oy, ox)): the binned micrograph min-max
+    quantised, /255, transposed and reflect-padded, as ``MicrographFeed`` hands it to the network."""
+    b, rng, geometry = _bin(path, bin, device)
+    _, net = torch.ops.sprk.ingest_finish(b, rng, False, True)
+    return net[None, None], geometry[:2], geometry
+
+
+class RawMicrographFeed:
+    """``feed.MicrographFeed`` for raw micrographs: same rows (``micrograph_io.read_image_table``), same order
+    (``count`` wrapping, ``rank`` / ``world`` striding), same items — but a file is read when its turn comes (nothing
+    is held in memory) and its tensor comes from ``ingest``.  IMAGE_SHAPE is [1, bx, by] (tensors are transposed), the
+    target is all zeros (evaluation has no labels to draw), BIN_GEOMETRY carries (by, bx, oy, ox)."""
+
+    def __init__(self, rows, bin, count=None, device="cuda", rank=0, world=1, gt=None):
+        self.bin = check_bin(bin)
+        self.device = torch.device(device)
+        self.gt = gt or {}
+        images = {}
+        for source, name, path in rows:                      # grouping and order of feed.load_micrographs
+            images.setdefault(source, {})[name] = path
+        self.items = [(path, name) for name, path in next(iter(images.values())).items()] if images else []
+        if not self.items:
+            raise ValueError("empty evaluation set")
+        for path, _ in self.items:                           # before the first micrograph is evaluated, not at its turn
+            require_mrc(path)
+        order = sampler_mod.sequential_indices(len(self.items), count)
+        self.order = [(pos, k) for pos, k in enumerate(order) if pos % world == rank]
+        self._reader = _reader(self.device)
+
+    def __len__(self):
+        return len(self.order)
+
+    def __iter__(self):
+        M = DetectionDataset.Metadata
+        for pos, k in self.order:
+            path, name = self.items[k]
+            inp, (by, bx), geometry = ingest(path, self.bin, self.device)
+            md = {M.INDEXES: torch.tensor([k]), M.NAME: [name], M.IMAGE_SHAPE: torch.tensor([[1, bx, by]]), M.GT: [],
+                  M.BIN_GEOMETRY: [geometry]}
+            if name in self.gt:
+                g = micrograph_io.to_unit_float(self.gt[name]).T[None]
+                md[M.GT] = [torch.from_numpy(np.ascontiguousarray(g))]
+            hm = torch.zeros_like(inp)
+            yield pos, DetectionDataset.make_batch(inp, hm[..., :bx, :by], hm=hm, metadata=md)
+
+
+def unbinned_map(N, ox, oy):
+    """The coordinate map ``picks.write_scores`` applies for ``{name}_scores_unbinned.txt``: plain ints through
+    ``to_unbinned``."""
+    def to_raw(x, y):
+        return to_unbinned(int(x), int(y), N, ox, oy)
+    return to_raw
+
+
+def bin_dataset(dataset, bin, out_dir, labels=None, device="cuda"):
+    """``joint bin``: every micrograph of the table / directory ``dataset`` binned on the device and written as a
+    float32 MRC ``out_dir/{name}.mrc``, plus ``out_dir/images.txt`` (image_name, path) and, with ``labels``,
+    ``out_dir/labels.txt`` (coordinates through ``to_binned``, points outside the binned area dropped, other columns
+    kept).  Label rows of images that are not in the dataset are dropped too, with a warning that names them.
+    -> {"images": path, "labels": path or None, "geometry": {name: (by, bx, oy, ox)},
+        "label_rows": {"kept", "outside", "unknown_image"} or None}."""
+    from . import coordinates
+    bin = check_bin(bin)
+    rows = micrograph_io.read_image_table(dataset)
+    if not rows:
+        raise ValueError("no micrographs found in %s" % dataset)
+    os.makedirs(out_dir, exist_ok=True)
+    geometry, lines = {}, ["image_name\tpath"]
+    for _, name, path in rows:
+        b, geometry[name] = binned(path, bin, device)
+        out = os.path.join(out_dir, name + ".mrc")
+        with open(out, "wb") as f:
+            micrograph_io.write_mrc(f, b.cpu().numpy())
+        lines.append("%s\t%s" % (name, out))
+    images = os.path.join(out_dir, "images.txt")
+    with open(images, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    labels_out, counts = None, None
+    if labels:
+        table = coordinates.read_coordinates(labels)
+        keep = np.zeros(len(table), dtype=bool)
+        unknown = {}
+        xs, ys = table["x_coord"].to_numpy().copy(), table["y_coord"].to_numpy().copy()
+        for i, name in enumerate(table["image_name"].astype(str)):
+            if name not in geometry:                         # not a micrograph of this dataset (a misspelt name?)
+                unknown[name] = unknown.get(name, 0) + 1
+                continue
+            by, bx, oy, ox = geometry[name]
+            xs[i], ys[i], keep[i] = to_binned(xs[i], ys[i], bin, ox, oy, bx, by)
+        outside = len(table) - int(keep.sum()) - sum(unknown.values())
+        logger.info("%s: %d of %d label rows kept, %d outside the binned area", labels, int(keep.sum()), len(table), outside)
+        if unknown:
+            logger.warning("%s: %d label rows dropped because their image_name is not in %s: %s", labels,
+                           sum(unknown.values()), dataset, ", ".join(sorted(unknown)[:10]) + (" ..." if len(unknown) > 10 else ""))
+        counts = {"kept": int(keep.sum()), "outside": outside, "unknown_image": sum(unknown.values())}
+        table = table.assign(x_coord=xs, y_coord=ys).loc[keep]
+        labels_out = os.path.join(out_dir, "labels.txt")
+        table.to_csv(labels_out, sep="\t", index=False)
+    return {"images": images, "labels": labels_out, "geometry": geometry, "label_rows": counts}

@@ -18,12 +18,15 @@ def filter_picks(scores, coords, shape, border=BORDER):
     return scores[keep], coords[keep]
 
 
-def write_scores(path, name, scores, coords, shape, border=BORDER):
+def write_scores(path, name, scores, coords, shape, border=BORDER, coord_map=None):
+    """coord_map: optional (x_coord, y_coord) -> (x_coord, y_coord) applied to the written columns AFTER the border filter
+    (``joint eval --bin N``: the same picks in the raw micrograph's frame, ingest.unbinned_map)."""
     s, c = filter_picks(scores, coords, shape, border)
     with open(path, "w") as f:
         print("image_name\tx_coord\ty_coord\tscore", file=f)
         for i in range(len(s)):
-            print(name + "\t" + str(c[i, 1]) + "\t" + str(c[i, 0]) + "\t" + str(s[i]), file=f)
+            x, y = (c[i, 1], c[i, 0]) if coord_map is None else coord_map(c[i, 1], c[i, 0])
+            print(name + "\t" + str(x) + "\t" + str(y) + "\t" + str(s[i]), file=f)
     return len(s)
 
 

@@ -514,6 +514,78 @@ _register("contam_mask", "(Tensor img, int crop, int ksize, float k_low, float k
           lambda img, *a: img.new_empty(tuple(img.shape), dtype=torch.uint8))
 
 
+# ---- micrograph ingest (ingest.py: raw MRC samples -> binned image -> uint8 image / network input) ---------------------------
+MRC_ITEMSIZE = {0: 1, 1: 2, 2: 4, 6: 2}          # bytes per sample of the MRC modes sprk_ingest_bin decodes
+INGEST_MAX_BIN = 16                              # SPRK_INGEST_MAX_BIN
+
+
+def _binned_shape(mode, ny, nx, bin):
+    if mode not in MRC_ITEMSIZE:
+        raise _lib.SprkError("ingest_bin: unsupported MRC mode %d" % mode)
+    if not 1 <= bin <= INGEST_MAX_BIN or ny // bin < 1 or nx // bin < 1:
+        raise _lib.SprkError("ingest_bin: bin factor %d on a %dx%d image (1..%d, at least one block)"
+                             % (bin, ny, nx, INGEST_MAX_BIN))
+    return ny // bin, nx // bin
+
+
+def net_size(by, bx):
+    """side of the network input of a [by, bx] image: both axes rounded up to a multiple of 32, then squared"""
+    return max((by + 31) // 32 * 32, (bx + 31) // 32 * 32)
+
+
+def _ingest_bin(raw, mode, ny, nx, bin):
+    """raw: uint8 CUDA tensor holding the file's ny*nx samples -> (binned float32 [by, bx], range float32 [2])."""
+    by, bx = _binned_shape(mode, ny, nx, bin)
+    if raw.dtype != torch.uint8 or raw.dim() != 1 or not raw.is_contiguous() or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
+        raise _lib.SprkError("ingest_bin: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
+                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+    L = _lib.lib()
+    binned, rng = _f32(raw, (by, bx)), _f32(raw, (2,))
+    ws = _ws(L.sprk_ingest_ws_bytes(ny, nx, bin), raw)
+    check(L.sprk_ingest_bin(_p(raw), int(mode), int(ny), int(nx), int(bin), _p(binned), _p(rng), _p(ws), ws.numel(),
+                            _stream(raw)), "sprk_ingest_bin")
+    return binned, rng
+
+
+_register("ingest_bin", "(Tensor raw, int mode, int ny, int nx, int bin) -> (Tensor, Tensor)", _ingest_bin,
+          lambda raw, mode, ny, nx, bin: (raw.new_empty(_binned_shape(mode, ny, nx, bin), dtype=torch.float32),
+                                          raw.new_empty((2,), dtype=torch.float32)))
+
+
+def _finish_shapes(binned, want_u8, want_net):
+    if binned.dim() != 2 or binned.dtype != torch.float32:
+        raise _lib.SprkError("ingest_finish: binned must be a 2-D float32 tensor, got %s %s" % (binned.dtype, tuple(binned.shape)))
+    by, bx = binned.shape
+    S = net_size(by, bx)
+    return ((by, bx) if want_u8 else (0, 0)), ((S, S) if want_net else (0, 0))
+
+
+def _ingest_finish(binned, rng, want_u8, want_net):
+    """-> (u8 [by, bx], net float32 [S, S]); the one that is not asked for is an empty tensor."""
+    if not (want_u8 or want_net):
+        raise _lib.SprkError("ingest_finish: neither output asked for")
+    su, sn = _finish_shapes(binned, want_u8, want_net)
+    if rng.dtype != torch.float32 or rng.numel() != 2 or not rng.is_contiguous() or rng.device != binned.device:
+        raise _lib.SprkError("ingest_finish: range must be a contiguous float32 tensor of 2 elements on %s, got %s %s on %s"
+                             % (binned.device, rng.dtype, tuple(rng.shape), rng.device))
+    binned = binned.contiguous()
+    u8 = torch.empty(su, dtype=torch.uint8, device=binned.device)
+    net = _f32(binned, sn)
+    by, bx = binned.shape
+    check(_lib.lib().sprk_ingest_finish(_p(binned), by, bx, _p(rng), _p(u8) if want_u8 else None,
+                                        _p(net) if want_net else None, sn[0], _stream(binned)), "sprk_ingest_finish")
+    return u8, net
+
+
+def _ingest_finish_fake(binned, rng, want_u8, want_net):
+    su, sn = _finish_shapes(binned, want_u8, want_net)
+    return binned.new_empty(su, dtype=torch.uint8), binned.new_empty(sn, dtype=torch.float32)
+
+
+_register("ingest_finish", "(Tensor binned, Tensor range, bool want_u8, bool want_net) -> (Tensor, Tensor)", _ingest_finish,
+          _ingest_finish_fake)
+
+
 def registered():
     """Names of the operators under torch.ops.sprk (tests)."""
     return tuple(_NAMES)

@@ -31,7 +31,8 @@ import numpy as np
 import torch
 
 from . import cfg as cfg_mod
-from . import checkpoint, distributed, feed as feed_mod, graph_step, outputs as outputs_mod, picks
+from . import checkpoint, distributed, feed as feed_mod, graph_step, ingest as ingest_mod, micrograph_io
+from . import outputs as outputs_mod, picks
 from .algorithms import CONTAM_STATS, contamination_mask, nms_device
 from .datasets import DetectionDataset
 from .denoiser import Denoiser
@@ -60,7 +61,7 @@ tensor_to_png = outputs_mod.tensor_to_png      # save_tensor_image (utils/data.p
 
 class DenoiserTrainer:
     def __init__(self, cfg, mode, state=None, runs_dir=cfg_mod.DEFAULT_RUN_DIR, run_dir=None, alpha=0.5, tau=0.01,
-                 bb=32, device=None, seed=0, graph=True, loss_scale=None, contamination=False):
+                 bb=32, device=None, seed=0, graph=True, loss_scale=None, contamination=False, bin=None):
         self.runs_dir = os.path.abspath(runs_dir)
         self._run_dir = run_dir
         self.cfg = cfg
@@ -86,6 +87,9 @@ class DenoiserTrainer:
         # contamination-aware picking (joint eval --contamination): a run option like the loss scale, never stored in
         # cfg or a checkpoint (params.py stays pickle-compatible with the reference)
         self.contamination = bool(contamination)
+        # raw-micrograph evaluation (joint eval --bin N): the test set is read, binned N x N and laid out on the device
+        # (ingest.py); a run option as well.  None = the host loader, as ever.
+        self.bin = None if bin is None else ingest_mod.check_bin(bin)
         self._metrics_file = None
         self._eval_modes_logged = set()
         self.trainfeed, self.testfeed = None, None
@@ -453,8 +457,13 @@ class DenoiserTrainer:
                 score_map = score_map.masked_fill(mask, float("-inf"))
                 self.writer.png(mask[None].to(torch.float32), path(fileformat, "contam"))
             scores, coords = nms_device(score_map, self.cfg[ConfigValue.NMS], NMS_THRESHOLD)
-            self.writer.call(picks.write_scores, path(scoreformat, "scores"), name, scores.cpu().numpy(),
-                             coords.cpu().numpy(), tuple(score_map.shape))
+            scores, coords = scores.cpu().numpy(), coords.cpu().numpy()
+            self.writer.call(picks.write_scores, path(scoreformat, "scores"), name, scores, coords, tuple(score_map.shape))
+            if self.bin is not None and self.bin > 1:
+                # the same picks in the raw micrograph's frame ({name}_scores.txt stays in the binned frame of the labels)
+                _, _, oy, ox = metadata[DetectionDataset.Metadata.BIN_GEOMETRY][batch_index]
+                self.writer.call(picks.write_scores, path(scoreformat, "scores_unbinned"), name, scores, coords,
+                                 tuple(score_map.shape), picks.BORDER, ingest_mod.unbinned_map(self.bin, ox, oy))
             if contam is not None:
                 st = dict(zip(CONTAM_STATS, contam.tolist()))
                 logger.info("%s: contamination mask excludes %.3f%% of the score map (%d seeds)", name,
@@ -650,6 +659,10 @@ class DenoiserTrainer:
         c = self.cfg
         self._require_txt(ConfigValue.TEST_DATASET_TYPE)
         gt = feed_mod.load_reference_images(c[ConfigValue.TEST_GT_PATH]) if c.get(ConfigValue.TEST_GT_PATH) else None
+        if self.bin is not None:
+            return ingest_mod.RawMicrographFeed(micrograph_io.read_image_table(c[ConfigValue.TEST_DATA_PATH]), self.bin,
+                                                count=cfg_mod.test_length(c), device=self.device, rank=self.rank,
+                                                world=self.world, gt=gt)
         groups, names = feed_mod.load_micrographs(c[ConfigValue.TEST_DATA_PATH], c.get(ConfigValue.TEST_LABEL_PATH),
                                                   radius=3, bb=c[ConfigValue.BB])
         return feed_mod.MicrographFeed(groups, names, count=cfg_mod.test_length(c), device=self.device,
