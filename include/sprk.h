@@ -108,7 +108,7 @@ typedef struct sprk_conv_epilogue {
  * entry points exist).  A binding must refuse a library whose sprk_version() differs from the header it was
  * written against, and may compare sprk_struct_bytes(0 | 1 | 2) with its own sizeof(sprk_conv_geom |
  * sprk_conv_epilogue | sprk_reduce_item). */
-#define SPRK_ABI_VERSION 430   /* 430: sprk_contam_*; sprk_ingest_* joined it compatibly (no signature or struct changed:
+#define SPRK_ABI_VERSION 430   /* 430: sprk_contam_*; sprk_ingest_* and sprk_extract_boxes joined it compatibly (no signature or struct changed:
                                 * a binding that needs them finds a library without them by the missing symbol) */
 const char *sprk_last_error(void);
 int sprk_version(void);
@@ -461,6 +461,29 @@ int sprk_ingest_bin(const void *raw, int mode, int ny, int nx, int bin, float *b
                     size_t ws_bytes, void *stream);
 int sprk_ingest_finish(const float *binned, int by, int bx, const float *range, uint8_t *u8_out, float *net_out, int S,
                        void *stream);
+
+/* ---- particle extraction (`joint extract`) -----------------------------------------------
+ * Boxes cut out of ONE raw micrograph (the buffer sprk_ingest_bin takes: [ny,nx] samples of mode 0 / 1 / 2 / 6, 16-byte
+ * aligned start), binned, background-normalised and optionally inverted: out [P, b, b] fp32 with b = box / bin, status [P].
+ * xy: int32 [P,2] on the device, (x along nx, y along ny) of each centre in raw samples; particle p covers rows
+ * y0 .. y0+box-1, columns x0 .. x0+box-1 with x0 = x - box/2, y0 = y - box/2, output pixel (i, j) the bin x bin block at
+ * (y0 + i*bin, x0 + j*bin).  2 <= box <= 1024, bin in 1..SPRK_INGEST_MAX_BIN, box % bin == 0, b >= 2, bg_radius >= 0 (in
+ * output pixels).
+ * Block value v: sprk_ingest_bin's sum (exact integer; float32: fp32 adds from 0.0f, row-major within the block).
+ * status 1: the box is not entirely inside the image — all zeros, and none of its samples is read.
+ * flags = 0: out = float(v) / float(bin*bin) (sprk_ingest_bin's value for that block, bit for bit), status 0.
+ * SPRK_EXTRACT_NORMALIZE: background = {(i,j): (i - b/2)^2 + (j - b/2)^2 > bg_radius^2}, n pixels.
+ *   integer modes: d = v - v[0,0]; S1 = sum_bg d, S2 = sum_bg d^2 exact (int64); mean = double(S1)/double(n);
+ *     var = double(S2)/double(n) - mean*mean (two roundings); out = float((double(d) - mean) / sqrt(var));
+ *   float32: mean = sum_bg v / n and var = sum_bg (v - mean)^2 / n in double (a fixed summation order: the same call
+ *     gives the same bytes); out = float((double(v) - mean) / sqrt(var));
+ *   status 2 and all zeros when n == 0 or !(var > 0).
+ * SPRK_EXTRACT_INVERT: out is negated.
+ * P == 0 returns SPRK_OK without a launch.  One launch on `stream`, no workspace, no host synchronisation. */
+#define SPRK_EXTRACT_NORMALIZE 1
+#define SPRK_EXTRACT_INVERT 2
+int sprk_extract_boxes(const void *raw, int mode, int ny, int nx, const int *xy, int P, int box, int bin, int bg_radius,
+                       int flags, float *out, int *status, void *stream);
 
 /* ---- in-library kernel timing (bench.py's roofline leg) --------------------------------
  * sprk_prof_enable(mask): bit k set = every launch of kernel class k is bracketed by HIP events

@@ -1,6 +1,7 @@
 """``joint`` command line (cli/cli.py, cli/cmds/train.py:24-300, cli/cmds/eval.py:15-71 of the
 reference): ``joint train start|resume`` and ``joint eval`` with the same flags and the same
-flag -> configuration mapping, plus ``joint bin`` (the README's ``newstack -bin`` preparation, on the GPU).  Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
+flag -> configuration mapping, plus ``joint bin`` (the README's ``newstack -bin`` preparation, on the GPU) and ``joint extract``
+(particle stacks from the pick tables and the raw micrographs, on the GPU).  Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
 under ``python -m torch.distributed.run --nproc-per-node N -m spr_pick_amd -- ...`` (keep the ``--``)."""
 import argparse
 
@@ -44,8 +45,28 @@ def _bin_factor(text):
     return n
 
 
+class _Parser(argparse.ArgumentParser):
+    """A (sub-)parser may carry ``check``: arguments validated against each other at parse time (ValueError -> the
+    parser's usage error), so that `--box 100 --bin 3` is refused like any other bad value and not by a traceback."""
+    check = None
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        if self.check is not None:
+            try:
+                self.check(ns)
+            except ValueError as e:
+                self.error(str(e))
+        return ns, rest
+
+
+def _check_extract(ns):
+    from .extract import check_box
+    check_box(ns.box, ns.bin, ns.bg_radius)
+
+
 def build_parser():
-    parser = argparse.ArgumentParser(prog="joint", description="Joint denoising + particle picking on MI355X "
+    parser = _Parser(prog="joint", description="Joint denoising + particle picking on MI355X "
                                      "(train / evaluate), drop-in for spr_pick's `joint` command.")
     parser.add_argument("--version", action="version", version="%(prog)s v" + __version__)
     cmds = parser.add_subparsers(dest="command", required=True)
@@ -87,6 +108,24 @@ def build_parser():
     bn.add_argument("--bin", type=_bin_factor, required=True, metavar="N", help="bin factor (at most 16, SPRK_INGEST_MAX_BIN)")
     bn.add_argument("--out", "-o", required=True, help="Directory for {name}.mrc (float32), images.txt and labels.txt.")
     bn.add_argument("--labels", "-l", help="Particle coordinates of the raw micrographs; written binned to labels.txt.")
+
+    ex = cmds.add_parser("extract", help="Cut normalised particle stacks out of raw micrographs on the GPU "
+                                         "(replaces the relion_preprocess step after picking).")
+    ex.add_argument("--dataset", "-d", required=True, help="Table (image_name, path) or directory of raw MRC micrographs.")
+    ex.add_argument("--picks", "-p", required=True,
+                    help="Directory of {name}_scores_unbinned.txt / {name}_scores.txt pick tables (joint eval's eval_imgs), "
+                         "or one scores file.")
+    ex.add_argument("--box", "-b", type=int, required=True, metavar="B", help="box side in raw samples (2..1024, a multiple of --bin)")
+    ex.add_argument("--out", "-o", required=True, help="Directory for {name}.mrcs (float32 stacks) and particles.star.")
+    ex.add_argument("--bin", type=_bin_factor, default=1, metavar="N", help="bin every box N x N: stacks of side B / N")
+    ex.add_argument("--picks_bin", type=_bin_factor, default=1, metavar="K",
+                    help="the pick tables are in the frame of `joint eval --bin K` ({name}_scores.txt); default 1: raw samples")
+    ex.add_argument("--bg_radius", type=int, metavar="R",
+                    help="background = output pixels farther than R from the box centre (default 3/8 of B / N)")
+    ex.add_argument("--threshold", type=float, metavar="S", help="keep picks with score > S (default: all)")
+    ex.add_argument("--invert", action="store_true", help="invert the contrast")
+    ex.add_argument("--no_norm", action="store_true", help="block means only, no background normalisation")
+    ex.check = _check_extract
     return parser
 
 
@@ -151,6 +190,16 @@ def run_bin(args):
     return ingest.bin_dataset(args["dataset"], args["bin"], args["out"], labels=args.get("labels"))
 
 
+def run_extract(args):
+    import json
+    from . import extract
+    counts = extract.extract_dataset(args["dataset"], args["picks"], args["out"], args["box"], bin=args["bin"],
+                                     picks_bin=args["picks_bin"], threshold=args.get("threshold"),
+                                     bg_radius=args.get("bg_radius"), normalize=not args["no_norm"], invert=args["invert"])
+    print(json.dumps({"particles": sum(c["written"] for c in counts.values()), "micrographs": counts}))
+    return counts
+
+
 def start(argv=None):
     import sys
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -162,4 +211,6 @@ def start(argv=None):
         return run_train(args, parser)
     if args["command"] == "bin":
         return run_bin(args)
+    if args["command"] == "extract":
+        return run_extract(args)
     return run_eval(args)

@@ -1,0 +1,266 @@
+// Particle extraction: boxes cut out of the sample block of a 2-D MRC image, as it sits in the file, binned, background-
+// normalised and optionally contrast-inverted (`joint extract`, spr_pick_amd/extract.py).
+//
+// raw: the buffer sprk_ingest_bin takes (modes 0 int8, 1 int16, 2 float32, 6 uint16).  xy [P, 2] int32 on the device:
+// (x along nx, y along ny) of each centre in raw samples.  Particle p covers rows y0 .. y0+B-1 and columns x0 .. x0+B-1,
+// x0 = x - B/2, y0 = y - B/2; output pixel (i, j) of its [b, b] image, b = B / N, is the N x N block at (y0 + iN, x0 + jN).
+//   block value v: integer modes the exact int32 sum; float32 fp32 adds from 0.0f in row-major order within the block,
+//       every add its own rounding (sprk_ingest_bin's order);
+//   a box that is not entirely inside the image: status 1, all zeros, and NOT ONE sample of it is read — the coordinates
+//       live in device memory, so this check is the kernel's (in 64-bit: any int32 centre is safe);
+//   without SPRK_EXTRACT_NORMALIZE: out = float(v) / float(N*N), one correctly rounded division (sprk_ingest_bin's value);
+//   with it: background = {(i, j): (i - b/2)^2 + (j - b/2)^2 > R^2}, n pixels; n == 0 -> status 2, zeros;
+//       integer modes: d = v - v[0,0] (int32), S1 = sum_bg d, S2 = sum_bg d^2 exact in int64, mean = double(S1) / double(n),
+//           var = double(S2) / double(n) - mean*mean (two roundings, no fma); !(var > 0) -> status 2, zeros; else
+//           out = float((double(d) - mean) / sqrt(var));
+//       float32: two passes in double over the fp32 v: mean = sum_bg v / n, var = sum_bg (v - mean)^2 / n, same rule and
+//           formula with v in place of d;
+//   SPRK_EXTRACT_INVERT negates the output.
+//
+// One workgroup per particle.  Phase 1: lanes stride over the output pixels (adjacent lanes read adjacent chunks of a
+// row), kUnroll pixels per lane at a time, and form d or v and their share of the background sums.  Phase 2: the sums
+// over the wave by an xor butterfly (both partners add the same two numbers, so every lane holds the same bits), over
+// the workgroup through LDS with the waves added in index order — a fixed order, no atomics: the same call gives the
+// same bytes.  Phase 3: write.  The box's d / v stay in LDS between the phases when 4*b*b bytes fit kResidentBytes; a
+// larger box is formed again from global memory (its samples were just read: L2 serves them).  Every lane meets in
+// phases 2 and 3 the pixels it formed in phase 1, so the resident values need no barrier of their own.
+// Box rows start at an arbitrary x0 and are only itemsize-aligned: every sample is fetched by an element load of its
+// own type, never by a wider one, and only samples of rows y0 .. y0+B-1, columns x0 .. x0+B-1 of an inside box are
+// addressed.
+//
+// Compiled with -ffp-contract=off like ingest.hip (Makefile): mean*mean and the subtraction are separate roundings.
+#include <cstdint>
+#include <type_traits>
+
+#include "common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kUnroll = 8;                       // output pixels a lane forms together (for_each_pixel)
+constexpr int kScratchBytes = 128;              // head of the dynamic LDS: kWaves slots of 8 bytes for the reductions
+// LDS residency of a box: 4*b*b <= 64 KiB, b <= 128.  A workgroup may take all 160 KiB of a CU (b <= 202), but it
+// would then be the CU's only one — four waves to hide the latency of phase 1's loads.  64 KiB keeps two workgroups
+// (eight waves) on a CU at the largest resident box and more at the usual ones (b = 64: 16 KiB, nine workgroups).
+constexpr int kResidentBytes = 64 * 1024;
+constexpr int kMaxBox = 1024;
+
+template <typename T>
+struct Sum {                                    // the contract's block accumulator
+    using value = int;
+    int v = 0;
+    __device__ __forceinline__ void add(T s) { v += (int)s; }
+};
+template <>
+struct Sum<float> {
+    using value = float;
+    float v = 0.0f;
+    __device__ __forceinline__ void add(float s) { v = __fadd_rn(v, s); }
+};
+
+// Calls f(e, i, j, v) for every output pixel e = i*b + j of this thread's share (e = tid, tid + kThreads, ...), v its
+// block value.  kUnroll pixels are formed together: their loads do not depend on one another, so a lane keeps kUnroll
+// of them in flight instead of one (a particle is one workgroup: with one load per lane in flight a 256 x 256 box
+// is 256 dependent round trips to memory: measured 288 us for 1000 such boxes, 154 us with eight in flight).  Each pixel's own adds keep the
+// contract's order.  A slot past the last pixel reads the box's first block (valid samples) and is dropped.
+// Samples read: origin[r*nx + q], 0 <= r, q < b*N.
+template <typename T, typename F>
+__device__ __forceinline__ void for_each_pixel(const T *__restrict__ origin, int nx, int N, int b, float inv_b, F f) {
+    const int npix = b * b;
+    for (int e0 = threadIdx.x; e0 < npix; e0 += kUnroll * kThreads) {
+        const T *p[kUnroll];
+        int row[kUnroll];
+        Sum<T> acc[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int e = e0 + u * kThreads;
+            row[u] = e < npix ? fast_div(e, inv_b) : 0;                // exact: e < 2^20 (common.h; every b checked)
+            const int col = e < npix ? e - row[u] * b : 0;
+            p[u] = origin + (long)(row[u] * N) * nx + col * N;
+        }
+        for (int r = 0; r < N; ++r) {
+            for (int q = 0; q < N; ++q) {
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) acc[u].add(p[u][q]);
+            }
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) p[u] += nx;
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int e = e0 + u * kThreads;
+            if (e < npix) f(e, row[u], e - row[u] * b, acc[u].v);
+        }
+    }
+}
+
+// the workgroup's sum in a fixed order, returned to every thread (all threads must call)
+template <typename S>
+__device__ __forceinline__ S block_sum(S v, S *red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    S t = red[0];
+    for (int w = 1; w < kWaves; ++w) t += red[w];
+    __syncthreads();                            // red is used again
+    return t;
+}
+
+__device__ __forceinline__ void zero_box(float *__restrict__ o, int npix, int *__restrict__ status, int code) {
+    for (int e = threadIdx.x; e < npix; e += kThreads) o[e] = 0.0f;
+    if (threadIdx.x == 0) *status = code;
+}
+
+// grid: P workgroups.  resident: the dynamic LDS holds kScratchBytes + 4*b*b bytes, else kScratchBytes.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void extract_kernel(const T *__restrict__ raw, int ny, int nx,
+                                                           const int *__restrict__ xy, int B, int N, float inv_b,
+                                                           long R2, int flags, int resident, float *__restrict__ out,
+                                                           int *__restrict__ status) {
+    using V = typename Sum<T>::value;
+    extern __shared__ __align__(16) unsigned char lds[];
+    V *box = reinterpret_cast<V *>(lds + kScratchBytes);
+    const int p = blockIdx.x, b = B / N, npix = b * b, c = b / 2;
+    const bool invert = flags & SPRK_EXTRACT_INVERT;
+    float *o = out + (long)p * npix;
+    const long x0 = (long)xy[2 * p] - B / 2, y0 = (long)xy[2 * p + 1] - B / 2;
+    if (x0 < 0 || y0 < 0 || x0 + B > nx || y0 + B > ny) {      // before any sample is addressed
+        zero_box(o, npix, status + p, 1);
+        return;
+    }
+    const T *origin = raw + y0 * nx + x0;                      // samples read: origin[r*nx + q], 0 <= r, q < B
+    auto is_bg = [&](int i, int j) { return (long)((i - c) * (i - c) + (j - c) * (j - c)) > R2; };
+
+    if (!(flags & SPRK_EXTRACT_NORMALIZE)) {
+        const float nn = (float)(N * N);
+        for_each_pixel(origin, nx, N, b, inv_b, [&](int e, int, int, V v) {
+            const float m = __fdiv_rn((float)v, nn);           // |integer sum| <= 16^2 * 65535 < 2^24: exact
+            o[e] = invert ? -m : m;
+        });
+        if (threadIdx.x == 0) status[p] = 0;
+        return;
+    }
+
+    int n = 0;
+    double mean, var;
+    V anchor = 0;
+    if constexpr (std::is_same<T, float>::value) {
+        double s = 0.0;
+        for_each_pixel(origin, nx, N, b, inv_b, [&](int e, int i, int j, float v) {
+            if (resident) box[e] = v;
+            if (is_bg(i, j)) {
+                s += (double)v;
+                ++n;
+            }
+        });
+        n = block_sum(n, reinterpret_cast<int *>(lds));
+        if (n == 0) {
+            zero_box(o, npix, status + p, 2);
+            return;
+        }
+        mean = block_sum(s, reinterpret_cast<double *>(lds)) / (double)n;
+        double q = 0.0;
+        auto square = [&](int, int i, int j, float v) {
+            if (is_bg(i, j)) {
+                const double t = (double)v - mean;
+                q += t * t;
+            }
+        };
+        if (resident) {
+            for (int e = threadIdx.x; e < npix; e += kThreads) {
+                const int i = fast_div(e, inv_b);
+                square(e, i, e - i * b, box[e]);
+            }
+        } else {
+            for_each_pixel(origin, nx, N, b, inv_b, square);   // the same pixels in the same order per lane
+        }
+        var = block_sum(q, reinterpret_cast<double *>(lds)) / (double)n;
+    } else {
+        // |d| <= 2 * N^2 * 65535 < 2^26 and S2 <= b^2 * d^2 = 4 * B^2 * N^2 * 65535^2 <= 4.6e18 < 2^63 at B = 1024,
+        // N = 16: the int64 sums cannot overflow for any box sprk_extract_boxes admits (kMaxBox)
+        Sum<T> first;                                          // v[0, 0]; every lane the same addresses: broadcasts
+        for (int r = 0; r < N; ++r)
+            for (int q = 0; q < N; ++q) first.add(origin[(long)r * nx + q]);
+        anchor = first.v;
+        long long s1 = 0, s2 = 0;
+        for_each_pixel(origin, nx, N, b, inv_b, [&](int e, int i, int j, int v) {
+            const int d = v - anchor;
+            if (resident) box[e] = d;
+            if (is_bg(i, j)) {
+                s1 += d;
+                s2 += (long long)d * d;
+                ++n;
+            }
+        });
+        n = block_sum(n, reinterpret_cast<int *>(lds));
+        if (n == 0) {
+            zero_box(o, npix, status + p, 2);
+            return;
+        }
+        s1 = block_sum(s1, reinterpret_cast<long long *>(lds));
+        s2 = block_sum(s2, reinterpret_cast<long long *>(lds));
+        mean = (double)s1 / (double)n;
+        var = __dsub_rn((double)s2 / (double)n, __dmul_rn(mean, mean));
+    }
+    if (!(var > 0.0)) {                                        // the same bits in every lane: a uniform branch
+        zero_box(o, npix, status + p, 2);
+        return;
+    }
+    const double sd = sqrt(var);
+    auto write = [&](int e, V d) {
+        const float r = (float)(((double)d - mean) / sd);
+        o[e] = invert ? -r : r;
+    };
+    if (resident) {
+        for (int e = threadIdx.x; e < npix; e += kThreads) write(e, box[e]);
+    } else {
+        for_each_pixel(origin, nx, N, b, inv_b, [&](int e, int, int, V v) {
+            if constexpr (std::is_same<T, float>::value) write(e, v);
+            else write(e, v - anchor);
+        });
+    }
+    if (threadIdx.x == 0) status[p] = 0;
+}
+
+template <typename T>
+int launch_extract(const void *raw, int ny, int nx, const int *xy, int P, int B, int N, int R, int flags, float *out,
+                   int *status, hipStream_t s) {
+    const int b = B / N;
+    const size_t box_bytes = (size_t)4 * b * b;
+    const int resident = (flags & SPRK_EXTRACT_NORMALIZE) && box_bytes <= (size_t)kResidentBytes;
+    const size_t lds = kScratchBytes + (resident ? box_bytes : 0);
+    if (int rc = sprk::lds_optin(reinterpret_cast<const void *>(extract_kernel<T>), kScratchBytes + kResidentBytes,
+                                 "extract_boxes"))
+        return rc;
+    hipLaunchKernelGGL(extract_kernel<T>, dim3(P), dim3(kThreads), lds, s, (const T *)raw, ny, nx, xy, B, N,
+                       1.0f / (float)b, (long)R * R, flags, resident, out, status);
+    return sprk::check_launch("extract_boxes");
+}
+
+}  // namespace
+
+extern "C" int sprk_extract_boxes(const void *raw, int mode, int ny, int nx, const int *xy, int P, int box, int bin,
+                                  int bg_radius, int flags, float *out, int *status, void *stream) {
+    SPRK_REQUIRE(mode == SPRK_MRC_INT8 || mode == SPRK_MRC_INT16 || mode == SPRK_MRC_FLOAT32 || mode == SPRK_MRC_UINT16,
+                 "extract_boxes: unsupported MRC mode %d (0, 1, 2 and 6 are)", mode);
+    SPRK_REQUIRE(bin >= 1 && bin <= SPRK_INGEST_MAX_BIN, "extract_boxes: bin factor %d (1..%d)", bin, SPRK_INGEST_MAX_BIN);
+    // box <= 1024 is what keeps the int64 sum of squares of the integer modes below 2^63 (see the kernel)
+    SPRK_REQUIRE(box >= 2 && box <= kMaxBox && box % bin == 0 && box / bin >= 2,
+                 "extract_boxes: box %d with bin %d (2..%d, a multiple of the bin factor, at least 2 output pixels a side)",
+                 box, bin, kMaxBox);
+    SPRK_REQUIRE(bg_radius >= 0, "extract_boxes: background radius %d (>= 0)", bg_radius);
+    SPRK_REQUIRE((flags & ~(SPRK_EXTRACT_NORMALIZE | SPRK_EXTRACT_INVERT)) == 0, "extract_boxes: unknown flags 0x%x", flags);
+    SPRK_REQUIRE(ny > 0 && nx > 0 && (long)ny * nx < (1L << 31), "extract_boxes: bad image size %dx%d", ny, nx);
+    SPRK_REQUIRE(P >= 0, "extract_boxes: %d particles", P);
+    if (P == 0) return SPRK_OK;
+    SPRK_REQUIRE(raw && xy && out && status, "extract_boxes: null pointer");
+    SPRK_REQUIRE(((uintptr_t)raw & 15) == 0, "extract_boxes: the sample buffer must start 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    switch (mode) {
+        case SPRK_MRC_INT8: return launch_extract<int8_t>(raw, ny, nx, xy, P, box, bin, bg_radius, flags, out, status, s);
+        case SPRK_MRC_INT16: return launch_extract<int16_t>(raw, ny, nx, xy, P, box, bin, bg_radius, flags, out, status, s);
+        case SPRK_MRC_FLOAT32: return launch_extract<float>(raw, ny, nx, xy, P, box, bin, bg_radius, flags, out, status, s);
+        default: return launch_extract<uint16_t>(raw, ny, nx, xy, P, box, bin, bg_radius, flags, out, status, s);
+    }
+}

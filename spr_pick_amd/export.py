@@ -18,6 +18,9 @@ RELION_NAMES = {"score": "AutopickFigureOfMerit", "image_name": "MicrographName"
 
 STAR_HEADER = ("# version 30001\n\ndata_\n\nloop_\n_rlnCoordinateX #1\n_rlnCoordinateY #2\n"
                "_rlnMicrographName #3\n_rlnAutopickFigureOfMerit #4\n")
+# particles.star of `joint extract` (extract.py): the same table with the particle's place in its stack
+PARTICLES_STAR_HEADER = ("# version 30001\n\ndata_\n\nloop_\n_rlnCoordinateX #1\n_rlnCoordinateY #2\n_rlnImageName #3\n"
+                         "_rlnMicrographName #4\n_rlnAutopickFigureOfMerit #5\n")
 
 
 def coordinates_to_star(table, image_ext=""):

@@ -586,6 +586,61 @@ _register("ingest_finish", "(Tensor binned, Tensor range, bool want_u8, bool wan
           _ingest_finish_fake)
 
 
+# ---- particle extraction (extract.py: raw MRC samples + pick coordinates -> normalised particle stack) ------------------------
+EXTRACT_MAX_BOX = 1024                           # sprk_extract_boxes: the int64 sum of squares stays below 2^63 up to here
+EXTRACT_NORMALIZE, EXTRACT_INVERT = 1, 2         # SPRK_EXTRACT_*
+
+
+def extract_side(box, bin, bg_radius=0):
+    """Argument check shared by the operator, extract.py and the command line -> b = box // bin, the output side."""
+    if not 1 <= bin <= INGEST_MAX_BIN:
+        raise _lib.SprkError("extract_boxes: bin factor %d (1..%d)" % (bin, INGEST_MAX_BIN))
+    if not 2 <= box <= EXTRACT_MAX_BOX or box % bin or box // bin < 2:
+        raise _lib.SprkError("extract_boxes: box %d with bin %d (2..%d, a multiple of the bin factor, at least 2 output "
+                             "pixels a side)" % (box, bin, EXTRACT_MAX_BOX))
+    if bg_radius < 0:
+        raise _lib.SprkError("extract_boxes: background radius %d (>= 0)" % bg_radius)
+    return box // bin
+
+
+def _extract_shapes(raw, mode, ny, nx, xy, box, bin, bg_radius):
+    if mode not in MRC_ITEMSIZE:
+        raise _lib.SprkError("extract_boxes: unsupported MRC mode %d" % mode)
+    b = extract_side(box, bin, bg_radius)
+    if ny < 1 or nx < 1 or ny * nx >= 1 << 31:
+        raise _lib.SprkError("extract_boxes: bad image size %dx%d" % (ny, nx))
+    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
+        raise _lib.SprkError("extract_boxes: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
+                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+    if xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or xy.device != raw.device:
+        raise _lib.SprkError("extract_boxes: xy must be an int32 tensor [P, 2] on %s, got %s %s on %s"
+                             % (raw.device, xy.dtype, tuple(xy.shape), xy.device))
+    return xy.shape[0], b
+
+
+def _extract_boxes(raw, mode, ny, nx, xy, box, bin, bg_radius, normalize, invert):
+    """-> (out float32 [P, b, b], status int32 [P]: 0 ok, 1 outside the image, 2 no or flat background)."""
+    P, b = _extract_shapes(raw, mode, ny, nx, xy, box, bin, bg_radius)
+    if not raw.is_contiguous():
+        raise _lib.SprkError("extract_boxes: raw must be contiguous")
+    xy = xy.contiguous()
+    out = _f32(raw, (P, b, b))
+    status = torch.empty((P,), dtype=torch.int32, device=raw.device)
+    flags = (EXTRACT_NORMALIZE if normalize else 0) | (EXTRACT_INVERT if invert else 0)
+    check(_lib.lib().sprk_extract_boxes(_p(raw), int(mode), int(ny), int(nx), _p(xy), P, int(box), int(bin),
+                                        int(bg_radius), flags, _p(out), _p(status), _stream(raw)), "sprk_extract_boxes")
+    return out, status
+
+
+def _extract_boxes_fake(raw, mode, ny, nx, xy, box, bin, bg_radius, normalize, invert):
+    P, b = _extract_shapes(raw, mode, ny, nx, xy, box, bin, bg_radius)
+    return raw.new_empty((P, b, b), dtype=torch.float32), raw.new_empty((P,), dtype=torch.int32)
+
+
+_register("extract_boxes", "(Tensor raw, int mode, int ny, int nx, Tensor xy, int box, int bin, int bg_radius, "
+                           "bool normalize, bool invert) -> (Tensor, Tensor)", _extract_boxes, _extract_boxes_fake)
+
+
 def registered():
     """Names of the operators under torch.ops.sprk (tests)."""
     return tuple(_NAMES)
