@@ -22,8 +22,13 @@ void prof_bytes(double bytes);   // algorithmic HBM bytes of the launch opened b
 // Per-DEVICE facts and one-time set-up (a process may drive any device; nothing here is per process):
 // compute units of the calling thread's current device (persistent kernels launch one workgroup per CU)
 int num_cus();
-// opt a kernel in to `bytes` of dynamic LDS on the current device (hipFuncSetAttribute once per device and function)
+// allow a kernel `bytes` of dynamic LDS on the current device, before every launch that asks for them (core.hip);
+// what: the kernel family the error text names
 int lds_optin(const void *kernel, size_t bytes, const char *what);
+template <typename K>
+int lds_optin(K *kernel, size_t bytes, const char *what) {
+    return lds_optin(reinterpret_cast<const void *>(kernel), bytes, what);
+}
 
 inline int check_launch(const char *what) {
     g_launches.fetch_add(1, std::memory_order_relaxed);

@@ -1142,28 +1142,14 @@ bool plan_fwd(const sprk::Corr &c, FwdPlan *p) {
     return true;
 }
 
-template <typename K>
-int set_lds(K kernel, size_t bytes) {
-    if (bytes > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bytes) != hipSuccess) {
-            sprk::set_error("cannot reserve %zu bytes of LDS", bytes);
-            return SPRK_ELAUNCH;
-        }
-    }
-    return SPRK_OK;
-}
-
 template <int MT, int NT, int RB>
 int launch_fwd_one(const ConvArgs &a, const FwdPlan &p, dim3 grid, hipStream_t s) {
-    if (a.xtab) {
-        if (int rc = set_lds(conv_mfma_kernel<MT, NT, RB, true>, p.ldsBytes)) return rc;
-        hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, RB, true>), grid, dim3(kBlock), p.ldsBytes, s, a);
-    } else {
-        if (int rc = set_lds(conv_mfma_kernel<MT, NT, RB, false>, p.ldsBytes)) return rc;
-        hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, RB, false>), grid, dim3(kBlock), p.ldsBytes, s, a);
-    }
-    return SPRK_OK;
+    auto go = [&](auto kernel) {
+        if (int rc = sprk::lds_optin(kernel, p.ldsBytes, "conv_mfma")) return rc;
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), p.ldsBytes, s, a);
+        return (int)SPRK_OK;
+    };
+    return a.xtab ? go(conv_mfma_kernel<MT, NT, RB, true>) : go(conv_mfma_kernel<MT, NT, RB, false>);
 }
 
 template <int MT, int RB>
@@ -1364,7 +1350,7 @@ bool plan_wgrad(const sprk_conv_geom *g, WgPlan *p) {
 template <int IT, int NT, int MODE>
 int launch_wg_one(const WgArgs &a, const WgPlan &p, dim3 grid, hipStream_t s) {
     constexpr int WJ = (NT % 2 == 0) ? 2 : 1;   // two waves per SIMD whenever the cout tiles split evenly
-    if (int rc = set_lds(conv_wgrad_mfma_kernel<IT, NT, WJ, MODE>, p.ldsBytes)) return rc;
+    if (int rc = sprk::lds_optin(conv_wgrad_mfma_kernel<IT, NT, WJ, MODE>, p.ldsBytes, "conv_wgrad_mfma")) return rc;
     hipLaunchKernelGGL((conv_wgrad_mfma_kernel<IT, NT, WJ, MODE>), grid, dim3(256 * WJ), p.ldsBytes, s, a);
     return SPRK_OK;
 }
@@ -1397,6 +1383,61 @@ int launch_wg(const WgArgs &a, const WgPlan &p, dim3 grid, hipStream_t s) {
     }
     sprk::set_error("conv2d_bwd_weight: no kernel for %d k-tiles per wave", p.IT);
     return SPRK_EINVAL;
+}
+
+// conv_wgrad_mfma_kernel's argument block for layer g under plan p, and the kernel's MODE for these tensors (the plan's,
+// or the general kernel's 0 where their alignment or size rules the plan's staging out); wsf: the call's workspace (a
+// zero-block-sized gap, then the partial sums)
+int wgrad_args(const sprk_conv_geom *g, const WgPlan &p, const float *x, const float *x2, const float *gy, float *wsf,
+               WgArgs &a, int *mode) {
+    const float *zeros = nullptr;  // device-resident, never written: no per-call memset
+    if (hipGetSymbolAddress((void **)&zeros, HIP_SYMBOL(g_zero_block)) != hipSuccess || !zeros) {
+        sprk::set_error("conv2d_bwd_weight: zero block unavailable");
+        return SPRK_ELAUNCH;
+    }
+    const int Cin = g->C1 + g->C2;
+    a = WgArgs{};
+    a.x = x; a.x2 = x2; a.gy = gy; a.zeros = zeros; a.partial = wsf + kZeroFloats;
+    a.N = g->N; a.C1 = g->C1; a.C2 = g->C2; a.Hin = g->Hin; a.Win = g->Win; a.up1 = g->up1;
+    a.H1 = g->up1 ? g->Hin / 2 : g->Hin;
+    a.W1 = g->up1 ? g->Win / 2 : g->Win;
+    a.Cout = g->Cout; a.CoutP = p.CoutP; a.Hout = g->Hout; a.Wout = g->Wout;
+    a.KH = g->KH; a.KW = g->KW; a.stride = g->stride; a.dil = g->dil; a.padT = g->pad_top; a.padL = g->pad_left;
+    a.lgTC = p.lgTC; a.lgTR = p.lgTR; a.tilesX = p.tilesX; a.tilesY = p.tilesY; a.nTiles = p.nTiles;
+    a.tilesPerGroup = p.tilesPerGroup;
+    a.CKW = p.CKW; a.ioffN = p.ioffN;
+    a.inRows = p.inRows; a.inCols = p.inCols; a.pitch = p.pitch; a.cplane = p.cplane; a.colOff = p.colOff;
+    a.invImg = 1.0f / (float)(p.inRows * p.pitch);
+    a.invPitch = 1.0f / (float)p.pitch;
+    {
+        const bool geo = ((1 << p.lgTC) * g->stride) % 4 == 0 && (g->Win % 4) == 0;
+        a.vec1 = (geo && !g->up1 && aligned16(x)) ? 1 : 0;
+        a.vec2 = (geo && x2 && aligned16(x2)) ? 1 : 0;
+        a.deal = 1;
+    }
+    a.xrow = p.xrow;
+    a.g4 = (p.lgTC >= 2 && (g->Wout % 4) == 0 && ((uintptr_t)gy & 15) == 0) ? 1 : 0;
+    // buffer-load staging of the row tiles needs 16-byte aligned rows and 32-bit byte offsets inside one tile
+    // group and one channel block; otherwise the general kernel (MODE 0) runs
+    const long planeI = (long)g->Hin * g->Win, planeO = (long)g->Hout * g->Wout;
+    const int NIw = 64 >> (p.lgTC + p.lgTR);
+    const bool fits = (long)NIw * Cin * planeI < (1L << 28) && (long)NIw * g->Cout * planeO < (1L << 28) &&
+                      (long)p.CKW * planeI < (1L << 28) && (long)p.NT * 16 * planeO < (1L << 28);
+    static const int rowbuf = sprk::knob_env("SPRK_WG_ROWBUF", 1);
+    const bool fast = rowbuf && fits && a.g4;
+    a.xtab = fast ? 1 : 0;
+    if (a.xrow && (!fast || (((uintptr_t)x & 15) != 0))) {
+        sprk::set_error("conv2d_bwd_weight: 1x1 row staging needs 16-byte aligned x / gy and < 2^28-element tiles");
+        return SPRK_EINVAL;
+    }
+    // MODE 2 additionally needs 16-byte aligned x / x2 (the general kernel ignores the table area in LDS)
+    const bool planesOk = a.vec1 && (g->C2 == 0 || a.vec2);
+    *mode = !fast ? 0 : (p.mode == 2 && !planesOk) ? 0 : p.mode;
+    static const int wg_diag = sprk::diag_env("SPRK_WG_DIAG");
+    a.diag = wg_diag;
+    a.nG1 = p.nG1;
+    a.nG2 = p.nG2;
+    return SPRK_OK;
 }
 
 // the calls whose activation tensors are 16-bit tensors (SPRK_DT_X16 / SPRK_DT_Y16) end here when no 16-bit kernel took them
@@ -1575,104 +1616,75 @@ int sprk_conv2d_bwd_data_wprep(const float *w, const sprk_conv_geom *g, void *ws
     return rc == sprk::kWprepDescribed ? (int)SPRK_OK : rc;
 }
 
-size_t sprk_conv2d_bwd_weight_ws_bytes(const sprk_conv_geom *g) {
-    if (!g) return 0;
-    const size_t wino = sprk::wino_wgrad_eligible(*g)
-                            ? sprk::wino_wgrad_ws_bytes(g->C1, g->C2, g->Cout) : 0;
-    const size_t w16 = (g->dtype & SPRK_DT_MASK) != SPRK_DT_F32 ? sprk::wgrad16_ws_bytes(*g) : 0;
+// What a backward-weight call of g can ask for: the maximum over the stages of wgrad_dispatch that take a workspace,
+// by the predicates and sizes the dispatcher itself uses.  SPRK_DT_NAIVE is ignored (the direct kernel needs none):
+// ops.py and the graph stepper size long-lived buffers by this, whatever flags a later call carries.
+static size_t wgrad_ws_bytes(const sprk_conv_geom &g) {
+    size_t need = sprk::wgrad16_ws_bytes(g);
     WgPlan p;
-    if (!plan_wgrad(g, &p)) return std::max(wino, w16);
-    return std::max(std::max(p.wsBytes, wino), w16);
+    if (sprk::wino_wgrad_eligible(g)) need = std::max(need, sprk::wino_wgrad_ws_bytes(g));
+    if (plan_wgrad(&g, &p)) need = std::max(need, p.wsBytes);
+    return need;
 }
 
-int sprk_conv2d_bwd_weight(const float *x, const float *x2, const float *gy, float *gw, const sprk_conv_geom *g,
-                           void *ws, size_t ws_bytes, void *stream) {
-    return sprk_conv2d_bwd_weight_partial(x, x2, gy, gw, g, ws, ws_bytes, nullptr, stream);
-}
+size_t sprk_conv2d_bwd_weight_ws_bytes(const sprk_conv_geom *g) { return g ? wgrad_ws_bytes(*g) : 0; }
 
-// item == nullptr: finish the sum over the partial buffers now; otherwise describe it in *item (sprk.h)
-int sprk_conv2d_bwd_weight_partial(const float *x, const float *x2, const float *gy, float *gw, const sprk_conv_geom *g,
-                                   void *ws, size_t ws_bytes, sprk_reduce_item *item, void *stream) {
+// The one place where a backward-weight call meets its kernel, the twin of conv_dispatch; the layer's sprk_conv_geom is
+// the common description, and a kernel family is a predicate, a workspace size and a run function over it (DESIGN.md,
+// "The convolution dispatcher").  item == nullptr: finish the sum over the partial buffers now; otherwise describe it in
+// *item (sprk.h).  The stages, in order:
+//   direct kernel (SPRK_DT_NAIVE) -> 16-bit operands -> storage guard -> Winograd -> MFMA (-> direct: no plan fits LDS)
+static int wgrad_dispatch(const float *x, const float *x2, const float *gy, float *gw, const sprk_conv_geom *g, void *ws,
+                          size_t ws_bytes, sprk_reduce_item *item, void *stream) {
+    const char *who = "conv2d_bwd_weight";
     if (item) *item = sprk_reduce_item{nullptr, nullptr, SPRK_RED_NONE, 0, 0, 0, 0, 0};
     if (int rc = check_geom(g)) return rc;
     SPRK_REQUIRE(x && gy && gw, "conv2d_bwd_weight: null tensor");
     SPRK_REQUIRE(g->C2 == 0 || x2, "conv2d_bwd_weight: C2 > 0 but x2 is null");
     hipStream_t s = (hipStream_t)stream;
-    const int Cin = g->C1 + g->C2;
-    const char *who = "conv2d_bwd_weight";
-    if ((g->dtype & SPRK_DT_MASK) != SPRK_DT_F32 && !naive_of(g) && sprk::wgrad16_eligible(*g))
-        return sprk::wgrad16_run(*g, x, x2, gy, gw, ws, ws_bytes, item, s);
-    if (int rc = check_storage32(who, g->dtype)) return rc;
-    if (!naive_of(g) && sprk::wino_wgrad_eligible(*g)) {
-        if (int rc = sprk::check_ws(who, ws, ws_bytes, sprk::wino_wgrad_ws_bytes(g->C1, g->C2, g->Cout))) return rc;
-        sprk::WinoWgArgs wa{x, x2, gy, gw, (float *)ws, g->N, g->C1, g->C2, g->Hin, g->Win, g->Cout, g->pad_top, g->pad_left, 4,
-                            sprk::conv_flops(*g)};   // profiling class 4
-        return sprk::wino_wgrad(wa, s);
+    const bool naive = naive_of(g);   // skips the kernels, not the storage guard: the direct kernel reads fp32 tensors
+
+    if (const size_t need16 = naive ? 0 : sprk::wgrad16_ws_bytes(*g)) {   // eligible (never with fp32 operands)
+        if (int rc = sprk::check_ws(who, ws, ws_bytes, need16)) return rc;
+        return sprk::wgrad16_run(*g, x, x2, gy, gw, ws, item, s);
     }
+    if (int rc = check_storage32(who, g->dtype)) return rc;
+
+    if (!naive && sprk::wino_wgrad_eligible(*g)) {
+        if (int rc = sprk::check_ws(who, ws, ws_bytes, sprk::wino_wgrad_ws_bytes(*g))) return rc;
+        return sprk::wino_wgrad(*g, x, x2, gy, gw, ws, item, s);
+    }
+
     WgPlan p;
-    const bool ok = plan_wgrad(g, &p);
-    if (naive_of(g) || !ok) {
+    if (naive || !plan_wgrad(g, &p)) {
         DirectArgs a{x, x2, nullptr, gy, gw, *g, sprk::kNoEpilogue};
-        hipLaunchKernelGGL(conv_bwd_weight_direct_kernel, dim3(g->Cout * Cin), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(conv_bwd_weight_direct_kernel, dim3(g->Cout * (g->C1 + g->C2)), dim3(256), 0, s, a);
         return sprk::check_launch("conv_bwd_weight_direct");
     }
     if (int rc = sprk::check_ws(who, ws, ws_bytes, p.wsBytes)) return rc;
     float *wsf = (float *)ws;
-    const float *zeros = nullptr;  // device-resident, never written: no per-call memset
-    if (hipGetSymbolAddress((void **)&zeros, HIP_SYMBOL(g_zero_block)) != hipSuccess || !zeros) {
-        sprk::set_error("conv2d_bwd_weight: zero block unavailable");
-        return SPRK_ELAUNCH;
-    }
-    WgArgs a{};
-    a.x = x; a.x2 = x2; a.gy = gy; a.zeros = zeros; a.partial = wsf + kZeroFloats;
-    a.N = g->N; a.C1 = g->C1; a.C2 = g->C2; a.Hin = g->Hin; a.Win = g->Win; a.up1 = g->up1;
-    a.H1 = g->up1 ? g->Hin / 2 : g->Hin;
-    a.W1 = g->up1 ? g->Win / 2 : g->Win;
-    a.Cout = g->Cout; a.CoutP = p.CoutP; a.Hout = g->Hout; a.Wout = g->Wout;
-    a.KH = g->KH; a.KW = g->KW; a.stride = g->stride; a.dil = g->dil; a.padT = g->pad_top; a.padL = g->pad_left;
-    a.lgTC = p.lgTC; a.lgTR = p.lgTR; a.tilesX = p.tilesX; a.tilesY = p.tilesY; a.nTiles = p.nTiles;
-    a.tilesPerGroup = p.tilesPerGroup;
-    a.CKW = p.CKW; a.ioffN = p.ioffN;
-    a.inRows = p.inRows; a.inCols = p.inCols; a.pitch = p.pitch; a.cplane = p.cplane; a.colOff = p.colOff;
-    a.invImg = 1.0f / (float)(p.inRows * p.pitch);
-    a.invPitch = 1.0f / (float)p.pitch;
-    {
-        const bool geo = ((1 << p.lgTC) * g->stride) % 4 == 0 && (g->Win % 4) == 0;
-        a.vec1 = (geo && !g->up1 && aligned16(x)) ? 1 : 0;
-        a.vec2 = (geo && x2 && aligned16(x2)) ? 1 : 0;
-        a.deal = 1;
-    }
-    a.xrow = p.xrow;
-    a.g4 = (p.lgTC >= 2 && (g->Wout % 4) == 0 && ((uintptr_t)gy & 15) == 0) ? 1 : 0;
-    // buffer-load staging of the row tiles needs 16-byte aligned rows and 32-bit byte offsets inside one tile
-    // group and one channel block; otherwise the general kernel (MODE 0) runs
-    const long planeI = (long)g->Hin * g->Win, planeO = (long)g->Hout * g->Wout;
-    const int NIw = 64 >> (p.lgTC + p.lgTR);
-    const bool fits = (long)NIw * Cin * planeI < (1L << 28) && (long)NIw * g->Cout * planeO < (1L << 28) &&
-                      (long)p.CKW * planeI < (1L << 28) && (long)p.NT * 16 * planeO < (1L << 28);
-    static const int rowbuf = sprk::knob_env("SPRK_WG_ROWBUF", 1);
-    const bool fast = rowbuf && fits && a.g4;
-    a.xtab = fast ? 1 : 0;
-    if (a.xrow && (!fast || (((uintptr_t)x & 15) != 0))) {
-        sprk::set_error("conv2d_bwd_weight: 1x1 row staging needs 16-byte aligned x / gy and < 2^28-element tiles");
-        return SPRK_EINVAL;
-    }
-    // MODE 2 additionally needs 16-byte aligned x / x2 (the general kernel ignores the table area in LDS)
-    const bool planesOk = a.vec1 && (g->C2 == 0 || a.vec2);
-    const int mode = !fast ? 0 : (p.mode == 2 && !planesOk) ? 0 : p.mode;
-    static const int wg_diag = sprk::diag_env("SPRK_WG_DIAG");
-    a.diag = wg_diag;
-    a.nG1 = p.nG1;
-    a.nG2 = p.nG2;
+    WgArgs a;
+    int mode;
+    if (int rc = wgrad_args(g, p, x, x2, gy, wsf, a, &mode)) return rc;
     dim3 grid(p.groups, p.nChunks, p.nblkN);
     sprk::prof_begin(1, sprk::conv_flops(*g), s);
     const int rc = mode == 1 ? launch_wg<1>(a, p, grid, s) : mode == 2 ? launch_wg<2>(a, p, grid, s) : launch_wg<0>(a, p, grid, s);
     if (rc) return rc;
     sprk::prof_end(1, s);
     if (int rc2 = sprk::check_launch("conv_wgrad_mfma")) return rc2;
-    const int K = Cin * g->KH * g->KW;
+    const int K = (g->C1 + g->C2) * g->KH * g->KW;
     const sprk_reduce_item it{wsf + kZeroFloats, gw, SPRK_RED_WGRAD, p.groups, 0, K, g->Cout, p.CoutP};
     return sprk::finish_or_defer(it, item, s);
+}
+
+int sprk_conv2d_bwd_weight(const float *x, const float *x2, const float *gy, float *gw, const sprk_conv_geom *g,
+                           void *ws, size_t ws_bytes, void *stream) {
+    return wgrad_dispatch(x, x2, gy, gw, g, ws, ws_bytes, nullptr, stream);
+}
+
+int sprk_conv2d_bwd_weight_partial(const float *x, const float *x2, const float *gy, float *gw, const sprk_conv_geom *g,
+                                   void *ws, size_t ws_bytes, sprk_reduce_item *item, void *stream) {
+    return wgrad_dispatch(x, x2, gy, gw, g, ws, ws_bytes, item, stream);
 }
 
 static int act_nsplit(int N, int C) {

@@ -945,12 +945,7 @@ bool plan16(int Nimg, int Ck, int Nn, int Ho, int Wo, int KH, int KW, int padL, 
 template <typename T, int MT, int RB>
 int launch16_nt(const Conv16Args &k, const Plan16 &p, dim3 grid, hipStream_t s) {
     auto go = [&](auto kernel) {
-        if (p.ldsBytes > 64 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)p.ldsBytes) != hipSuccess) {
-            sprk::set_error("conv16: cannot reserve %zu bytes of LDS", p.ldsBytes);
-            return (int)SPRK_ELAUNCH;
-        }
+        if (int rc = sprk::lds_optin(kernel, p.ldsBytes, "conv16")) return rc;
         hipLaunchKernelGGL(kernel, grid, dim3(kBlock), p.ldsBytes, s, k);
         return (int)SPRK_OK;
     };
@@ -1016,11 +1011,7 @@ int launch_tile(const Tile16Args &k, const PlanT &p, hipStream_t s) {
     const int slots = std::max(1, sprk::num_cus() / p.nblkN);
     dim3 grid(persist ? std::min(ntiles, slots) : ntiles, p.nblkN);
     auto go = [&](auto kernel) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)p.ldsBytes) != hipSuccess) {
-            sprk::set_error("conv16: cannot reserve %zu bytes of LDS", p.ldsBytes);
-            return (int)SPRK_ELAUNCH;
-        }
+        if (int rc = sprk::lds_optin(kernel, p.ldsBytes, "conv16")) return rc;
         hipLaunchKernelGGL(kernel, grid, dim3(kTileThreads), p.ldsBytes, s, k);
         return (int)SPRK_OK;
     };
@@ -1151,11 +1142,7 @@ template <typename T, int CQ, int CK>
 static int launch_head(const Head16Args &a, int x16, int y16, hipStream_t s) {
     constexpr size_t lds = 2 * (size_t)((CK / 8) * 64 * (8 / CQ) * 16 + (CK / 8) * 96 * CQ * 16);
     auto go = [&](auto kernel) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess) {
-            set_error("conv16: cannot reserve %zu bytes of LDS", lds);
-            return (int)SPRK_ELAUNCH;
-        }
+        if (int rc = lds_optin(kernel, lds, "conv16")) return rc;
         hipLaunchKernelGGL(kernel, dim3(a.N * a.tilesPerImage), dim3(512), lds, s, a);
         return (int)SPRK_OK;
     };

@@ -35,7 +35,13 @@ int num_cus() {
     return v;
 }
 
+// The library's only hipFuncSetAttribute.  A kernel's limit is only ever raised, and the largest value granted is kept per
+// device and kernel, so a launch loop reaches the runtime once per kernel (or once per larger plan) instead of on every
+// launch; up to the 64 KiB every kernel may use unasked nothing happens at all.  The limit is a permission, not a
+// reservation: each launch passes its own ldsBytes as the dynamic size, so occupancy is that of the launch whatever was
+// granted before.  A captured graph holds the launches only; none of this is replayed.
 int lds_optin(const void *kernel, size_t bytes, const char *what) {
+    if (bytes <= 64 * 1024) return SPRK_OK;
     static std::mutex mu;
     static std::vector<std::tuple<int, const void *, size_t>> done;
     int dev = 0;

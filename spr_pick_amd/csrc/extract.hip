@@ -230,8 +230,7 @@ int launch_extract(const void *raw, int ny, int nx, const int *xy, int P, int B,
     const size_t box_bytes = (size_t)4 * b * b;
     const int resident = (flags & SPRK_EXTRACT_NORMALIZE) && box_bytes <= (size_t)kResidentBytes;
     const size_t lds = kScratchBytes + (resident ? box_bytes : 0);
-    if (int rc = sprk::lds_optin(reinterpret_cast<const void *>(extract_kernel<T>), kScratchBytes + kResidentBytes,
-                                 "extract_boxes"))
+    if (int rc = sprk::lds_optin(extract_kernel<T>, kScratchBytes + kResidentBytes, "extract_boxes"))
         return rc;
     hipLaunchKernelGGL(extract_kernel<T>, dim3(P), dim3(kThreads), lds, s, (const T *)raw, ny, nx, xy, B, N,
                        1.0f / (float)b, (long)R * R, flags, resident, out, status);

@@ -7,12 +7,13 @@
 
 namespace sprk {
 
-// c: the layer; with SPRK_DT_X16 in c.dtype x, x2 and gy are 16-bit tensors of the operand type
-bool wgrad16_eligible(const sprk_conv_geom &c);
+// c: the layer; with SPRK_DT_X16 in c.dtype x, x2 and gy are 16-bit tensors of the operand type.
+// The workspace of a call, 0 for a layer that is not eligible: one plan answers both questions of wgrad_dispatch
 size_t wgrad16_ws_bytes(const sprk_conv_geom &c);
-// item: see sprk_conv2d_bwd_weight_partial (nullptr = add the workgroups' partial dW now)
+inline bool wgrad16_eligible(const sprk_conv_geom &c) { return wgrad16_ws_bytes(c) != 0; }
+// ws: at least wgrad16_ws_bytes(c); item: see sprk_conv2d_bwd_weight_partial (nullptr = add the workgroups' partial dW now)
 int wgrad16_run(const sprk_conv_geom &c, const void *x, const void *x2, const void *gy, float *gw, void *ws,
-                size_t ws_bytes, sprk_reduce_item *item, hipStream_t s);
+                sprk_reduce_item *item, hipStream_t s);
 long wgrad16_launches();
 
 }  // namespace sprk

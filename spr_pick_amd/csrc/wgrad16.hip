@@ -635,21 +635,40 @@ static bool plan_wg1x1(const sprk_conv_geom &c, Plan1 *p) {
     return true;
 }
 
-bool wgrad16_eligible(const sprk_conv_geom &c) {
-    PlanW p;
-    Plan1 p1;
-    return plan_wg16(c, &p) || plan_wg1x1(c, &p1);
-}
-
 size_t wgrad16_ws_bytes(const sprk_conv_geom &c) {
     PlanW p;
     Plan1 p1;
-    return plan_wg16(c, &p) ? p.wsBytes : plan_wg1x1(c, &p1) ? p1.wsBytes : 0;
+    return plan_wg16(c, &p) ? p.wsBytes : plan_wg1x1(c, &p1) ? p1.wsBytes : 0;   // (no plan needs 0 bytes)
+}
+
+long wgrad16_launches() { return g_wgrad16_launches.load(); }
+
+template <typename K, typename A>
+static int launch_wg16(K kernel, dim3 grid, size_t ldsBytes, const A &a, const char *what, hipStream_t s) {
+    if (int rc = lds_optin(kernel, ldsBytes, what)) return rc;
+    hipLaunchKernelGGL(kernel, grid, dim3(kWgThreads), ldsBytes, s, a);
+    return SPRK_OK;
+}
+
+// What both kernel families do around their launch: pick(tag of the operand type) launches inside the profiling
+// bracket; the `parts` partial dW of n floats each that the workgroups leave in ws are summed now or described in *item.
+template <typename Pick>
+static int run_wg16(const sprk_conv_geom &c, Pick pick, const char *what, const void *ws, float *gw, int parts, long n,
+                    sprk_reduce_item *item, hipStream_t s) {
+    const bool x16 = (c.dtype & SPRK_DT_X16) != 0;
+    prof_begin(kClass16W, conv_flops(c), s);
+    prof_bytes((x16 ? 2.0 : 4.0) * c.N * ((double)(c.C1 + c.C2) * c.Hin * c.Win + (double)c.Cout * c.Hout * c.Wout));
+    const int rc = (c.dtype & SPRK_DT_MASK) == SPRK_DT_BF16 ? pick(__bf16{}) : pick(_Float16{});
+    if (rc) return rc;
+    prof_end(kClass16W, s);
+    if (int rc2 = check_launch(what)) return rc2;
+    g_wgrad16_launches.fetch_add(1, std::memory_order_relaxed);
+    const sprk_reduce_item it{(const float *)ws, gw, SPRK_RED_ROWS, parts, (int)n, 0, 0, 0};
+    return finish_or_defer(it, item, s);
 }
 
 static int wgrad16_run_1x1(const sprk_conv_geom &c, const Plan1 &p, const void *x, const void *gy, float *gw, void *ws,
-                           size_t ws_bytes, sprk_reduce_item *item, hipStream_t s) {
-    if (int rc = check_ws("wgrad16 (1x1)", ws, ws_bytes, p.wsBytes)) return rc;
+                           sprk_reduce_item *item, hipStream_t s) {
     if ((((uintptr_t)x | (uintptr_t)gy) & 15) != 0) {
         set_error("wgrad16 (1x1): tensors must be 16-byte aligned");
         return SPRK_EINVAL;
@@ -661,44 +680,26 @@ static int wgrad16_run_1x1(const sprk_conv_geom &c, const Plan1 &p, const void *
     a.regPerImg = p.regPerImg; a.nRegions = p.nRegions; a.perPart = p.perPart;
     static const int diag = sprk::diag_env("SPRK_C16_DIAG");
     a.diag = diag;
-    dim3 grid(p.parts, p.coBlocks, p.ciBlocks);
     auto go = [&](auto kernel) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)p.ldsBytes) != hipSuccess) {
-            set_error("wgrad16 (1x1): cannot reserve %zu bytes of LDS", p.ldsBytes);
-            return (int)SPRK_ELAUNCH;
-        }
-        hipLaunchKernelGGL(kernel, grid, dim3(kWgThreads), p.ldsBytes, s, a);
-        return (int)SPRK_OK;
+        return launch_wg16(kernel, dim3(p.parts, p.coBlocks, p.ciBlocks), p.ldsBytes, a, "wgrad16_1x1", s);
     };
     auto pick = [&](auto tag) {
         using T = decltype(tag);
         if (x16) return p.wide ? go(wgrad16_1x1_kernel<T, 4, 3, 6, true>) : go(wgrad16_1x1_kernel<T, 2, 3, 6, true>);
         return p.wide ? go(wgrad16_1x1_kernel<T, 4, 3, 6, false>) : go(wgrad16_1x1_kernel<T, 2, 3, 6, false>);
     };
-    prof_begin(kClass16W, conv_flops(c), s);
-    prof_bytes((x16 ? 2.0 : 4.0) * c.N * ((double)(c.C1 + c.C2) * c.Hin * c.Win + (double)c.Cout * c.Hout * c.Wout));
-    const int rc = (c.dtype & SPRK_DT_MASK) == SPRK_DT_BF16 ? pick(__bf16{}) : pick(_Float16{});
-    if (rc) return rc;
-    prof_end(kClass16W, s);
-    if (int rc2 = check_launch("wgrad16_1x1")) return rc2;
-    g_wgrad16_launches.fetch_add(1, std::memory_order_relaxed);
-    const sprk_reduce_item it{(const float *)ws, gw, SPRK_RED_ROWS, p.parts, c.Cout * c.C1, 0, 0, 0};
-    return finish_or_defer(it, item, s);
+    return run_wg16(c, pick, "wgrad16_1x1", ws, gw, p.parts, (long)c.Cout * c.C1, item, s);
 }
 
-long wgrad16_launches() { return g_wgrad16_launches.load(); }
-
 int wgrad16_run(const sprk_conv_geom &c, const void *x, const void *x2, const void *gy, float *gw, void *ws,
-                size_t ws_bytes, sprk_reduce_item *item, hipStream_t s) {
+                sprk_reduce_item *item, hipStream_t s) {
     PlanW p;
     if (!plan_wg16(c, &p)) {
         Plan1 p1;
-        if (plan_wg1x1(c, &p1)) return wgrad16_run_1x1(c, p1, x, gy, gw, ws, ws_bytes, item, s);
+        if (plan_wg1x1(c, &p1)) return wgrad16_run_1x1(c, p1, x, gy, gw, ws, item, s);
         set_error("wgrad16: geometry not eligible");
         return SPRK_EINVAL;
     }
-    if (int rc = check_ws("wgrad16", ws, ws_bytes, p.wsBytes)) return rc;
     const bool x16 = (c.dtype & SPRK_DT_X16) != 0;
     Wg16Args a{};
     a.x = x; a.x2 = x2; a.gy = gy; a.partial = (float *)ws;
@@ -707,17 +708,7 @@ int wgrad16_run(const sprk_conv_geom &c, const void *x, const void *x2, const vo
     static const int diag = sprk::diag_env("SPRK_C16_DIAG");
     a.diag = diag;
     a.xcd = xcd_on();
-    const int dt = c.dtype & SPRK_DT_MASK;
-    dim3 grid(p.parts, p.nBlocks);
-    auto go = [&](auto kernel) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)p.ldsBytes) != hipSuccess) {
-            set_error("wgrad16: cannot reserve %zu bytes of LDS", p.ldsBytes);
-            return (int)SPRK_ELAUNCH;
-        }
-        hipLaunchKernelGGL(kernel, grid, dim3(kWgThreads), p.ldsBytes, s, a);
-        return (int)SPRK_OK;
-    };
+    auto go = [&](auto kernel) { return launch_wg16(kernel, dim3(p.parts, p.nBlocks), p.ldsBytes, a, "wgrad16", s); };
     auto pick = [&](auto tag) {
         using T = decltype(tag);
         auto shape = [&](auto x16c, auto pl1c) {
@@ -730,16 +721,7 @@ int wgrad16_run(const sprk_conv_geom &c, const void *x, const void *x2, const vo
         if (x16) return pl1 ? shape(std::true_type{}, std::true_type{}) : shape(std::true_type{}, std::false_type{});
         return pl1 ? shape(std::false_type{}, std::true_type{}) : shape(std::false_type{}, std::false_type{});
     };
-    prof_begin(kClass16W, conv_flops(c), s);
-    prof_bytes((x16 ? 2.0 : 4.0) * c.N * ((double)(c.C1 + c.C2) * c.Hin * c.Win + (double)c.Cout * c.Hout * c.Wout));
-    const int rc = dt == SPRK_DT_BF16 ? pick(__bf16{}) : pick(_Float16{});
-    if (rc) return rc;
-    prof_end(kClass16W, s);
-    if (int rc2 = check_launch("wgrad16")) return rc2;
-    const long n = (long)c.Cout * (c.C1 + c.C2) * 9;
-    g_wgrad16_launches.fetch_add(1, std::memory_order_relaxed);
-    const sprk_reduce_item it{(const float *)ws, gw, SPRK_RED_ROWS, p.parts, (int)n, 0, 0, 0};
-    return finish_or_defer(it, item, s);
+    return run_wg16(c, pick, "wgrad16", ws, gw, p.parts, (long)c.Cout * (c.C1 + c.C2) * 9, item, s);
 }
 
 }  // namespace sprk

@@ -6,15 +6,6 @@
 
 namespace sprk {
 
-struct WinoWgArgs {
-    const float *x, *x2, *gy;   // sources [N,C1,H,W], [N,C2,H,W] (x2 may be null), output gradient [N,Cout,H,W]
-    float *gw;                  // [Cout][C1+C2][3][3]
-    float *partial;             // workspace of wino_wgrad_ws_bytes()
-    int N, C1, C2, H, W, Cout, padT, padL;
-    int kclass;
-    double flops;
-};
-
 bool wino_eligible(const Corr &c);
 size_t wino_ws_bytes(const Corr &c);
 // x, x2: sources [N,C1,H,W], [N,C2,H,W] (x2 may be null); w: the forward layer's taps (c.taps); y: [N,Cout,H,W], or
@@ -23,7 +14,10 @@ size_t wino_ws_bytes(const Corr &c);
 int wino_conv(const Corr &c, const float *x, const float *x2, const float *w, float *y, float *U, const float *mask,
               int mask_act, hipStream_t s);
 bool wino_wgrad_eligible(const sprk_conv_geom &g);
-size_t wino_wgrad_ws_bytes(int C1, int C2, int Cout);
-int wino_wgrad(const WinoWgArgs &a, hipStream_t s);
+size_t wino_wgrad_ws_bytes(const sprk_conv_geom &g);
+// x, x2: sources [N,C1,H,W], [N,C2,H,W] (x2 may be null); gy: [N,Cout,H,W]; gw: [Cout][C1+C2][3][3]; ws: workspace of
+// wino_wgrad_ws_bytes().  The kernel's own pass sums its partial results: nothing is left pending in the reduce item.
+int wino_wgrad(const sprk_conv_geom &g, const float *x, const float *x2, const float *gy, float *gw, void *ws,
+               sprk_reduce_item *, hipStream_t s);
 
 }  // namespace sprk

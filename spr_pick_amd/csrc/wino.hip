@@ -872,7 +872,7 @@ int wino_conv(const Corr &w, const float *x, const float *x2, const float *taps,
     const dim3 grid(persist ? std::min(a.ntiles, std::max(1, num_cus() / groups)) : a.ntiles, groups);
     const size_t lds = lds_bytes_of(NT);
     auto launch = [&](auto kernel) {
-        if (int rc = lds_optin(reinterpret_cast<const void *>(kernel), lds, "wino_conv")) return rc;
+        if (int rc = lds_optin(kernel, lds, "wino_conv")) return rc;
         hipLaunchKernelGGL(kernel, grid, dim3(kThreads), lds, s, a);
         return (int)SPRK_OK;
     };
@@ -932,52 +932,57 @@ bool wino_wgrad_eligible(const sprk_conv_geom &g) {
 }
 
 constexpr int kWgParts = 256;   // most partial results any launch leaves (one workgroup per CU)
+constexpr int kClassWinoW = 4;  // profiling class of wino_wgrad_kernel
 
-size_t wino_wgrad_ws_bytes(int C1, int C2, int Cout) {
-    return (size_t)kWgParts * Cout * (C1 + C2) * 9 * sizeof(float);
+size_t wino_wgrad_ws_bytes(const sprk_conv_geom &g) {
+    return (size_t)kWgParts * g.Cout * (g.C1 + g.C2) * 9 * sizeof(float);
 }
 
-int wino_wgrad(const WinoWgArgs &w, hipStream_t s) {
-    if ((((uintptr_t)w.x | (uintptr_t)w.x2 | (uintptr_t)w.gy | (uintptr_t)w.partial) & 15) != 0) {
+int wino_wgrad(const sprk_conv_geom &g, const float *x, const float *x2, const float *gy, float *gw, void *ws,
+               sprk_reduce_item *, hipStream_t s) {
+    float *partial = (float *)ws;
+    if ((((uintptr_t)x | (uintptr_t)x2 | (uintptr_t)gy | (uintptr_t)partial) & 15) != 0) {
         set_error("wino_wgrad: tensors must be 16-byte aligned");
         return SPRK_EINVAL;
     }
-    const int CinTot = w.C1 + w.C2;
+    const double flops = conv_flops(g);
+    const int CinTot = g.C1 + g.C2;
     WgRanges rg{};
     int nr = 0;
     auto launch = [&](const float *src, int Csrc, int ci0) -> int {
         int g48, tail;
         wg_split(Csrc, &g48, &tail);
-        WgKArgs a{src, w.gy, w.partial, w.N, Csrc, 0, ci0, CinTot, w.H, w.W, w.Cout, w.padT, w.padL, w.W / WRW, w.H / WRH, xcd_on()};
+        WgKArgs a{src, gy, partial, g.N, Csrc, 0, ci0, CinTot, g.Hin, g.Win, g.Cout, g.pad_top, g.pad_left, g.Win / WRW,
+                  g.Hin / WRH, xcd_on()};
         if (g48 > 0) {
-            if (int rc = lds_optin(reinterpret_cast<const void *>(wino_wgrad_kernel<3>), kWgLdsBytes, "wino_wgrad")) return rc;
+            if (int rc = lds_optin(wino_wgrad_kernel<3>, kWgLdsBytes, "wino_wgrad")) return rc;
             const int parts = std::min(kWgParts, num_cus()) / g48;   // K split: one workgroup per CU over all channel groups
-            prof_begin(w.kclass, w.flops * (48.0 * g48) / CinTot, s);
+            prof_begin(kClassWinoW, flops * (48.0 * g48) / CinTot, s);
             hipLaunchKernelGGL(wino_wgrad_kernel<3>, dim3(parts, g48), dim3(kThreads), kWgLdsBytes, s, a);
-            prof_end(w.kclass, s);
+            prof_end(kClassWinoW, s);
             if (int rc = check_launch("wino_wgrad<3>")) return rc;
             rg.end[nr] = ci0 + 48 * g48;
             rg.parts[nr++] = parts;
         }
         if (tail > 0) {
-            if (int rc = lds_optin(reinterpret_cast<const void *>(wino_wgrad_kernel<1>), kWgLdsBytes, "wino_wgrad")) return rc;
+            if (int rc = lds_optin(wino_wgrad_kernel<1>, kWgLdsBytes, "wino_wgrad")) return rc;
             WgKArgs t = a;
             t.cbase = 48 * g48;   // the tail group sits after the 48-channel groups
-            prof_begin(w.kclass, w.flops * (double)tail / CinTot, s);
+            prof_begin(kClassWinoW, flops * (double)tail / CinTot, s);
             hipLaunchKernelGGL(wino_wgrad_kernel<1>, dim3(std::min(kWgParts, num_cus()), 1), dim3(kThreads), kWgLdsBytes, s, t);
-            prof_end(w.kclass, s);
+            prof_end(kClassWinoW, s);
             if (int rc = check_launch("wino_wgrad<1>")) return rc;
             rg.end[nr] = ci0 + Csrc;
             rg.parts[nr++] = std::min(kWgParts, num_cus());
         }
         return SPRK_OK;
     };
-    if (int rc = launch(w.x, w.C1, 0)) return rc;
-    if (w.C2 > 0)
-        if (int rc = launch(w.x2, w.C2, w.C1)) return rc;
+    if (int rc = launch(x, g.C1, 0)) return rc;
+    if (g.C2 > 0)
+        if (int rc = launch(x2, g.C2, g.C1)) return rc;
     for (int i = nr; i < 4; ++i) rg.end[i] = CinTot, rg.parts[i] = rg.parts[nr - 1];
-    const long n = (long)w.Cout * CinTot * 9;
-    hipLaunchKernelGGL(wino_wgrad_reduce_kernel, dim3(cdiv(n, 32)), dim3(256), 0, s, w.partial, w.gw, n, CinTot, rg);
+    const long n = (long)g.Cout * CinTot * 9;
+    hipLaunchKernelGGL(wino_wgrad_reduce_kernel, dim3(cdiv(n, 32)), dim3(256), 0, s, partial, gw, n, CinTot, rg);
     if (int rc = check_launch("wino_wgrad_reduce")) return rc;
     g_wino_launches.fetch_add(1, std::memory_order_relaxed);
     return SPRK_OK;

@@ -118,11 +118,15 @@ def test_workspace_query_covers_the_dispatch():
     SPRK_EWORKSPACE: the query and the dispatcher agree on every kernel the call can take, whatever its operand type,
     flags and epilogue.  With fp32 activation tensors every one of these layers has a kernel, so the call succeeds;
     with SPRK_DT_X16 / _Y16 it may be refused (SPRK_EINVAL: no 16-bit-storage kernel), never for its workspace.
-    Planning runs on the host (no launch in describe mode), so this needs no GPU."""
+    Planning runs on the host (no launch in describe mode), so this needs no GPU.
+
+    Backward-weight has no describe mode, so it is asked the other way round: a call with an empty workspace is refused
+    before anything is launched, under the entry point's name, for a need B <= sprk_conv2d_bwd_weight_ws_bytes; with
+    SPRK_DT_X16 the storage guard may refuse it instead.  (SPRK_DT_NAIVE needs no workspace and would launch: left out.)"""
     import ctypes
     from spr_pick_amd import _lib
     L = _lib.lib()
-    OK, EWORKSPACE = 0, -2
+    OK, EINVAL, EWORKSPACE = 0, -1, -2
     W, WS, AUX = 0x100000, 0x200000, 0x300000          # never dereferenced in describe mode; 16-byte aligned
     store16 = _lib.DT_X16 | _lib.DT_Y16
     flags = (0, _lib.DT_FORCE, _lib.DT_PIN, store16, _lib.DT_NAIVE)
@@ -152,4 +156,16 @@ def test_workspace_query_covers_the_dispatch():
             assert rc != EWORKSPACE, ("bwd_data", what, need_b, L.sprk_last_error())
             assert rc == OK or (dt & store16), ("bwd_data", what, rc, L.sprk_last_error())
             calls += 1
-    assert calls == len(WS_GEOMS) * 15 * 6
+            if dt & _lib.DT_NAIVE:
+                continue
+            need_w = L.sprk_conv2d_bwd_weight_ws_bytes(ctypes.byref(g))
+            rc = L.sprk_conv2d_bwd_weight_partial(AUX, AUX, AUX, AUX, ctypes.byref(g), WS, 0, ctypes.byref(_lib.ReduceItem()),
+                                                  None)
+            err = L.sprk_last_error().decode()
+            if rc == EINVAL:
+                assert (dt & _lib.DT_X16) and "16-bit activation tensors" in err, ("bwd_weight", what, err)
+            else:
+                m = re.fullmatch(r"conv2d_bwd_weight: workspace 0 < (\d+)", err)
+                assert rc == EWORKSPACE and m and int(m.group(1)) <= need_w, ("bwd_weight", what, rc, err, need_w)
+            calls += 1
+    assert calls == len(WS_GEOMS) * (15 * 6 + 12)

@@ -868,6 +868,59 @@ def test_deferred_reductions_match_immediate(dtype):
     assert torch_ops.pending_count(d) == 0
 
 
+def _float_offset(t, off):
+    """A copy of ``t`` on the GPU that starts ``off`` floats into its (16-byte aligned) buffer."""
+    buf = torch.empty(t.numel() + 4, device=dev())
+    v = buf[off:off + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 4 * off
+    return v
+
+
+@pytest.mark.parametrize("which", ["x", "gy", "x+gy", "x2"])
+def test_conv2d_bwd_weight_float_aligned_tensors(which):
+    """Tensors that are float-aligned but not 16-byte aligned are legal input of the fp32 MFMA backward-weight kernel:
+    the call then leaves the plan's table-driven 16-byte staging (MODE 2 for this 3x3 layer) for the general kernel
+    (MODE 0).  x (or x2) offset: that source's planes go through dword DMA, the gy rows still in 16-byte pieces; gy
+    offset: the gy rows through dword DMA too.  Against conv2d_weight in fp64 at this file's gradient budget (5e-5 of
+    max |gw|), immediate and deferred, which must agree bit for bit."""
+    from spr_pick_amd import _lib, torch_ops
+    N, C1, C2, H, W, Cout, pad = 4, 48, (48 if which == "x2" else 0), 16, 16, (96 if which == "x2" else 48), (2, 0, 1, 1)
+    g = torch.Generator().manual_seed(41)
+    x = torch.randn(N, C1, H, W, generator=g)
+    x2 = torch.randn(N, C2, H, W, generator=g) if C2 else None
+    gy = torch.randn(N, Cout, H, W, generator=g)
+    xin = x if x2 is None else torch.cat((x, x2), 1)
+    want = torch.nn.grad.conv2d_weight(F.pad(xin.double(), (pad[2], pad[3], pad[0], pad[1])), (Cout, C1 + C2, 3, 3), gy.double())
+    xd = _float_offset(x, 1 if "x" in which.split("+") else 0)
+    x2d = None if x2 is None else _float_offset(x2, 1)
+    gyd = _float_offset(gy, 1 if "gy" in which else 0)
+    geom = torch_ops.geom_list(_lib.ConvGeom(N, C1, C2, H, W, 0, Cout, H, W, 3, 3, 1, 1, pad[0], pad[2], 0))
+    gw = [torch.full((Cout, C1 + C2, 3, 3), float("nan"), device=dev()) for _ in range(2)]
+    torch.ops.sprk.conv2d_bwd_weight(xd, x2d, gyd, geom, gw[0], False)
+    pending = torch_ops.pending_count(dev())
+    torch.ops.sprk.conv2d_bwd_weight(xd, x2d, gyd, geom, gw[1], True)
+    assert torch_ops.pending_count(dev()) == pending + 1
+    torch.ops.sprk.reduce_pending(gw[1])
+    close(gw[0], want, rel=5e-5, name="gw, %s one float off 16 bytes" % which)
+    assert torch.equal(gw[0], gw[1]), "deferred and immediate sums differ"
+
+
+def test_conv2d_bwd_weight_1x1_rows_need_16_byte_alignment():
+    """The row-staged 1x1 form (unpadded, stride 1, one full-resolution source) has no 4-byte staging: a float-aligned
+    x is refused with SPRK_EINVAL before anything is launched, and the gradient tensor is left alone."""
+    from spr_pick_amd import _lib, torch_ops
+    g = torch.Generator().manual_seed(42)
+    xd = _float_offset(torch.randn(4, 96, 16, 16, generator=g), 1)
+    gyd = torch.randn(4, 96, 16, 16, generator=g).to(dev())
+    geom = torch_ops.geom_list(_lib.ConvGeom(4, 96, 0, 16, 16, 0, 96, 16, 16, 1, 1, 1, 1, 0, 0, 0))
+    gw = torch.full((96, 96, 1, 1), 7.0, device=dev())
+    before = _lib.lib().sprk_launch_count()
+    with pytest.raises(_lib.SprkError, match=r"\(-1\): conv2d_bwd_weight: 1x1 row staging needs 16-byte aligned"):
+        torch.ops.sprk.conv2d_bwd_weight(xd, None, gyd, geom, gw, False)
+    assert _lib.lib().sprk_launch_count() == before and bool((gw == 7.0).all())
+
+
 def test_pu_loss_kernel_every_label_mix():
     """ops.pu_loss (one launch: value + gradient) against the oracle's statement of utils/losses.py:303-349 and the
     gradient autograd derives from the torch mask form, for mixed, all-unlabelled, all-labelled, single-unlabelled
