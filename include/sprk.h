@@ -108,7 +108,8 @@ typedef struct sprk_conv_epilogue {
  * entry points exist).  A binding must refuse a library whose sprk_version() differs from the header it was
  * written against, and may compare sprk_struct_bytes(0 | 1 | 2) with its own sizeof(sprk_conv_geom |
  * sprk_conv_epilogue | sprk_reduce_item). */
-#define SPRK_ABI_VERSION 430   /* 430: sprk_contam_*; sprk_ingest_* and sprk_extract_boxes joined it compatibly (no signature or struct changed:
+#define SPRK_ABI_VERSION 430   /* 430: sprk_contam_*; sprk_ingest_*, sprk_extract_boxes, sprk_conv2d_fwd_unrot[_eligible] and
+                                * sprk_unrot_act_bwd[_eligible] joined it compatibly (no signature or struct changed:
                                 * a binding that needs them finds a library without them by the missing symbol) */
 const char *sprk_last_error(void);
 int sprk_version(void);
@@ -261,6 +262,25 @@ int sprk_rot4_stack_bwd(const float *gy, float *gx, int B, int C, int P, void *s
 /* io = SPRK_IO2(type of the input, type of the output) */
 int sprk_unrot4_shift_concat_fwd(const void *d, void *f, int B, int C, int P, int io, void *stream);
 int sprk_unrot4_shift_concat_bwd(const void *gf, void *gd, int B, int C, int P, int io, void *stream);
+/* Training: sprk_unrot4_shift_concat_bwd followed by sprk_act_bwd of the activated layer that produced d, in one pass
+ * (fp32).  gf [B,4C,P,P]: gradient of f; f [B,4C,P,P]: the un-rotated tensor itself, which holds the layer's
+ * post-activation output at the very addresses its gradient arrives at, so the stack tensor d need not be kept;
+ * gpre [4B,C,P,P]: the layer's pre-activation gradient (row P-1 of every plane is +0); gbias as in sprk_act_bwd, with
+ * ws of sprk_act_bwd_ws_bytes(4B, C, P*P) bytes.  item != NULL: the bias sum is left pending (sprk_act_bwd_partial),
+ * NULL: finished at once.  Same additions in the same order as the two calls it replaces: bit-identical.
+ * sprk_unrot_act_bwd_eligible: 1 where the kernel exists (P == 64, act LEAKY or RELU), else the call is refused. */
+int sprk_unrot_act_bwd_eligible(int B, int C, int P, int act);
+/* Training: sprk_conv2d_fwd whose kernel stores straight into the un-rotated tensor: x (x2) are the 4B images of a
+ * 4-rotation stack, f [B,4*Cout,P,P] = sprk_unrot4_shift_concat_fwd(sprk_conv2d_fwd(...)) bit for bit, the stack tensor
+ * [4B,Cout,P,P] is never written (row 0 of every shifted plane, which no output reaches, is written as zeros by the same
+ * launch).  Same workspace, same prepared weights (sprk_conv2d_fwd_wprep, SPRK_DT_WPREP) as sprk_conv2d_fwd.
+ * sprk_conv2d_fwd_unrot_eligible: 1 where the call runs (the layer takes the fp32 Winograd kernel, P == 64, N % 4 == 0,
+ * 49..96 output channels, no fused up-sampling, no residual); elsewhere it is refused (SPRK_EINVAL). */
+int sprk_conv2d_fwd_unrot_eligible(const sprk_conv_geom *g, const sprk_conv_epilogue *ep);
+int sprk_conv2d_fwd_unrot(const float *x, const float *x2, const float *w, float *f, const sprk_conv_geom *g,
+                          const sprk_conv_epilogue *ep, void *ws, size_t ws_bytes, void *stream);
+int sprk_unrot_act_bwd(const float *gf, const float *f, float *gpre, float *gbias, int act, int B, int C, int P,
+                       void *ws, size_t ws_bytes, sprk_reduce_item *item, void *stream);
 
 /* ---- BatchNorm2d (+ optional ReLU), detector: joint_network_v2.py:547,558;
  * feature_extractor.py:287-288,320-324,338-346,412-414.

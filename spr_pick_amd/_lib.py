@@ -84,6 +84,10 @@ _SIGS = {
     "sprk_rot4_stack_bwd": (c_i, [c_f, c_f, c_i, c_i, c_i, c_vp]),
     "sprk_unrot4_shift_concat_fwd": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_vp]),
     "sprk_unrot4_shift_concat_bwd": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_vp]),
+    "sprk_unrot_act_bwd_eligible": (c_i, [c_i, c_i, c_i, c_i]),
+    "sprk_conv2d_fwd_unrot_eligible": (c_i, [ctypes.POINTER(ConvGeom), ctypes.POINTER(ConvEpilogue)]),
+    "sprk_conv2d_fwd_unrot": (c_i, [c_f, c_f, c_f, c_f, ctypes.POINTER(ConvGeom), ctypes.POINTER(ConvEpilogue), c_vp, c_sz, c_vp]),
+    "sprk_unrot_act_bwd": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_vp, c_sz, ctypes.POINTER(ReduceItem), c_vp]),
     "sprk_bn_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "sprk_bn_train_fwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, ctypes.c_float, ctypes.c_float, c_i, c_vp, c_sz, c_vp]),
     "sprk_bn_eval_fwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_float, c_i, c_vp]),

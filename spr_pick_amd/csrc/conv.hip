@@ -990,6 +990,73 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const TG *g, const TY *__r
     }
 }
 
+// Backward of Shift2d + chunk + rotate + concat (elem.hip: unrot4_tile64_kernel<false>) and the activation backward of
+// the layer in front of it in one pass, P = 64, fp32 (sprk_unrot_act_bwd).  gf [B,4C,P,P] is the gradient of the
+// un-rotated tensor f [B,4C,P,P], which is itself the mask: f at gf's address is y at the position the gradient goes
+// to, so plane (n = kB + b, c) of gpre [4B,C,P,P] reads gf and f at plane (b, kC + c) along its rows, masks there, and
+// turns the plane through LDS.  The decomposition is act_bwd_kernel's, so that the bias sums are the same additions in
+// the same order: grid (C, nsplit), workgroup (c, s) walks images s, s + nsplit, ..., thread t owns elements
+// 4t + 1024p of each plane.  Row P-1 of every gpre plane is +0 (Shift2d dropped it).
+__global__ __launch_bounds__(256) void unrot_act_bwd64_kernel(const float *__restrict__ gf, const float *__restrict__ f,
+                                                              float *__restrict__ gpre, float *__restrict__ partial,
+                                                              int act, int B, int C, int nsplit) {
+    constexpr int P = 64;
+    __shared__ float tile[P][P + 1];
+    const int c = blockIdx.x, s = blockIdx.y, N = 4 * B;
+    const int j4 = (threadIdx.x & 15) << 2, r0 = threadIdx.x >> 4;
+    const bool lk = act == SPRK_ACT_LEAKY;
+    float sum = 0.f;
+    for (int n = s; n < N; n += nsplit) {
+        const int k = n / B, b = n - k * B, rot = (4 - k) & 3;
+        const long src = (((long)b * 4 + k) * C + c) * (P * P);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int i = r0 + 16 * p;
+            float4 v = *reinterpret_cast<const float4 *>(gf + src + i * P + j4);
+            const float4 yv = *reinterpret_cast<const float4 *>(f + src + i * P + j4);
+            v.x = yv.x > 0.f ? v.x : (lk ? v.x * kLeak : 0.f);
+            v.y = yv.y > 0.f ? v.y : (lk ? v.y * kLeak : 0.f);
+            v.z = yv.z > 0.f ? v.z : (lk ? v.z * kLeak : 0.f);
+            v.w = yv.w > 0.f ? v.w : (lk ? v.w * kLeak : 0.f);
+            tile[i][j4] = v.x;
+            tile[i][j4 + 1] = v.y;
+            tile[i][j4 + 2] = v.z;
+            tile[i][j4 + 3] = v.w;
+        }
+        __syncthreads();
+        float *dst = gpre + ((long)n * C + c) * (P * P);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int r = r0 + 16 * p;
+            float o[4] = {0.f, 0.f, 0.f, 0.f};
+            if (r + 1 < P) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    // gd (r, j) <- gf at rot_dst(rot; r + 1, j)   (elem.hip)
+                    const int u = r + 1, w = j4 + q;
+                    const int i = rot == 0 ? u : rot == 1 ? P - 1 - w : rot == 2 ? P - 1 - u : w;
+                    const int j = rot == 0 ? w : rot == 1 ? u : rot == 2 ? P - 1 - w : P - 1 - u;
+                    o[q] = tile[i][j];
+                }
+            }
+            const float4 v = make_float4(o[0], o[1], o[2], o[3]);
+            *reinterpret_cast<float4 *>(dst + r * P + j4) = v;
+            sum += (v.x + v.y) + (v.z + v.w);
+        }
+        __syncthreads();
+    }
+    if (partial) {
+        __shared__ float red[256];
+        red[threadIdx.x] = sum;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) partial[c * nsplit + s] = red[0];
+    }
+}
+
 __global__ void concat_up_bwd_kernel(const float *__restrict__ gin, float *__restrict__ ga, float *__restrict__ gb,
                                      int N, int C1, int C2, int H, int W, int up1) {
     const int Cin = C1 + C2;
@@ -1518,11 +1585,14 @@ static int mask_in_place(float *gin, const float *mask_y, int mask_act, const sp
 // here ("The convolution dispatcher").  g / ep: the layer as the caller gave it; for backward-data x = gy,
 // x2 = null, y = gin, and mask_y / mask_act the optional mask of sprk_conv2d_bwd_data_masked.  The stages, in order:
 //   direct kernels (SPRK_DT_NAIVE; strided backward-data) -> 16-bit operands -> storage guard -> Winograd -> MFMA
+// unrot (forward only): y is the un-rotated tensor f [N/4, 4*Cout, H, W] of sprk_unrot4_shift_concat_fwd, stored by the
+// kernel itself (sprk_conv2d_fwd_unrot); only the fp32 Winograd stage has such a store, any other stage refuses.
 static int conv_dispatch(bool bwd, const float *x, const float *x2, const float *w, float *y, const sprk_conv_geom *g,
                          const sprk_conv_epilogue *ep, const float *mask_y, int mask_act, void *ws, size_t ws_bytes,
-                         void *stream) {
-    const char *who = bwd ? "conv2d_bwd_data" : "conv2d_fwd";
+                         void *stream, bool unrot = false) {
+    const char *who = bwd ? "conv2d_bwd_data" : unrot ? "conv2d_fwd_unrot" : "conv2d_fwd";
     if (int rc = check_geom(g)) return rc;
+    SPRK_REQUIRE(!unrot || sprk_conv2d_fwd_unrot_eligible(g, ep), "conv2d_fwd_unrot: no kernel with an un-rotated store for this layer");
     SPRK_REQUIRE(x && w && y, "%s: null tensor", who);
     if (bwd) {
         SPRK_REQUIRE(mask_act == SPRK_ACT_NONE || (mask_y && !g->up1), "conv2d_bwd_data: mask needs the saved input, no upsampling");
@@ -1559,9 +1629,10 @@ static int conv_dispatch(bool bwd, const float *x, const float *x2, const float 
         if (int rc = sprk::check_ws(who, ws, ws_bytes, sprk::wino_ws_bytes(c))) return rc;
         // the mask is d act / d y of the layer that produced this conv's input, applied in the output transform: gin
         // leaves the kernel as that layer's pre-activation gradient
-        if (int rc = sprk::wino_conv(c, x, x2, w, y, (float *)ws, mask_y, mask_act, s)) return rc;
+        if (int rc = sprk::wino_conv(c, x, x2, w, y, (float *)ws, mask_y, mask_act, s, unrot ? g->N / 4 : 0)) return rc;
         return sprk::check_launch(bwd ? "wino_conv(bwd_data)" : "wino_conv");
     }
+    SPRK_REQUIRE(!unrot, "conv2d_fwd_unrot: the call left the Winograd stage");
 
     FwdPlan p;
     SPRK_REQUIRE(plan_fwd(c, &p), "%s: geometry does not fit LDS", who);
@@ -1582,6 +1653,22 @@ int sprk_conv2d_fwd(const float *x, const float *x2, const float *w, float *y, c
                     const sprk_conv_epilogue *ep, void *ws, size_t ws_bytes, void *stream) {
     sprk::WprepScope scope(nullptr, g ? g->dtype : 0);
     return scope.verify(conv_dispatch(false, x, x2, w, y, g, ep, nullptr, SPRK_ACT_NONE, ws, ws_bytes, stream));
+}
+
+// 1: sprk_conv2d_fwd_unrot runs for this layer — the call would reach the fp32 Winograd stage of conv_dispatch (no
+// SPRK_DT_NAIVE, fp32 operands and tensors) and the kernel has the store (wino_unrot_eligible: a 4-rotation stack of
+// 64 x 64 planes, 49..96 output channels, no fused up-sampling or residual)
+int sprk_conv2d_fwd_unrot_eligible(const sprk_conv_geom *g, const sprk_conv_epilogue *ep) {
+    if (!g || check_geom(g) || naive_of(g)) return 0;
+    const sprk::Corr c(*g, ep);
+    if (c.dt() != SPRK_DT_F32 || c.x16() || c.y16()) return 0;
+    return sprk::wino_unrot_eligible(c) ? 1 : 0;
+}
+
+int sprk_conv2d_fwd_unrot(const float *x, const float *x2, const float *w, float *f, const sprk_conv_geom *g,
+                          const sprk_conv_epilogue *ep, void *ws, size_t ws_bytes, void *stream) {
+    sprk::WprepScope scope(nullptr, g ? g->dtype : 0);
+    return scope.verify(conv_dispatch(false, x, x2, w, f, g, ep, nullptr, SPRK_ACT_NONE, ws, ws_bytes, stream, true));
 }
 
 int sprk_conv2d_fwd_wprep(const float *w, const sprk_conv_geom *g, const sprk_conv_epilogue *ep, void *ws,
@@ -1733,6 +1820,33 @@ int sprk_act_bwd_partial(const void *g, const void *y, void *gpre, float *gbias,
     });
     SPRK_REQUIRE(drc == 0, "act_bwd: bad storage types (io)");
     if (int rc = sprk::check_launch("act_bwd")) return rc;
+    if (gbias) {
+        const sprk_reduce_item it{(const float *)ws, gbias, SPRK_RED_COLS, ns, C, 0, 0, 0};
+        return sprk::finish_or_defer(it, item, s);
+    }
+    return SPRK_OK;
+}
+
+int sprk_unrot_act_bwd_eligible(int B, int C, int P, int act) {
+    return B > 0 && C > 0 && P == 64 && (act == SPRK_ACT_LEAKY || act == SPRK_ACT_RELU);
+}
+
+int sprk_unrot_act_bwd(const float *gf, const float *f, float *gpre, float *gbias, int act, int B, int C, int P,
+                       void *ws, size_t ws_bytes, sprk_reduce_item *item, void *stream) {
+    if (item) *item = sprk_reduce_item{nullptr, nullptr, SPRK_RED_NONE, 0, 0, 0, 0, 0};
+    SPRK_REQUIRE(gf && f && gpre && gpre != gf && gpre != f, "unrot_act_bwd: null or aliased tensor");
+    SPRK_REQUIRE(sprk_unrot_act_bwd_eligible(B, C, P, act), "unrot_act_bwd: needs P == 64 and an activation (B %d, C %d, P %d, act %d)",
+                 B, C, P, act);
+    SPRK_REQUIRE((((uintptr_t)gf | (uintptr_t)f | (uintptr_t)gpre) & 15) == 0, "unrot_act_bwd: tensors must be 16-byte aligned");
+    const int N = 4 * B, ns = act_nsplit(N, C);
+    if (gbias && (ws_bytes < (size_t)C * ns * sizeof(float) || !ws)) {
+        sprk::set_error("unrot_act_bwd: workspace too small");
+        return SPRK_EWORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(unrot_act_bwd64_kernel, dim3(C, ns), dim3(256), 0, s, gf, f, gpre, gbias ? (float *)ws : nullptr, act,
+                       B, C, ns);
+    if (int rc = sprk::check_launch("unrot_act_bwd")) return rc;
     if (gbias) {
         const sprk_reduce_item it{(const float *)ws, gbias, SPRK_RED_COLS, ns, C, 0, 0, 0};
         return sprk::finish_or_defer(it, item, s);

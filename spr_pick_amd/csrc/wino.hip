@@ -116,12 +116,17 @@ struct KArgs {
     const float *x, *x2, *U, *bias, *scale, *shift, *mask;
     float *y;
     int N, C1, C2, H, W, Cout, padT, padL, act, tilesX, tilesY, ntiles, nc1, nch, up2, xcd, diag, mact;
+    int unrotB;   // UNROT kernels: images per rotation of the stack (N = 4 * unrotB), y is f [unrotB, 4 * Cout, H, W]
 #ifdef WINO_STAMP
     unsigned *dbg;
 #endif
 };
 
-template <int NT, int SQ>
+// UNROT (training, decode_block_1[2] at P = 64): the output transform stores each finished 2x2 tile of stack image
+// n = k * B + b, channel c straight into plane (b, k * Cout + c) of the un-rotated tensor (elem.hip: Shift2d + chunk +
+// rotate + concat), f[i][j] = y[s][v] at (i, j) = rot_dst((4 - k) & 3; s + 1, v): the stack tensor is never written.
+// An instantiation of its own: the other launches of a step keep their code.
+template <int NT, int SQ, int UNROT = 0>
 __global__ __launch_bounds__(kThreads, 1) void wino_conv_kernel(const KArgs a) {
     constexpr int UFLOATS = ufloats_of(NT);
     constexpr int TR = Geo<SQ>::TR, TC = Geo<SQ>::TC, RP = Geo<SQ>::RP, RPLANE = Geo<SQ>::RPLANE, LGTX = Geo<SQ>::LGTX;
@@ -377,7 +382,41 @@ __global__ __launch_bounds__(kThreads, 1) void wino_conv_kernel(const KArgs a) {
     float *E = smem + 2 * UFLOATS + 2 * RAWF;
     // reader lane -> tile (row rl_ty, column rl_tx) = tile index T = (rl_ty << LGTX) + rl_tx = lane
     const int rl_tx = lane & ((1 << LGTX) - 1), rl_ty = lane >> LGTX;
-    const int tprime = lane;
+    int tprime = lane;
+    // UNROT: byte offsets inside f's plane of the lane's two pair stores and of its edge stores (kXZero: dropped), and
+    // whether the edge stores write the zero line
+    int uoffA = kXZero, uoffB = kXZero, uoffE = kXZero, urot = 0, uk = 0, ub = 0;
+    bool uzero = false;
+    if constexpr (UNROT) {
+        uk = __builtin_amdgcn_readfirstlane(e_n / a.unrotB);
+        ub = e_n - uk * a.unrotB;
+        urot = (4 - uk) & 3;
+        const int P = a.W;
+        // 90 / 270 degrees: the output row follows the stack COLUMN, so consecutive lanes walk down the tile column
+        // (runs of 64 >> LGTX pairs along the output row); the reader lane -> tile map is free (E is indexed by tile)
+        const int tx = (urot & 1) ? lane >> (6 - LGTX) : rl_tx, ty = (urot & 1) ? lane & ((64 >> LGTX) - 1) : rl_ty;
+        tprime = (ty << LGTX) + tx;
+        const int s0 = e_by * TR + 2 * ty, v0 = e_bx * TC + 2 * tx;   // first stack row / column of the lane's tile
+        const bool top = s0 == 0, last = s0 == P - 2;                  // zero line; the tile's second row is dropped
+        uzero = top;
+        if (urot == 0) {          // (i, j) = (s + 1, v): pairs (o0[0], o0[1]), (o1[0], o1[1]); zero row 0
+            uoffA = ((s0 + 1) * P + v0) * 4;
+            uoffB = last ? kXZero : uoffA + P * 4;
+            uoffE = top ? v0 * 4 : kXZero;
+        } else if (urot == 2) {   // (i, j) = (P-2-s, P-1-v): pairs reversed; zero row P-1
+            uoffA = ((P - 2 - s0) * P + (P - 2 - v0)) * 4;
+            uoffB = last ? kXZero : uoffA - P * 4;
+            uoffE = top ? ((P - 1) * P + (P - 2 - v0)) * 4 : kXZero;
+        } else if (urot == 3) {   // (i, j) = (v, P-2-s): rows v0, v0+1, pairs (o1[c], o0[c]) from column P-3-s0; zero column P-1
+            uoffA = last ? kXZero : (v0 * P + (P - 3 - s0)) * 4;
+            uoffB = last ? kXZero : uoffA + P * 4;
+            uoffE = top ? (v0 * P + P - 1) * 4 : last ? (v0 * P) * 4 : kXZero;   // second edge store: + one row
+        } else {                  // (i, j) = (P-1-v, s+1): rows P-1-v0, P-2-v0, pairs (o0[c], o1[c]) from column s0+1; zero column 0
+            uoffA = last ? kXZero : ((P - 1 - v0) * P + s0 + 1) * 4;
+            uoffB = last ? kXZero : uoffA - P * 4;
+            uoffE = top ? ((P - 2 - v0) * P) * 4 : last ? ((P - 2 - v0) * P + P - 1) * 4 : kXZero;   // rows P-2-v0 (c = 1), then + one row (c = 0)
+        }
+    }
     // stores: a wave-uniform plane pointer (scalar arithmetic) + the lane's fixed byte offset inside the tile
     const int lane_off = a.up2 ? ((4 * rl_ty) * (2 * a.W) + 4 * rl_tx) * 4 : ((2 * rl_ty) * a.W + 2 * rl_tx) * 4;
     const long tile_org = a.up2 ? ((long)(2 * e_by * TR) * (2 * a.W) + 2 * e_bx * TC) : ((long)(e_by * TR) * a.W + e_bx * TC);
@@ -405,9 +444,9 @@ __global__ __launch_bounds__(kThreads, 1) void wino_conv_kernel(const KArgs a) {
         // the reader in three forms picked once per pass (plain / masked by a fused activation backward / fused x2
         // up-sampling stores) instead of run-time branches per channel; channel planes by pointer increments
         auto reader = [&](auto modec) {
-            constexpr int MODE = decltype(modec)::value;   // 0 plain, 1 mask, 2 up2
-            const long ch0 = (long)e_n * a.Cout + grp * (NT * 16) + pass * 32 + wave;
-            const float *yc = uniform_ptr(a.y + ch0 * plane + tile_org);
+            constexpr int MODE = decltype(modec)::value;   // 0 plain, 1 mask, 2 up2, 3 un-rotated store
+            const long ch0 = (MODE == 3 ? (long)(ub * 4 + uk) : (long)e_n) * a.Cout + grp * (NT * 16) + pass * 32 + wave;
+            const float *yc = uniform_ptr(a.y + ch0 * plane + (MODE == 3 ? 0 : tile_org));
             const float *mc = MODE == 1 ? uniform_ptr(a.mask + ch0 * plane + tile_org) : nullptr;
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
@@ -447,7 +486,23 @@ __global__ __launch_bounds__(kThreads, 1) void wino_conv_kernel(const KArgs a) {
                     // buffer stores: wave-uniform descriptor (plane + tile origin, scalar arithmetic), the lane's fixed
                     // byte offset, the row stride in the scalar offset — no vector address arithmetic in the epilogue
                     const rsrc_t yr = make_rsrc(yc);
-                    if constexpr (MODE == 2) {   // nearest x2 upsampling fused into the stores: each value to its 2x2 block
+                    if constexpr (MODE == 3) {
+                        const int rowb = 4 * a.W;
+                        if (urot & 1) {   // 90 / 270 degrees: the pair is one column of the tile, (o0[c], o1[c]) or reversed
+                            const bool rev = urot == 3;
+                            __builtin_amdgcn_raw_buffer_store_b64((u32x2){fbits(rev ? o1[0] : o0[0]), fbits(rev ? o0[0] : o1[0])}, yr, uoffA, 0, 0);
+                            __builtin_amdgcn_raw_buffer_store_b64((u32x2){fbits(rev ? o1[1] : o0[1]), fbits(rev ? o0[1] : o1[1])}, yr, uoffB, 0, 0);
+                            // edge lanes, one element per row: the zero column, or o0[c] alone where o1[c] is the dropped row
+                            const unsigned e0 = uzero ? 0u : fbits(rev ? o0[0] : o0[1]), e1 = uzero ? 0u : fbits(rev ? o0[1] : o0[0]);
+                            __builtin_amdgcn_raw_buffer_store_b32(e0, yr, uoffE, 0, 0);
+                            __builtin_amdgcn_raw_buffer_store_b32(e1, yr, uoffE, rowb, 0);
+                        } else {          // 0 / 180 degrees: the pair is one row of the tile, reversed for 180
+                            const bool rev = urot == 2;
+                            __builtin_amdgcn_raw_buffer_store_b64((u32x2){fbits(rev ? o0[1] : o0[0]), fbits(rev ? o0[0] : o0[1])}, yr, uoffA, 0, 0);
+                            __builtin_amdgcn_raw_buffer_store_b64((u32x2){fbits(rev ? o1[1] : o1[0]), fbits(rev ? o1[0] : o1[1])}, yr, uoffB, 0, 0);
+                            __builtin_amdgcn_raw_buffer_store_b64((u32x2){0u, 0u}, yr, uoffE, 0, 0);   // the zero row (top tiles)
+                        }
+                    } else if constexpr (MODE == 2) {   // nearest x2 upsampling fused into the stores: each value to its 2x2 block
                         const int W2b = 8 * a.W;
                         const u32x4 r0 = {fbits(o0[0]), fbits(o0[0]), fbits(o0[1]), fbits(o0[1])},
                                     r1 = {fbits(o1[0]), fbits(o1[0]), fbits(o1[1]), fbits(o1[1])};
@@ -464,7 +519,9 @@ __global__ __launch_bounds__(kThreads, 1) void wino_conv_kernel(const KArgs a) {
                 if constexpr (MODE == 1) mc += 8 * plane;
             }
         };
-        if (a.up2)
+        if constexpr (UNROT)
+            reader(IC<3>{});
+        else if (a.up2)
             reader(IC<2>{});
         else if (a.mask)
             reader(IC<1>{});
@@ -839,8 +896,12 @@ size_t wino_ws_bytes(const Corr &c) {
     return (size_t)groups * nch * ufloats_of(NT) * sizeof(float);
 }
 
+bool wino_unrot_eligible(const Corr &c) {
+    return wino_eligible(c) && nt_of(c.Cout) == 6 && c.Hin == 64 && c.Win == 64 && c.N % 4 == 0 && !c.ep.up2 && c.taps == 0;
+}
+
 int wino_conv(const Corr &w, const float *x, const float *x2, const float *taps, float *y, float *U, const float *mask,
-              int mask_act, hipStream_t s) {
+              int mask_act, hipStream_t s, int unrotB) {
     const int NT = nt_of(w.Cout), groups = cdiv(w.Cout, NT * 16);
     const int kclass = w.Cout > 48 ? kClassWino : 2;
     KArgs a{};
@@ -853,7 +914,15 @@ int wino_conv(const Corr &w, const float *x, const float *x2, const float *taps,
     a.xcd = xcd_on();
     static const int diag = sprk::diag_env("SPRK_WINO_DIAG");   // timing experiments only
     a.diag = diag;
-    const int sq = wino_square(a.H, a.W);
+    a.unrotB = unrotB;
+    if (unrotB && (mask || !wino_unrot_eligible(w) || unrotB * 4 != w.N)) {
+        set_error("wino_conv: no un-rotated store for this call");
+        return SPRK_EINVAL;
+    }
+    // (un-rotated store: 4 x 16 tiles give 32-byte runs along the output row for 90 / 270 degrees and 128-byte runs for
+    // 0 / 180, 8 x 8 tiles 64-byte runs for all four; SPRK_WINO_UNROT_SQ=1 in a diagnostic build takes the latter)
+    static const int unrot_sq = knob_env("SPRK_WINO_UNROT_SQ", 0);
+    const int sq = (unrotB && unrot_sq) ? 1 : wino_square(a.H, a.W);
     a.tilesX = a.W / (sq ? Geo<1>::TC : Geo<0>::TC); a.tilesY = a.H / (sq ? Geo<1>::TR : Geo<0>::TR);
     a.ntiles = a.tilesX * a.tilesY * w.N;
     a.nc1 = cdiv(w.C1, CK);
@@ -883,7 +952,8 @@ int wino_conv(const Corr &w, const float *x, const float *x2, const float *taps,
     a.dbg = dbg;
 #endif
     prof_begin(kclass, w.flops, s);
-    if (int rc = NT == 6 ? (sq ? launch(wino_conv_kernel<6, 1>) : launch(wino_conv_kernel<6, 0>))
+    if (int rc = unrotB ? (sq ? launch(wino_conv_kernel<6, 1, 1>) : launch(wino_conv_kernel<6, 0, 1>))
+                 : NT == 6 ? (sq ? launch(wino_conv_kernel<6, 1>) : launch(wino_conv_kernel<6, 0>))
                          : (sq ? launch(wino_conv_kernel<3, 1>) : launch(wino_conv_kernel<3, 0>)))
         return rc;
     prof_end(kclass, s);

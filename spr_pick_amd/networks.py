@@ -73,16 +73,17 @@ class Conv2d(nn.Module):
         p = self.padding
         return (p, p, p, p)
 
-    def forward(self, x, skip=None, up=False, up_out=False, x_act=ACT_NONE, premasked=False):
+    def forward(self, x, skip=None, up=False, up_out=False, x_act=ACT_NONE, premasked=False, unrot_out=False):
         """skip: second input source (channel concat); up: x is half resolution, upsampled on load;
         up_out: write the output nearest-upsampled x2 (the nn.Upsample that follows in the reference);
-        x_act / premasked: activation backward fused into the neighbouring operators (ops.conv2d)."""
+        x_act / premasked: activation backward fused into the neighbouring operators (ops.conv2d);
+        unrot_out: return the un-rotated [B,4*Cout,P,P] tensor of a blind-spot stack (ops.conv2d)."""
         # inference (no autograd): the kernel choice is pinned to the layer's structure (_lib.DT_PIN), so that a window
         # of a micrograph gets the very arithmetic the whole micrograph gets (Denoiser._tiled_networks)
         dtype = self.mfma_dtype if torch.is_grad_enabled() else (self.mfma_dtype_nograd | DT_PIN)
         return ops.conv2d(x, self.weight, self.bias, x2=skip, up1=up, stride=self.stride, dil=self.dilation,
                           pad=self._pad(), act=self.act, up_out=up_out, dtype=dtype, x_act=x_act, premasked=premasked,
-                          store16=self.store16 and (dtype & 0xff) != 0)
+                          store16=self.store16 and (dtype & 0xff) != 0, unrot_out=unrot_out)
 
     def extra_repr(self):
         return "%d, %d, kernel_size=%s, stride=%d, padding=%d, dilation=%d, act=%d%s" % (
@@ -127,6 +128,11 @@ class ShiftMaxPool(nn.Module):
 FUSED_UNROT = True      # debug: False = materialise the un-rotated [B,384,P,P] tensor in front of the fused head
 FUSED_HEAD = True       # debug: False = the three 1x1 convolutions of a U-Net's head as separate launches in inference too
 FUSE_ACT_BWD = True     # debug: False = every convolution runs its own activation-backward pass
+# Training at P = 64, fp32: the un-rotation runs inside its neighbours.  Both False = the separate
+# unrot4_shift_concat operator (the stack tensor is then written, and kept for backward); one of them False = that half
+# as separate kernels (debug / A-B).
+FUSE_UNROT_STORE = True   # the last decoder convolution's Winograd kernel stores the un-rotated tensor itself
+FUSE_UNROT_BWD = True     # un-rotation backward + that convolution's activation backward in one kernel
 
 
 def _kaiming_leaky(mod):
@@ -300,8 +306,17 @@ class DualNetwork(_UNetBase):
                                   (self.decode_block_1, x, False)):
             fuse_c = self._fuse_chain(blk[0], blk[2])
             t = blk[0](t, skip=skip, premasked=fuse_c)
-            t = blk[2](t, up_out=up_out, x_act=blk[0].act if fuse_c else ACT_NONE)
-        if self._blindspot:
+            # training at P = 64: the last decoder convolution hands on the un-rotated tensor itself and keeps only that
+            # (its backward is one kernel for un-rotation backward + activation backward)
+            unrot = 0
+            if self._blindspot and blk is self.decode_block_1 and (FUSE_UNROT_STORE or FUSE_UNROT_BWD):
+                c = blk[2]
+                if FUSE_UNROT_STORE and ops.unrot_store_eligible(t, c.weight, c.bias, c._pad(), c.act, c.mfma_dtype):
+                    unrot |= ops.UNROT_STORE
+                if FUSE_UNROT_BWD and ops.unrot_train_eligible(t, c.act, c.mfma_dtype):
+                    unrot |= ops.UNROT_BWD
+            t = blk[2](t, up_out=up_out, x_act=blk[0].act if fuse_c else ACT_NONE, unrot_out=unrot)
+        if self._blindspot and not unrot:
             c1, c2, c3 = self.output_block[0], self.output_block[2], self.output_conv
             if FUSED_HEAD and FUSED_UNROT and ops.head1x1_unrot_eligible(t, c1, c2, c3):
                 # inference: Shift2d + un-rotation + concat are the input gather of the fused head

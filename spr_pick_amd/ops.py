@@ -190,15 +190,19 @@ def make_geom(x, x2, w, up1, stride, dil, pad, out_hw=None, dtype=0):
     return ConvGeom(N, C1, C2, Hin, Win, 1 if up1 else 0, Cout, Hout, Wout, KH, KW, stride, dil, pt, pl, int(dtype))
 
 
-def conv2d_forward(x, x2, w, g, bias=None, act=ACT_NONE, scale=None, shift=None, res=None, res_off=0, up_out=False):
+def conv2d_forward(x, x2, w, g, bias=None, act=ACT_NONE, scale=None, shift=None, res=None, res_off=0, up_out=False,
+                   unrot=False):
     """Raw forward launch (no autograd).  Returns y [N,Cout,Hout,Wout] ([N,Cout,2Hout,2Wout] with
-    ``up_out``: nearest x2 upsampling fused into the store)."""
+    ``up_out``: nearest x2 upsampling fused into the store; the un-rotated [N/4,4*Cout,Hout,Wout] with ``unrot``:
+    sprk_conv2d_fwd_unrot, same workspace and prepared weights as the plain call)."""
     _need_act(x, x2)
     _need_gpu(w, bias, scale, shift, res)
     ws = None
     if _WPREP is not None:
         ep = torch_ops._epilogue(bias, scale, shift, res, int(res_off), int(act), up_out)
         g, ws = _prep_fwd(w, g, (bool(up_out), res is not None), ep)
+    if unrot:
+        return _S.conv2d_fwd_unrot(x, x2, w, bias, geom_list(g), int(act), ws)
     return _S.conv2d_fwd(x, x2, w, bias, scale, shift, res, geom_list(g), int(res_off), int(act), 1 if up_out else 0, ws)
 
 
@@ -238,8 +242,8 @@ class _Conv2dFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, x2, w, bias, up1, stride, dil, pad, act, up_out, dtype, x_act=ACT_NONE, premasked=False,
-                store16=False):
-        ctx.x_act, ctx.premasked = x_act, premasked
+                store16=False, unrot_out=False):
+        ctx.x_act, ctx.premasked, ctx.unrot_out = x_act, premasked, unrot_out
         ctx.in_dtypes = (x.dtype, None if x2 is None else x2.dtype)
         x = x.contiguous()
         x2 = None if x2 is None else x2.contiguous()
@@ -258,7 +262,18 @@ class _Conv2dFn(torch.autograd.Function):
             x2 = None if x2 is None else x2.float()
             in16 = False
         g.dtype |= (_lib.DT_X16 if in16 else 0) | (_lib.DT_Y16 if (store16 and (caps & 1)) else 0)
-        y = conv2d_forward(x, x2, w, g, bias=bias, act=act, up_out=up_out)
+        if unrot_out:
+            # the layer's output leaves as the un-rotated f [B,4*Cout,P,P]; f is also what backward keeps (it holds y at
+            # the addresses the gradient arrives at: sprk_unrot_act_bwd).  UNROT_STORE: the kernel's output transform
+            # writes f itself and the stack tensor never exists; otherwise it is un-rotated and released here.
+            if act == ACT_NONE or premasked or up_out or in16 or (g.dtype & 0xff) or g.N % 4 or g.Hout != g.Wout:
+                raise _lib.SprkError("conv2d: unrot_out needs an activated fp32 layer on a 4-rotation stack of square images")
+            if unrot_out & UNROT_STORE:
+                y = conv2d_forward(x, x2, w, g, bias=bias, act=act, unrot=True)
+            else:
+                y = _S.unrot4_shift_concat_fwd(conv2d_forward(x, x2, w, g, bias=bias, act=act))
+        else:
+            y = conv2d_forward(x, x2, w, g, bias=bias, act=act, up_out=up_out)
         ctx.geom = g
         ctx.caps = caps
         ctx.act = act
@@ -287,7 +302,20 @@ class _Conv2dFn(torch.autograd.Function):
         # premasked: the consumer of this layer's output (the next convolution's backward-data, or the pooling backward)
         # has already multiplied the gradient by act'(y): only the bias sum is left of the activation backward
         act_here = ACT_NONE if ctx.premasked else ctx.act
-        if act_here != ACT_NONE or need_b or up2:
+        if ctx.unrot_out:
+            # gy is the gradient of f, y is f
+            defer_b = False
+            if need_b:
+                gb, defer_b = _grad_dest(bias)
+            if ctx.unrot_out & UNROT_BWD:
+                # un-rotation backward + activation backward (+ bias sum) in one kernel
+                gpre = _S.unrot_act_bwd(gy.contiguous(), y, act_here, gb, defer_b)
+            else:
+                # two kernels (debug / A-B): the un-rotation backward of f gives the stack tensor back, but for its
+                # dropped last row, whose gradient is +0 whatever the mask says
+                gd = _S.unrot4_shift_concat_bwd(gy.contiguous())
+                gpre = _S.act_bwd(gd, _S.unrot4_shift_concat_bwd(y), act_here, [g.N, g.Cout, g.Hout, g.Wout], 0, True, gb, defer_b, 0)
+        elif act_here != ACT_NONE or need_b or up2:
             want_gpre = act_here != ACT_NONE or bool(up2)
             defer_b = False
             if need_b:
@@ -368,24 +396,55 @@ class _Conv2dFn(torch.autograd.Function):
                 gx = gx.to(ctx.in_dtypes[0])
             if gx2 is not None and ctx.in_dtypes[1] is not None and gx2.dtype != ctx.in_dtypes[1]:
                 gx2 = gx2.to(ctx.in_dtypes[1])
-        return gx, gx2, gw, gb, None, None, None, None, None, None, None, None, None, None
+        return gx, gx2, gw, gb, None, None, None, None, None, None, None, None, None, None, None
 
 
 def conv2d(x, w, bias=None, x2=None, up1=False, stride=1, dil=1, pad=(0, 0, 0, 0), act=ACT_NONE, up_out=False,
-           dtype=0, x_act=ACT_NONE, premasked=False, store16=False):
+           dtype=0, x_act=ACT_NONE, premasked=False, store16=False, unrot_out=False):
     """y = act(conv(cat(up2(x) if up1 else x, x2), w) + bias); pad = (top, bottom, left, right).
     up_out: return nearest-x2-upsampled y (the upsampling is fused into the conv's stores).
     dtype: _lib.DT_F32 / DT_BF16 / DT_F16 — precision of the MFMA operands in forward, backward-data and
     backward-weight (a request: layers without a 16-bit kernel run in fp32; tensors are fp32 either way).
     Activation backward fused into the neighbours (conv -> conv and conv -> pool chains; a pair of promises the CALLER
     makes, networks.py): ``premasked`` — this layer's output is consumed by exactly one operator, which was told so
-    (``x_act``) and returns the gradient already multiplied by act'(y); ``x_act`` — x is such an output."""
+    (``x_act``) and returns the gradient already multiplied by act'(y); ``x_act`` — x is such an output.
+    unrot_out (training; UNROT_STORE | UNROT_BWD, each where its query says so: ``unrot_store_eligible``,
+    ``unrot_train_eligible``): x is a 4-rotation stack [4B,..]; returns unrot4_shift_concat(y) [B,4*Cout,P,P] and keeps
+    that tensor instead of y.  UNROT_STORE: the convolution kernel stores it directly; UNROT_BWD: the un-rotation
+    backward and this layer's activation backward are one kernel.  Bit-identical to the operators applied one after the
+    other, whichever bits are set."""
     _need_act(x, x2)
     _need_gpu(w, bias)
     if premasked and (up_out or act == ACT_NONE):
         raise ValueError("conv2d: premasked needs an activated, not upsampled output")
     return _Conv2dFn.apply(x, x2, w, bias, bool(up1), int(stride), int(dil), tuple(int(p) for p in pad), int(act),
-                           bool(up_out), int(dtype), int(x_act), bool(premasked), bool(store16))
+                           bool(up_out), int(dtype), int(x_act), bool(premasked), bool(store16), int(unrot_out))
+
+
+UNROT_STORE, UNROT_BWD = 1, 2
+
+
+def unrot_store_eligible(x, w, bias, pad, act, dtype=0, x2=None):
+    """Will conv2d(x, w, bias, x2=x2, pad=pad, act=act, dtype=dtype, unrot_out=UNROT_STORE) find a kernel with the
+    un-rotated store (sprk_conv2d_fwd_unrot_eligible: the fp32 Winograd kernel at P == 64)?  Asked before the call."""
+    if not torch.is_grad_enabled() or (dtype & 0xff) != 0 or x.dtype != _F32 or not x.is_cuda or act == ACT_NONE:
+        return False
+    if x.dim() != 4 or x.shape[0] % 4 or (x2 is not None and x2.dtype != _F32):
+        return False
+    g = make_geom(x, x2, w, False, 1, 1, pad, dtype=dtype)
+    ep = torch_ops._epilogue(bias, None, None, None, 0, int(act), False)
+    return bool(_lib.lib().sprk_conv2d_fwd_unrot_eligible(ctypes.byref(g), ctypes.byref(ep)))
+
+
+def unrot_train_eligible(x, conv_act, dtype=0):
+    """May the convolution that takes the 4-rotation stack x [4B,C,P,P] run with ``unrot_out`` (conv2d)?  True where
+    sprk_unrot_act_bwd has a kernel for what its backward will be handed: autograd recording, fp32 operands and
+    tensors, square P == 64 planes, an activated layer."""
+    if not torch.is_grad_enabled() or (dtype & 0xff) != 0 or x.dtype != _F32 or not x.is_cuda:
+        return False
+    if x.dim() != 4 or x.shape[0] % 4 or x.shape[2] != x.shape[3]:
+        return False
+    return bool(_lib.lib().sprk_unrot_act_bwd_eligible(x.shape[0] // 4, 1, x.shape[2], int(conv_act)))
 
 
 # ---- U-Net plumbing -----------------------------------------------------------------------------

@@ -97,6 +97,25 @@ def _conv2d_fwd(x, x2, w, bias, scale, shift, res, geom, res_off, act, up_out, w
     return y
 
 
+def _conv2d_fwd_unrot(x, x2, w, bias, geom, act, ws):
+    """The convolution of a 4-rotation stack whose kernel stores the un-rotated tensor: -> f [N/4, 4*Cout, P, P]
+    (sprk_conv2d_fwd_unrot; the caller asked sprk_conv2d_fwd_unrot_eligible)."""
+    L = _lib.lib()
+    g = ConvGeom(*geom)
+    f = _f32(x, (g.N // 4, 4 * g.Cout, g.Hout, g.Wout))
+    ep = _epilogue(bias, None, None, None, 0, act, False)
+    if ws is None:
+        ws = _ws(L.sprk_conv2d_fwd_ws_bytes(ctypes.byref(g)), x)
+    check(L.sprk_conv2d_fwd_unrot(_p(x), _p(x2), _p(w), _p(f), ctypes.byref(g), ctypes.byref(ep), _p(ws), ws.numel(), _stream(x)),
+          "sprk_conv2d_fwd_unrot")
+    return f
+
+
+_register("conv2d_fwd_unrot", "(Tensor x, Tensor? x2, Tensor w, Tensor? bias, int[] geom, int act, Tensor? ws) -> Tensor",
+          _conv2d_fwd_unrot,
+          lambda x, x2, w, bias, geom, act, ws: x.new_empty((geom[0] // 4, 4 * geom[6], geom[7], geom[8])))
+
+
 def _conv2d_fwd_fake(x, x2, w, bias, scale, shift, res, geom, res_off, act, up_out, ws):
     m = 2 if up_out else 1
     return x.new_empty((geom[0], geom[6], geom[7] * m, geom[8] * m), dtype=TORCH_OF[_out_code(geom[15])])
@@ -256,6 +275,29 @@ _register("act_bwd", "(Tensor gy, Tensor? y, int act, int[] nchw, int up2, bool 
                      "int out_code) -> Tensor", _act_bwd,
           lambda gy, y, act, nchw, up2, want_gpre, gbias, defer, out_code: gy.new_empty(
               tuple(nchw) if want_gpre else (0,), dtype=TORCH_OF[out_code] if want_gpre else gy.dtype))
+
+
+def _unrot_act_bwd(gf, f, act, gbias, defer):
+    """Un-rotation backward + activation backward in one pass (sprk_unrot_act_bwd): gf, f [B,4C,P,P] -> gpre [4B,C,P,P];
+    bias gradient into ``gbias`` when given (defer: its final sum is left to ``reduce_pending``)."""
+    L = _lib.lib()
+    B, C4, P, P2 = gf.shape
+    if C4 % 4 or P != P2 or tuple(f.shape) != tuple(gf.shape) or gf.dtype != torch.float32 or f.dtype != torch.float32:
+        raise _lib.SprkError("unrot_act_bwd: bad tensors %s %s / %s %s" % (tuple(gf.shape), gf.dtype, tuple(f.shape), f.dtype))
+    C = C4 // 4
+    gpre = _f32(gf, (4 * B, C, P, P))
+    nb = L.sprk_act_bwd_ws_bytes(4 * B, C, P * P)
+    ws = _ws(nb, gf)
+    item = _lib.ReduceItem() if (defer and gbias is not None) else None
+    check(L.sprk_unrot_act_bwd(_p(gf), _p(f), _p(gpre), _p(gbias), act, B, C, P, _p(ws), nb,
+                               ctypes.byref(item) if item is not None else None, _stream(gf)), "sprk_unrot_act_bwd")
+    if item is not None:
+        _pend(gf.device, item, ws)
+    return gpre
+
+
+_register("unrot_act_bwd", "(Tensor gf, Tensor f, int act, Tensor(a!)? gbias, bool defer) -> Tensor", _unrot_act_bwd,
+          lambda gf, f, act, gbias, defer: gf.new_empty((4 * gf.shape[0], gf.shape[1] // 4, gf.shape[2], gf.shape[3])))
 
 
 def _concat_up_bwd(gin, C1, C2, up1, x_shape, x2_shape):
