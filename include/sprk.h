@@ -481,6 +481,24 @@ int sprk_ingest_bin(const void *raw, int mode, int ny, int nx, int bin, float *b
                     size_t ws_bytes, void *stream);
 int sprk_ingest_finish(const float *binned, int by, int bx, const float *range, uint8_t *u8_out, float *net_out, int S,
                        void *stream);
+/* sprk_ingest_clip (optional, between the two): the binned image clamped to two of its own order statistics, so that
+ * a hot pixel or a black spot no longer sets the range sprk_ingest_finish normalises by.
+ *   binned_in [by,bx] fp32 as sprk_ingest_bin leaves it (finite), n = by*bx < 2^31; range_in float[2] device: its min
+ *   and max (sprk_ingest_bin's range_out); ranks 0 <= k_lo <= k_hi <= n-1.
+ *   key(x) = the order-preserving uint32 encoding of the fp32 bits (negative: ~bits, else bits | 2^31; it orders -0.0
+ *   before +0.0).  lo = the element with the k_lo-th smallest key (counting from 0), hi = the one with the k_hi-th
+ *   smallest: exact order statistics, no interpolation — each an element of the image, bit for bit.
+ *   binned_out[i] = x < lo ? lo : (x > hi ? hi : x) in float comparisons (signed zeros are left alone; binned_out may
+ *   be binned_in); range_out float[2] device = (lo, hi) (may be range_in).  lo and hi survive the clamp, so the min-max
+ *   of binned_out is range_out, on the device and for micrograph_io.minmax_uint8 on the host alike.
+ *   k_lo = 0, k_hi = n-1 is the identity (same image, same range).
+ * Selection: a radix select on d = key(x) - key(min) in three passes of at most 11 bits taken from the highest set bit
+ * of key(max) - key(min) downward (found on the device); every pass counts into per-workgroup 2048-bin histograms
+ * (one per rank while their prefixes differ) in the workspace, which every workgroup writes in full: nothing to
+ * initialise.  Ten launches on `stream`, no host synchronisation. */
+size_t sprk_ingest_clip_ws_bytes(int by, int bx);
+int sprk_ingest_clip(const float *binned_in, float *binned_out, int by, int bx, long long k_lo, long long k_hi,
+                     const float *range_in, float *range_out, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- particle extraction (`joint extract`) -----------------------------------------------
  * Boxes cut out of ONE raw micrograph (the buffer sprk_ingest_bin takes: [ny,nx] samples of mode 0 / 1 / 2 / 6, 16-byte

@@ -45,6 +45,15 @@ def _bin_factor(text):
     return n
 
 
+def _clip(text):
+    """--clip LO[,HI]: ingest.parse_clip, its ValueError as the parser's usage error."""
+    from .ingest import parse_clip
+    try:
+        return parse_clip(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 class _Parser(argparse.ArgumentParser):
     """A (sub-)parser may carry ``check``: arguments validated against each other at parse time (ValueError -> the
     parser's usage error), so that `--box 100 --bin 3` is refused like any other bad value and not by a traceback."""
@@ -58,6 +67,11 @@ class _Parser(argparse.ArgumentParser):
             except ValueError as e:
                 self.error(str(e))
         return ns, rest
+
+
+def _check_eval(ns):
+    if ns.clip is not None and ns.bin is None:
+        raise ValueError("--clip belongs to the raw-micrograph ingest: give --bin N as well (N = 1 for unbinned files)")
 
 
 def _check_extract(ns):
@@ -102,12 +116,20 @@ def build_parser():
     ev.add_argument("--bin", type=_bin_factor, metavar="N",
                     help="the dataset holds RAW micrographs (MRC mode 0/1/2/6): bin each N x N, normalise and pad it on "
                          "the GPU instead of preparing binned copies; for N > 1 also writes {name}_scores_unbinned.txt")
+    ev.add_argument("--clip", type=_clip, metavar="LO[,HI]",
+                    help="with --bin: clamp each binned micrograph to its LO %% / (100 - HI) %% order statistics before the "
+                         "min-max normalisation, so that hot pixels and black spots do not set the range (HI = LO when "
+                         "omitted; 0 changes nothing)")
+    ev.check = _check_eval
 
     bn = cmds.add_parser("bin", help="Bin raw micrographs N x N on the GPU (replaces the `newstack -bin N` preparation).")
     bn.add_argument("--dataset", "-d", required=True, help="Table (image_name, path) or directory of raw MRC micrographs.")
     bn.add_argument("--bin", type=_bin_factor, required=True, metavar="N", help="bin factor (at most 16, SPRK_INGEST_MAX_BIN)")
     bn.add_argument("--out", "-o", required=True, help="Directory for {name}.mrc (float32), images.txt and labels.txt.")
     bn.add_argument("--labels", "-l", help="Particle coordinates of the raw micrographs; written binned to labels.txt.")
+    bn.add_argument("--clip", type=_clip, metavar="LO[,HI]",
+                    help="write the block means clamped to their LO %% / (100 - HI) %% order statistics (as `joint eval "
+                         "--bin N --clip` sees them); HI = LO when omitted")
 
     ex = cmds.add_parser("extract", help="Cut normalised particle stacks out of raw micrographs on the GPU "
                                          "(replaces the relion_preprocess step after picking).")
@@ -174,7 +196,7 @@ def run_train(args, parser):
 def run_eval(args):
     from .eval import DenoiserEvaluator
     evaluator = DenoiserEvaluator(args["model"], runs_dir=args["runs_dir"], contamination=args.get("contamination", False),
-                                  bin=args.get("bin"))
+                                  bin=args.get("bin"), clip=args.get("clip"))
     for flag, key in (("batch_size", ConfigValue.TEST_MINIBATCH_SIZE), ("nms", ConfigValue.NMS),
                       ("num", ConfigValue.NUM_EVAL)):
         if args.get(flag) is not None:
@@ -187,7 +209,7 @@ def run_eval(args):
 
 def run_bin(args):
     from . import ingest
-    return ingest.bin_dataset(args["dataset"], args["bin"], args["out"], labels=args.get("labels"))
+    return ingest.bin_dataset(args["dataset"], args["bin"], args["out"], labels=args.get("labels"), clip=args.get("clip"))
 
 
 def run_extract(args):

@@ -26,6 +26,17 @@
 //                                                           of MicrographFeed; refl folds as often as np.pad does)
 // in one launch: 32 x 32 tiles transposed through LDS, reads coalesced along the binned rows, writes along the net rows.
 //
+// Optional, between the two (sprk_ingest_clip): the binned image clamped to two of its own order statistics, which then
+// are the range stage B normalises by.  A radix select on d = key(x) - key(min) (min / max: stage A's range, read on the
+// device): three passes of at most 11 bits, taken from the highest set bit of key(max) - key(min) downward — a
+// micrograph's values share sign, exponent and leading mantissa bits, so digits at fixed positions would put every pixel
+// in one bin.  A pass: every workgroup (at most 256, grid-stride, 16-byte loads) counts the elements whose higher digits
+// match each rank's prefix into 2048-bin LDS histograms, one per rank while the prefixes differ, aggregated inside the
+// wave first, and stores its whole partial (nothing to zero, no same-address global atomics: see the note on stage A's
+// range); a second kernel sums the partials; a one-workgroup kernel scans the sums, picks each rank's bin and updates
+// (prefix, k) in the workspace.  Then the clamp x < lo ? lo : (x > hi ? hi : x) and the new range.  Exact: lo and hi are
+// elements of the image.  No host synchronisation.
+//
 // No a*b+c of this file may be contracted into an FMA.  hipcc contracts by default, and HIP's __fmul_rn / __fadd_rn are
 // plain operators that it contracts all the same (x*scale + shift came out as one v_fma_f32, and a file-scope
 // `#pragma clang fp contract(off)` did not stop it), so the Makefile compiles this translation unit with
@@ -229,6 +240,215 @@ __global__ __launch_bounds__(kThreads) void ingest_finish_kernel(const float *__
     }
 }
 
+// ---- sprk_ingest_clip: two order statistics of the binned image by radix select, then the clamp --------------------
+constexpr int kClipBins = 2048;      // an 11-bit digit
+constexpr int kClipPasses = 3;       // 11 + 11 + 10 bits cover any span of keys
+constexpr int kClipBlocks = 256;     // grid cap of the histogram kernel = partial histograms in the workspace
+constexpr int kClipThreads = 1024;   // ... whose workgroups are large instead: four waves per SIMD at one workgroup per CU
+constexpr int kPeelRounds = 4;
+
+// workspace: ClipState | sums [2][kClipBins] | partials [grid][2][kClipBins] (uint32); index 0 = the low rank, 1 = the high
+struct ClipState {
+    unsigned int prefix[2];   // the bits of d = key(x) - key(min) of each rank's element above the digits still to come
+    unsigned int k[2];        // its rank among the elements that share that prefix
+    float lohi[2];            // after the last pass: the two elements themselves
+    unsigned int pad[2];
+};
+
+// pass p takes bits [shift, top) of d, at most 11 from the highest set bit of the span down; top == shift: none left
+struct ClipDigits {
+    int top, shift;
+    unsigned int mask;
+};
+__device__ __forceinline__ ClipDigits clip_digits(unsigned int span, int pass) {
+    const int nbits = span ? 32 - __clz((int)span) : 0;
+    ClipDigits g;
+    g.top = max(nbits - 11 * pass, 0);
+    g.shift = max(g.top - 11, 0);
+    g.mask = (1u << (g.top - g.shift)) - 1u;
+    return g;
+}
+
+// One count per active lane into hist[digit].  Lanes that hold the same digit elect one lane, which adds their number:
+// a tied, two-valued or near-constant image puts a whole wave on one bin, and same-address LDS atomics serialise.  A
+// few rounds peel the wave's most common digits; what is left is spread over bins and adds lane by lane.  Every lane
+// of the wave must call (inactive ones with active == false).
+__device__ __forceinline__ void wave_count(unsigned int *hist, bool active, unsigned int digit) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(active);
+    for (int round = 0; round < kPeelRounds && todo; ++round) {
+        const int leader = __ffsll(todo) - 1;
+        const unsigned int dl = (unsigned int)__shfl((int)digit, leader, 64);
+        const unsigned long long same = __ballot(active && digit == dl);
+        if (lane == leader) atomicAdd(&hist[dl], (unsigned int)__popcll(same));
+        todo &= ~same;
+    }
+    if ((todo >> lane) & 1) atomicAdd(&hist[digit], 1u);
+}
+
+// vec: x starts 16-byte aligned (float4 loads, the next one in flight while this one is counted; the n % 4 tail one
+// element per lane).  Loop bounds are uniform over the workgroup, so that every lane reaches wave_count.
+__global__ __launch_bounds__(kClipThreads) void clip_hist_kernel(const float *__restrict__ x, long n, int vec,
+                                                             const float *__restrict__ range, int pass,
+                                                             const ClipState *__restrict__ st,
+                                                             unsigned int *__restrict__ partials) {
+    __shared__ unsigned int hist[2 * kClipBins];
+    const unsigned int kmin = enc(range[0]);
+    const ClipDigits g = clip_digits(enc(range[1]) - kmin, pass);
+    if (g.top == g.shift) return;
+    const unsigned int p0 = pass ? st->prefix[0] : 0u, p1 = pass ? st->prefix[1] : 0u;
+    const bool two = p0 != p1;                     // else both ranks share histogram 0
+    const int used = (two ? 2 : 1) * kClipBins;
+    for (int i = threadIdx.x; i < used; i += kClipThreads) hist[i] = 0u;
+    __syncthreads();
+    auto count = [&](bool in, float v) {
+        const unsigned int d = enc(v) - kmin;
+        const unsigned int pre = (unsigned int)((unsigned long long)d >> g.top);
+        const unsigned int digit = (d >> g.shift) & g.mask;                  // < kClipBins whatever v is
+        wave_count(hist, in && pre == p0, digit);
+        if (two) wave_count(hist + kClipBins, in && pre == p1, digit);
+    };
+    const long nvec = vec ? n / 4 : 0;
+    const long stride = (long)gridDim.x * kClipThreads;
+    auto load = [&](long e) {
+        return e < nvec ? reinterpret_cast<const float4 *>(x)[e] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    };
+    float4 v = load((long)blockIdx.x * kClipThreads + threadIdx.x);
+    for (long base = (long)blockIdx.x * kClipThreads; base < nvec; base += stride) {
+        const long e = base + threadIdx.x;
+        const float4 ahead = load(e + stride);
+        const bool in = e < nvec;
+        count(in, v.x);
+        count(in, v.y);
+        count(in, v.z);
+        count(in, v.w);
+        v = ahead;
+    }
+    for (long base = nvec * 4 + (long)blockIdx.x * kClipThreads; base < n; base += stride) {
+        const long e = base + threadIdx.x;
+        const bool in = e < n;
+        count(in, in ? x[e] : 0.0f);
+    }
+    __syncthreads();
+    unsigned int *out = partials + (size_t)blockIdx.x * 2 * kClipBins;       // the whole partial: nothing to initialise
+    for (int i = threadIdx.x; i < used; i += kClipThreads) out[i] = hist[i];
+}
+
+// grid (kClipBins / 64, 2): 64 bins of one histogram per workgroup, the partials dealt to its four waves
+__global__ __launch_bounds__(kThreads) void clip_sum_kernel(const unsigned int *__restrict__ partials, int nparts,
+                                                            const float *__restrict__ range, int pass,
+                                                            const ClipState *__restrict__ st,
+                                                            unsigned int *__restrict__ sums) {
+    __shared__ unsigned int red[kThreads / 64][64];
+    const ClipDigits g = clip_digits(enc(range[1]) - enc(range[0]), pass);
+    if (g.top == g.shift) return;
+    const int h = blockIdx.y;
+    if (h == 1 && (pass == 0 || st->prefix[0] == st->prefix[1])) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bin = blockIdx.x * 64 + lane;
+    unsigned int s = 0;
+    for (int i = wave; i < nparts; i += kThreads / 64) s += partials[((size_t)i * 2 + h) * kClipBins + bin];
+    red[wave][lane] = s;
+    __syncthreads();
+    if (wave == 0) {
+        for (int w = 1; w < kThreads / 64; ++w) s += red[w][lane];
+        sums[h * kClipBins + bin] = s;
+    }
+}
+
+// one workgroup: for both ranks, the bin of the summed histogram that holds the rank -> the next (prefix, k).  Thread
+// t owns bins 8t .. 8t+7.  Pass 0 starts from (0, k_lo), (0, k_hi); a pass without bits hands the state on as it is.
+__global__ __launch_bounds__(kThreads) void clip_pick_kernel(const unsigned int *__restrict__ sums,
+                                                             const float *__restrict__ range, int pass,
+                                                             unsigned int k_lo, unsigned int k_hi, ClipState *st) {
+    constexpr int PER = kClipBins / kThreads;
+    __shared__ unsigned int wtot[kThreads / 64];
+    __shared__ ClipState next;
+    const unsigned int kmin = enc(range[0]);
+    const ClipDigits g = clip_digits(enc(range[1]) - kmin, pass);
+    if (threadIdx.x == 0) {
+        if (pass) {
+            next = *st;
+        } else {
+            next.prefix[0] = next.prefix[1] = 0u;
+            next.k[0] = k_lo;
+            next.k[1] = k_hi;
+            next.lohi[0] = next.lohi[1] = 0.0f;
+            next.pad[0] = next.pad[1] = 0u;
+        }
+    }
+    __syncthreads();
+    const unsigned int prefix[2] = {next.prefix[0], next.prefix[1]}, rank[2] = {next.k[0], next.k[1]};
+    const bool two = prefix[0] != prefix[1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (g.top != g.shift) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const unsigned int *h = sums + (two && r ? kClipBins : 0);
+            unsigned int c[PER], t = 0;
+#pragma unroll
+            for (int j = 0; j < PER; ++j) {
+                c[j] = h[threadIdx.x * PER + j];
+                t += c[j];
+            }
+            unsigned int inc = t;                                  // inclusive scan of t over the workgroup
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned int u = (unsigned int)__shfl_up((int)inc, o, 64);
+                if (lane >= o) inc += u;
+            }
+            __syncthreads();                                       // wtot of the other rank has been read
+            if (lane == 63) wtot[wave] = inc;
+            __syncthreads();
+            unsigned int cum = inc - t;
+            for (int w = 0; w < wave; ++w) cum += wtot[w];
+            const unsigned int k = rank[r];
+            if (k >= cum && k - cum < t) {                         // the one thread whose bins hold rank k
+                bool done = false;
+#pragma unroll
+                for (int j = 0; j < PER; ++j) {
+                    if (!done) {
+                        if (k - cum < c[j]) {
+                            next.prefix[r] = (prefix[r] << (g.top - g.shift)) | (unsigned int)(threadIdx.x * PER + j);
+                            next.k[r] = k - cum;
+                            done = true;
+                        } else {
+                            cum += c[j];
+                        }
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (pass == kClipPasses - 1) {                             // shift == 0 by now: the prefix is all of d
+            next.lohi[0] = dec(kmin + next.prefix[0]);
+            next.lohi[1] = dec(kmin + next.prefix[1]);
+        }
+        *st = next;
+    }
+}
+
+// y may be x (every element is read and written by the same lane); vec: both start 16-byte aligned
+__global__ __launch_bounds__(kThreads) void clip_clamp_kernel(const float *x, float *y, long n, int vec,
+                                                              const ClipState *__restrict__ st, float *range_out) {
+    const float lo = st->lohi[0], hi = st->lohi[1];
+    auto clamp = [&](float v) { return v < lo ? lo : (v > hi ? hi : v); };
+    const long nvec = vec ? n / 4 : 0;
+    const long stride = (long)gridDim.x * kThreads;
+    for (long e = (long)blockIdx.x * kThreads + threadIdx.x; e < nvec; e += stride) {
+        const float4 v = reinterpret_cast<const float4 *>(x)[e];
+        reinterpret_cast<float4 *>(y)[e] = make_float4(clamp(v.x), clamp(v.y), clamp(v.z), clamp(v.w));
+    }
+    for (long e = nvec * 4 + (long)blockIdx.x * kThreads + threadIdx.x; e < n; e += stride) y[e] = clamp(x[e]);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        range_out[0] = lo;
+        range_out[1] = hi;
+    }
+}
+
+int clip_grid(long n) { return (int)std::min<long>(kClipBlocks, sprk::cdiv(sprk::cdiv(n, 4), kClipThreads)); }
+
 int sample_bytes(int mode) {
     switch (mode) {
         case SPRK_MRC_INT8: return 1;
@@ -314,6 +534,42 @@ int sprk_ingest_finish(const float *binned, int by, int bx, const float *range, 
                        dim3(kTile, kThreads / kTile), 0, (hipStream_t)stream, binned, by, bx, range, u8_out, net_out, La,
                        Lb);
     return sprk::check_launch("ingest_finish");
+}
+
+size_t sprk_ingest_clip_ws_bytes(int by, int bx) {
+    if (by < 1 || bx < 1 || (long)by * bx >= (1L << 31)) return 0;
+    return sizeof(ClipState) + (size_t)(2 + 2 * clip_grid((long)by * bx)) * kClipBins * sizeof(unsigned int);
+}
+
+int sprk_ingest_clip(const float *binned_in, float *binned_out, int by, int bx, long long k_lo, long long k_hi,
+                     const float *range_in, float *range_out, void *ws, size_t ws_bytes, void *stream) {
+    SPRK_REQUIRE(binned_in && binned_out && range_in && range_out, "ingest_clip: null pointer");
+    SPRK_REQUIRE(by > 0 && bx > 0 && (long)by * bx < (1L << 31), "ingest_clip: bad image size %dx%d", by, bx);
+    const long n = (long)by * bx;
+    SPRK_REQUIRE(k_lo >= 0 && k_lo <= k_hi && k_hi <= n - 1,
+                 "ingest_clip: ranks %lld, %lld of %ld elements (0 <= k_lo <= k_hi <= n-1)", k_lo, k_hi, n);
+    if (int rc = sprk::check_ws("ingest_clip", ws, ws_bytes, sprk_ingest_clip_ws_bytes(by, bx))) return rc;
+    SPRK_REQUIRE(((uintptr_t)ws & 15) == 0, "ingest_clip: the workspace must start 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    ClipState *st = (ClipState *)ws;
+    unsigned int *sums = (unsigned int *)(st + 1), *partials = sums + 2 * kClipBins;
+    const int grid = clip_grid(n);
+    const int vec_in = ((uintptr_t)binned_in & 15) == 0, vec_out = vec_in && ((uintptr_t)binned_out & 15) == 0;
+    for (int pass = 0; pass < kClipPasses; ++pass) {
+        hipLaunchKernelGGL(clip_hist_kernel, dim3(grid), dim3(kClipThreads), 0, s, binned_in, n, vec_in, range_in, pass, st,
+                           partials);
+        if (int rc = sprk::check_launch("ingest_clip_hist")) return rc;
+        hipLaunchKernelGGL(clip_sum_kernel, dim3(kClipBins / 64, 2), dim3(kThreads), 0, s, partials, grid, range_in, pass,
+                           st, sums);
+        if (int rc = sprk::check_launch("ingest_clip_sum")) return rc;
+        hipLaunchKernelGGL(clip_pick_kernel, dim3(1), dim3(kThreads), 0, s, sums, range_in, pass, (unsigned int)k_lo,
+                           (unsigned int)k_hi, st);
+        if (int rc = sprk::check_launch("ingest_clip_pick")) return rc;
+    }
+    const int grid_clamp = std::min(sprk::ew_blocks(sprk::cdiv(n, 4)), kMaxBlocks);      // plain streaming: no partials
+    hipLaunchKernelGGL(clip_clamp_kernel, dim3(grid_clamp), dim3(kThreads), 0, s, binned_in, binned_out, n, vec_out, st,
+                       range_out);
+    return sprk::check_launch("ingest_clip_clamp");
 }
 
 }  // extern "C"

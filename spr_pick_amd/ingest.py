@@ -7,9 +7,15 @@ ranged, normalised and laid out by csrc/ingest.hip (``torch.ops.sprk.ingest_bin`
 is bit for bit what the host path produces from the binned image: ``binned_uint8(path, N)`` equals ``load_image`` of
 the float32 MRC that ``joint bin --bin N`` writes, and ``ingest(path, 1)`` equals ``MicrographFeed``'s tensor.
 
+``clip=(lo_pct, hi_pct)`` (``--clip LO[,HI]``) clamps the binned image to two of its own order statistics before the
+min-max step (``torch.ops.sprk.ingest_clip``, an exact selection on the device), so that hot pixels and black spots do
+not set the 8-bit range; ``joint bin --clip`` writes the clamped block means, and the closure above holds with the flag
+on both sides.  ``None`` adds no launch and changes no byte.
+
 Coordinates: x runs along nx (columns), y along ny (rows) — the frame of the label tables and of ``*_scores.txt``.
 Bin factor N keeps the centred area: binned pixel (x, y) covers samples ox + N*x .. ox + N*x + N-1 (oy likewise)."""
 import logging
+import math
 import os
 
 import numpy as np
@@ -134,31 +140,70 @@ def read_raw(path, device="cuda"):
     return _reader(device).read(path)
 
 
-def _bin(path, N, device):
+def parse_clip(text):
+    """``--clip LO[,HI]`` -> (lo_pct, hi_pct): the percentages of the pixels clipped at the dark and at the bright end,
+    HI = LO when omitted.  ValueError for anything but two finite numbers >= 0 with LO + HI < 100."""
+    parts = str(text).split(",")
+    try:
+        if not 1 <= len(parts) <= 2:
+            raise ValueError
+        lo = float(parts[0])
+        hi = float(parts[1]) if len(parts) == 2 else lo
+    except ValueError:
+        raise ValueError("clip must be LO or LO,HI in percent, got %r" % (text,)) from None
+    return check_clip((lo, hi))
+
+
+def check_clip(clip):
+    try:
+        lo, hi = (float(v) for v in clip)
+    except (TypeError, ValueError):
+        raise ValueError("clip must be a pair (lo_pct, hi_pct), got %r" % (clip,)) from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo >= 0 and hi >= 0 and lo + hi < 100):
+        raise ValueError("clip percentages must be >= 0 with LO + HI < 100, got %r, %r" % (lo, hi))
+    return lo, hi
+
+
+def clip_ranks(n, clip):
+    """-> (k_lo, k_hi): the ranks (from 0, among the n pixels in ascending order) the image is clamped to:
+    k_lo = floor(LO/100 * (n-1)), k_hi = (n-1) - floor(HI/100 * (n-1)).  (0, 0) -> (0, n-1), the identity."""
+    lo, hi = check_clip(clip)
+    if n < 1:
+        raise ValueError("clip_ranks: an image of %d pixels" % n)
+    return int(math.floor(lo / 100 * (n - 1))), (n - 1) - int(math.floor(hi / 100 * (n - 1)))
+
+
+def _bin(path, N, device, clip=None):
     N = check_bin(N)
+    if clip is not None:
+        clip = check_clip(clip)
     raw, header = read_raw(path, device)
     geometry = binned_geometry(header.ny, header.nx, N)
     binned, rng = torch.ops.sprk.ingest_bin(raw, header.mode, header.ny, header.nx, N)
+    if clip is not None:      # the image clamped to two of its order statistics, which become the range (csrc/ingest.hip)
+        binned, rng = torch.ops.sprk.ingest_clip(binned, rng, *clip_ranks(binned.numel(), clip))
     return binned, rng, geometry
 
 
-def binned(path, bin, device="cuda"):
-    """-> (float32 CUDA tensor [by, bx]: the N x N block means, geometry) — what ``joint bin`` writes."""
-    b, _, geometry = _bin(path, bin, device)
+def binned(path, bin, device="cuda", clip=None):
+    """-> (float32 CUDA tensor [by, bx]: the N x N block means, geometry) — what ``joint bin`` writes.  ``clip``
+    (lo_pct, hi_pct): clamped to the order statistics of ``clip_ranks``; None: as they are."""
+    b, _, geometry = _bin(path, bin, device, clip)
     return b, geometry
 
 
-def binned_uint8(path, bin, device="cuda"):
-    """-> uint8 array [by, bx]: ``micrograph_io.load_image`` of the binned micrograph."""
-    b, rng, _ = _bin(path, bin, device)
+def binned_uint8(path, bin, device="cuda", clip=None):
+    """-> uint8 array [by, bx]: ``micrograph_io.load_image`` of the binned (and, with ``clip``, clamped) micrograph."""
+    b, rng, _ = _bin(path, bin, device, clip)
     u8, _ = torch.ops.sprk.ingest_finish(b, rng, True, False)
     return u8.cpu().numpy()
 
 
-def ingest(path, bin, device="cuda"):
-    """-> (network input float32 CUDA [1, 1, S, S], (by, bx), (by, bx, oy, ox)): the binned micrograph min-max
-    quantised, /255, transposed and reflect-padded, as ``MicrographFeed`` hands it to the network."""
-    b, rng, geometry = _bin(path, bin, device)
+def ingest(path, bin, device="cuda", clip=None):
+    """-> (network input float32 CUDA [1, 1, S, S], (by, bx), (by, bx, oy, ox)): the binned micrograph (with ``clip``:
+    clamped to its two order statistics first) min-max quantised, /255, transposed and reflect-padded, as
+    ``MicrographFeed`` hands it to the network."""
+    b, rng, geometry = _bin(path, bin, device, clip)
     _, net = torch.ops.sprk.ingest_finish(b, rng, False, True)
     return net[None, None], geometry[:2], geometry
 
@@ -169,8 +214,9 @@ class RawMicrographFeed:
     is held in memory) and its tensor comes from ``ingest``.  IMAGE_SHAPE is [1, bx, by] (tensors are transposed), the
     target is all zeros (evaluation has no labels to draw), BIN_GEOMETRY carries (by, bx, oy, ox)."""
 
-    def __init__(self, rows, bin, count=None, device="cuda", rank=0, world=1, gt=None):
+    def __init__(self, rows, bin, count=None, device="cuda", rank=0, world=1, gt=None, clip=None):
         self.bin = check_bin(bin)
+        self.clip = None if clip is None else check_clip(clip)
         self.device = torch.device(device)
         self.gt = gt or {}
         images = {}
@@ -192,7 +238,7 @@ class RawMicrographFeed:
         M = DetectionDataset.Metadata
         for pos, k in self.order:
             path, name = self.items[k]
-            inp, (by, bx), geometry = ingest(path, self.bin, self.device)
+            inp, (by, bx), geometry = ingest(path, self.bin, self.device, self.clip)
             md = {M.INDEXES: torch.tensor([k]), M.NAME: [name], M.IMAGE_SHAPE: torch.tensor([[1, bx, by]]), M.GT: [],
                   M.BIN_GEOMETRY: [geometry]}
             if name in self.gt:
@@ -210,7 +256,7 @@ def unbinned_map(N, ox, oy):
     return to_raw
 
 
-def bin_dataset(dataset, bin, out_dir, labels=None, device="cuda"):
+def bin_dataset(dataset, bin, out_dir, labels=None, device="cuda", clip=None):
     """``joint bin``: every micrograph of the table / directory ``dataset`` binned on the device and written as a
     float32 MRC ``out_dir/{name}.mrc``, plus ``out_dir/images.txt`` (image_name, path) and, with ``labels``,
     ``out_dir/labels.txt`` (coordinates through ``to_binned``, points outside the binned area dropped, other columns
@@ -219,13 +265,15 @@ def bin_dataset(dataset, bin, out_dir, labels=None, device="cuda"):
         "label_rows": {"kept", "outside", "unknown_image"} or None}."""
     from . import coordinates
     bin = check_bin(bin)
+    if clip is not None:
+        clip = check_clip(clip)
     rows = micrograph_io.read_image_table(dataset)
     if not rows:
         raise ValueError("no micrographs found in %s" % dataset)
     os.makedirs(out_dir, exist_ok=True)
     geometry, lines = {}, ["image_name\tpath"]
     for _, name, path in rows:
-        b, geometry[name] = binned(path, bin, device)
+        b, geometry[name] = binned(path, bin, device, clip)
         out = os.path.join(out_dir, name + ".mrc")
         with open(out, "wb") as f:
             micrograph_io.write_mrc(f, b.cpu().numpy())

@@ -628,6 +628,41 @@ _register("ingest_finish", "(Tensor binned, Tensor range, bool want_u8, bool wan
           _ingest_finish_fake)
 
 
+def _clip_check(binned, rng, k_lo, k_hi):
+    if binned.dim() != 2 or binned.dtype != torch.float32 or binned.numel() < 1:
+        raise _lib.SprkError("ingest_clip: binned must be a non-empty 2-D float32 tensor, got %s %s"
+                             % (binned.dtype, tuple(binned.shape)))
+    if rng.dtype != torch.float32 or rng.numel() != 2 or not rng.is_contiguous() or rng.device != binned.device:
+        raise _lib.SprkError("ingest_clip: range must be a contiguous float32 tensor of 2 elements on %s, got %s %s on %s"
+                             % (binned.device, rng.dtype, tuple(rng.shape), rng.device))
+    if not 0 <= k_lo <= k_hi <= binned.numel() - 1:
+        raise _lib.SprkError("ingest_clip: ranks %d, %d of %d elements (0 <= k_lo <= k_hi <= n-1)"
+                             % (k_lo, k_hi, binned.numel()))
+
+
+def _ingest_clip(binned, rng, k_lo, k_hi):
+    """-> (binned clamped to its k_lo-th and k_hi-th smallest elements, float32 [by, bx]; range float32 [2] = the two
+    elements).  Functional: neither argument is written."""
+    _clip_check(binned, rng, k_lo, k_hi)
+    binned = binned.contiguous()
+    by, bx = binned.shape
+    L = _lib.lib()
+    out, rng_out = _f32(binned, (by, bx)), _f32(binned, (2,))
+    ws = _ws(L.sprk_ingest_clip_ws_bytes(by, bx), binned)
+    check(L.sprk_ingest_clip(_p(binned), _p(out), by, bx, int(k_lo), int(k_hi), _p(rng), _p(rng_out), _p(ws), ws.numel(),
+                             _stream(binned)), "sprk_ingest_clip")
+    return out, rng_out
+
+
+def _ingest_clip_fake(binned, rng, k_lo, k_hi):
+    _clip_check(binned, rng, k_lo, k_hi)
+    return binned.new_empty(tuple(binned.shape), dtype=torch.float32), binned.new_empty((2,), dtype=torch.float32)
+
+
+_register("ingest_clip", "(Tensor binned, Tensor range, int k_lo, int k_hi) -> (Tensor, Tensor)", _ingest_clip,
+          _ingest_clip_fake)
+
+
 # ---- particle extraction (extract.py: raw MRC samples + pick coordinates -> normalised particle stack) ------------------------
 EXTRACT_MAX_BOX = 1024                           # sprk_extract_boxes: the int64 sum of squares stays below 2^63 up to here
 EXTRACT_NORMALIZE, EXTRACT_INVERT = 1, 2         # SPRK_EXTRACT_*
