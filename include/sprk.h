@@ -118,6 +118,8 @@ size_t sprk_struct_bytes(int which);
 long sprk_launch_count(void);
 /* number of convolutions (forward or backward-data) that took the Winograd F(2x2,3x3) kernel (diagnostics) */
 long sprk_wino_launch_count(void);
+/* number of masked backward-data calls that took the 1x1 kernel with the mask in its store (diagnostics / tests) */
+long sprk_mask1x1_launch_count(void);
 /* number of convolution launches (forward, backward-data or backward-weight) that ran on the 16-bit-operand
  * kernels (diagnostics / tests) */
 long sprk_conv16_launch_count(void);
@@ -166,6 +168,13 @@ int sprk_head1x1_unrot_fwd(const float *d, const float *w1, const float *b1, con
  * other kernels finish with an in-place pass, so the call is valid for every geometry without upsampled input. */
 int sprk_conv2d_bwd_data_masked(const float *gy, const float *w, float *gin, const sprk_conv_geom *g,
                                 const float *mask_y, int mask_act, void *ws, size_t ws_bytes, void *stream);
+/* 1: sprk_conv2d_bwd_data_masked on g applies the mask inside its kernel (the Winograd kernel, or the 1x1 kernel of
+ * few reduced channels: 1x1, stride 1, no padding, one full-resolution source, fp32, Hin * Win % 4 == 0, Cout <= 96,
+ * a launch of at least 512 workgroups of 128 pixels); 0: the call finishes with the in-place pass.  A caller that may
+ * choose (networks.py) fuses a producer's activation backward into this call only where the answer is 1: behind the
+ * in-place pass the producer's remaining bias sum is one pass more than the unfused pair.  (16-byte aligned tensors
+ * assumed; others take the in-place pass, with the same result.) */
+int sprk_conv2d_bwd_data_mask_fused(const sprk_conv_geom *g);
 /* bit 0 / 1 / 2: the forward / backward-data / backward-weight call of this layer exists for 16-bit activation tensors
  * (SPRK_DT_X16 / SPRK_DT_Y16; g->dtype carries the operand type, ep the forward epilogue or NULL) */
 int sprk_conv2d_storage16(const sprk_conv_geom *g, const sprk_conv_epilogue *ep);

@@ -56,6 +56,7 @@ _SIGS = {
     "sprk_struct_bytes": (c_sz, [c_i]),
     "sprk_launch_count": (ctypes.c_long, []),
     "sprk_wino_launch_count": (ctypes.c_long, []),
+    "sprk_mask1x1_launch_count": (ctypes.c_long, []),
     "sprk_conv16_launch_count": (ctypes.c_long, []),
     "sprk_wgrad16_launch_count": (ctypes.c_long, []),
     "sprk_conv2d_fwd_ws_bytes": (c_sz, [ctypes.POINTER(ConvGeom)]),
@@ -86,6 +87,7 @@ _SIGS = {
     "sprk_unrot4_shift_concat_bwd": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_vp]),
     "sprk_unrot_act_bwd_eligible": (c_i, [c_i, c_i, c_i, c_i]),
     "sprk_conv2d_fwd_unrot_eligible": (c_i, [ctypes.POINTER(ConvGeom), ctypes.POINTER(ConvEpilogue)]),
+    "sprk_conv2d_bwd_data_mask_fused": (c_i, [ctypes.POINTER(ConvGeom)]),
     "sprk_conv2d_fwd_unrot": (c_i, [c_f, c_f, c_f, c_f, ctypes.POINTER(ConvGeom), ctypes.POINTER(ConvEpilogue), c_vp, c_sz, c_vp]),
     "sprk_unrot_act_bwd": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_vp, c_sz, ctypes.POINTER(ReduceItem), c_vp]),
     "sprk_bn_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),

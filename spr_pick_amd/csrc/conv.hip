@@ -18,6 +18,7 @@
 // cross-check (SPRK_DT_NAIVE in sprk_conv_geom.dtype).
 #include "common.h"
 #include "conv16.h"
+#include "mask1x1.h"
 #include "wgrad16.h"
 #include "wino.h"
 #include "wprep_dev.h"
@@ -870,6 +871,81 @@ __global__ void conv_bwd_data_direct_kernel(const DirectArgs a) {
     }
 }
 
+// Strided backward-data of a layer whose weights fit LDS (the detector's 7x7 stride-2 stem): the sums of
+// conv_bwd_data_direct_kernel — the same loops in the same order, one chain s += gy * w from 0 per element, so the
+// results are equal bit for bit — with both operands read from LDS instead of global memory.  A workgroup owns a
+// kStemTW x kStemTH tile of input pixels of one image; it stages the weights [Cout][Cin][KH][KW] and the window of gy
+// its pixels can reach ([Cout][wr][wc], zero outside the image: never used) once, then each thread walks the input
+// channels of its pixel.
+constexpr int kStemTW = 32, kStemTH = 8;
+constexpr size_t kStemLdsLimit = 64 * 1024;   // no LDS opt-in
+
+struct StemPlan {
+    int wr, wc, tilesX, tilesY;
+    size_t ldsBytes;
+};
+
+// false: the weights and a tile's gradient window do not fit LDS (conv_bwd_data_direct_kernel runs)
+bool plan_stem_bwd(const sprk_conv_geom *g, StemPlan *p) {
+    if (g->stride < 1 || g->dil < 1) return false;
+    const long Cin = g->C1 + g->C2;
+    p->wr = (kStemTH - 1 + (g->KH - 1) * g->dil) / g->stride + 1;
+    p->wc = (kStemTW - 1 + (g->KW - 1) * g->dil) / g->stride + 1;
+    p->tilesX = sprk::cdiv(g->Win, kStemTW);
+    p->tilesY = sprk::cdiv(g->Hin, kStemTH);
+    const long floats = (long)g->Cout * Cin * g->KH * g->KW + (long)g->Cout * p->wr * p->wc;
+    p->ldsBytes = (size_t)floats * sizeof(float);
+    return p->ldsBytes <= kStemLdsLimit && (long)g->N * p->tilesX * p->tilesY < (1L << 31);
+}
+
+__global__ __launch_bounds__(kStemTW * kStemTH) void conv_bwd_data_stem_kernel(const DirectArgs a, int wr, int wc,
+                                                                               int tilesX, int tilesY) {
+    extern __shared__ __attribute__((aligned(16))) float stem_lds[];
+    const sprk_conv_geom &g = a.g;
+    const int Cin = g.C1 + g.C2, KHW = g.KH * g.KW;
+    const int nW = g.Cout * Cin * KHW;
+    float *wl = stem_lds, *gl = stem_lds + nW;
+    int bid = blockIdx.x;
+    const int tx = bid % tilesX; bid /= tilesX;
+    const int ty = bid % tilesY;
+    const int n = bid / tilesY;
+    const int iy0 = ty * kStemTH, ix0 = tx * kStemTW;
+    // first output row / column any pixel of the tile reaches: ceil((i0 + pad - (K - 1) * dil) / stride), at least 0
+    const int ylo = iy0 + g.pad_top - (g.KH - 1) * g.dil, xlo = ix0 + g.pad_left - (g.KW - 1) * g.dil;
+    const int oyLo = ylo <= 0 ? 0 : (ylo + g.stride - 1) / g.stride;
+    const int oxLo = xlo <= 0 ? 0 : (xlo + g.stride - 1) / g.stride;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < nW; i += kStemTW * kStemTH) wl[i] = a.w[i];
+    const int win = wr * wc;
+    for (int i = tid; i < g.Cout * win; i += kStemTW * kStemTH) {
+        const int co = i / win, rem = i - co * win;
+        const int r = rem / wc, oy = oyLo + r, ox = oxLo + rem - r * wc;
+        gl[i] = (oy < g.Hout && ox < g.Wout) ? a.gy[(((long)n * g.Cout + co) * g.Hout + oy) * g.Wout + ox] : 0.f;
+    }
+    __syncthreads();
+    const int iy = iy0 + tid / kStemTW, ix = ix0 + tid % kStemTW;
+    if (iy >= g.Hin || ix >= g.Win) return;
+    for (int c = 0; c < Cin; ++c) {
+        float s = 0.f;
+        for (int ky = 0; ky < g.KH; ++ky) {
+            const int ny = iy + g.pad_top - ky * g.dil;
+            if (ny < 0 || ny % g.stride) continue;
+            const int oy = ny / g.stride;
+            if (oy >= g.Hout) continue;
+            for (int kx = 0; kx < g.KW; ++kx) {
+                const int nx = ix + g.pad_left - kx * g.dil;
+                if (nx < 0 || nx % g.stride) continue;
+                const int ox = nx / g.stride;
+                if (ox >= g.Wout) continue;
+                const float *gp = gl + (oy - oyLo) * wc + (ox - oxLo);
+                const float *wp = wl + (c * g.KH + ky) * g.KW + kx;
+                for (int co = 0; co < g.Cout; ++co) s += gp[co * win] * wp[co * Cin * KHW];
+            }
+        }
+        a.y[(((long)n * Cin + c) * g.Hin + iy) * g.Win + ix] = s;
+    }
+}
+
 // one block per (co, c); y here is gw
 __global__ __launch_bounds__(256) void conv_bwd_weight_direct_kernel(const DirectArgs a) {
     const sprk_conv_geom &g = a.g;
@@ -1581,6 +1657,17 @@ static int mask_in_place(float *gin, const float *mask_y, int mask_act, const sp
                         nullptr, 0, s);
 }
 
+// Stage 5's narrow case: may the masked backward-data of layer g, planned as p, run on mask1x1_kernel (mask1x1.hip)
+// instead of conv_mfma_kernel + mask_in_place?  A 1x1 GEMM over few reduced channels whose plan walks its chunks with
+// chunk_mma (MT >= 2; chunk_mma_small of the MT = 1 plans sums in another order).  The one predicate of the dispatcher
+// and of sprk_conv2d_bwd_data_mask_fused.
+static bool mask1x1_takes(const sprk_conv_geom *g, const sprk::Corr &c, const FwdPlan &p) {
+    return g->KH == 1 && g->KW == 1 && g->stride == 1 && g->dil == 1 && g->pad_top == 0 && g->pad_left == 0 && !g->up1 &&
+           g->C2 == 0 && g->Hin == g->Hout && g->Win == g->Wout && c.dt() == SPRK_DT_F32 && !c.x16() && !c.y16() &&
+           ((long)g->Hin * g->Win) % 4 == 0 && (long)g->Hin * g->Win < (1L << 30) && p.MT >= 2 &&
+           sprk::mask1x1_steps(g->Cout, p.CK) > 0;
+}
+
 // The one place where a forward or (bwd) backward-data call meets its kernel; a new convolution kernel is plugged in
 // here ("The convolution dispatcher").  g / ep: the layer as the caller gave it; for backward-data x = gy,
 // x2 = null, y = gin, and mask_y / mask_act the optional mask of sprk_conv2d_bwd_data_masked.  The stages, in order:
@@ -1609,6 +1696,12 @@ static int conv_dispatch(bool bwd, const float *x, const float *x2, const float 
         if (sprk::wprep_describing()) return SPRK_OK;   // no weight transform on this path
         if (bwd) {
             DirectArgs a{nullptr, nullptr, w, x, y, *g, sprk::kNoEpilogue};
+            StemPlan sp;
+            if (!naive_of(g) && plan_stem_bwd(g, &sp)) {   // the same sums from LDS copies of both operands
+                hipLaunchKernelGGL(conv_bwd_data_stem_kernel, dim3(g->N * sp.tilesX * sp.tilesY), dim3(kStemTW * kStemTH),
+                                   sp.ldsBytes, s, a, sp.wr, sp.wc, sp.tilesX, sp.tilesY);
+                return masked(sprk::check_launch("conv_bwd_data_stem"));
+            }
             const long total = (long)g->N * (g->C1 + g->C2) * g->Hin * g->Win;
             hipLaunchKernelGGL(conv_bwd_data_direct_kernel, dim3(sprk::ew_blocks(total)), dim3(256), 0, s, a);
             return masked(sprk::check_launch("conv_bwd_data_direct"));
@@ -1639,6 +1732,13 @@ static int conv_dispatch(bool bwd, const float *x, const float *x2, const float 
     if (int rc = sprk::check_ws(who, ws, ws_bytes, p.wsBytes)) return rc;
     float *wsf = (float *)ws;
     if (int rc = transform_weights(w, wsf, g->Cout, g->C1 + g->C2, g->KH * g->KW, c.taps, p, s)) return rc;
+    if (bwd && mask_y && mask1x1_takes(g, c, p) && aligned16(x) && aligned16(y) && aligned16(mask_y)) {
+        // few reduced channels, 1x1: a streaming kernel of its own with the mask in its store, on the same slabs
+        const sprk::Mask1x1Call m{x, wsf + kZeroFloats, mask_y, y, g->N, g->Cout, g->C1, g->Hin * g->Win,
+                                  p.CK, p.R4, p.rows, p.ldw, p.NT, p.nblkN, mask_act};
+        if (int rc = sprk::mask1x1_run(m, s)) return rc;
+        return sprk::check_launch("mask1x1(bwd_data)");
+    }
     const ConvArgs a = conv_args(c, p, x, x2, wsf, y);
     // (a masked epilogue in this kernel costs 26 VGPRs — 160 -> 186, two workgroups per CU instead of three — for
     // every call, masked or not: measured in round 1 and again in round 3; the mask is applied by an in-place pass)
@@ -1692,6 +1792,17 @@ int sprk_conv2d_bwd_data_masked(const float *gy, const float *w, float *gin, con
                                 const float *mask_y, int mask_act, void *ws, size_t ws_bytes, void *stream) {
     sprk::WprepScope scope(nullptr, g ? g->dtype : 0);
     return scope.verify(conv_dispatch(true, gy, nullptr, w, gin, g, nullptr, mask_y, mask_act, ws, ws_bytes, stream));
+}
+
+// conv_dispatch's stages for a masked backward-data call of g, by their own predicates, in their order
+int sprk_conv2d_bwd_data_mask_fused(const sprk_conv_geom *g) {
+    if (!g || check_geom(g) != SPRK_OK || naive_of(g) || g->stride != 1 || g->up1) return 0;
+    const sprk::Corr c(*g);
+    if (c.dt() != SPRK_DT_F32 && sprk::conv16_eligible(c)) return 0;
+    if (c.dtype & (SPRK_DT_X16 | SPRK_DT_Y16)) return 0;
+    if (sprk::wino_eligible(c)) return 1;
+    FwdPlan p;
+    return (plan_fwd(c, &p) && mask1x1_takes(g, c, p)) ? 1 : 0;
 }
 
 int sprk_conv2d_bwd_data_wprep(const float *w, const sprk_conv_geom *g, void *ws, size_t ws_bytes, sprk_wprep_item *item) {

@@ -12,7 +12,7 @@
 namespace sprk {
 
 static thread_local char t_error[512] = "";
-std::atomic<long> g_launches{0}, g_wino_launches{0};
+std::atomic<long> g_launches{0}, g_wino_launches{0}, g_mask1x1_launches{0};
 
 void set_error(const char *fmt, ...) {
     va_list ap;
@@ -304,6 +304,7 @@ size_t sprk_struct_bytes(int which) {
 }
 long sprk_launch_count(void) { return sprk::g_launches.load(); }
 long sprk_wino_launch_count(void) { return sprk::g_wino_launches.load(); }
+long sprk_mask1x1_launch_count(void) { return sprk::g_mask1x1_launches.load(); }
 long sprk_conv16_launch_count(void) { return sprk::conv16_launches() + sprk::wgrad16_launches(); }
 long sprk_wgrad16_launch_count(void) { return sprk::wgrad16_launches(); }
 

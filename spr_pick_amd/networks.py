@@ -133,6 +133,12 @@ FUSE_ACT_BWD = True     # debug: False = every convolution runs its own activati
 # as separate kernels (debug / A-B).
 FUSE_UNROT_STORE = True   # the last decoder convolution's Winograd kernel stores the un-rotated tensor itself
 FUSE_UNROT_BWD = True     # un-rotation backward + that convolution's activation backward in one kernel
+# Training, fp32: the activation backward of the layers around the 1x1 head runs inside the next layer's backward-data
+# kernel where that kernel has the mask in its store (ops.bwd_data_mask_fused).  One switch per link
+# (debug / A-B): False = the layer's own act_bwd pass.
+FUSE_HEAD_MASK_IN = True    # decode_block_1[2] -> output_block[0] (the U-Nets without a blind spot)
+FUSE_HEAD_MASK_12 = True    # output_block[0] -> output_block[2]
+FUSE_HEAD_MASK_23 = True    # output_block[2] -> output_conv
 
 
 def _kaiming_leaky(mod):
@@ -197,12 +203,32 @@ class _UNetBase(nn.Module):
         fuse = torch.is_grad_enabled() and FUSE_ACT_BWD and conv.act != ACT_NONE
         return self._run_pool(block, conv(x, premasked=fuse), conv.act if fuse else ACT_NONE)
 
-    def _head(self, t):
-        """output_block (two 1x1 convolutions) + output_conv: in inference one fused launch (ops.head1x1)."""
+    @staticmethod
+    def _mask_link(switch, first, second, n, h, w):
+        """second(first(x)), `second` a 1x1 layer of the head on [n, first.out_channels, h, w]: may the activation
+        backward of `first` run inside `second`'s backward-data kernel?  Only where that kernel applies the mask itself:
+        behind the in-place pass the bias sum `first` keeps would be one pass more than the unfused pair."""
+        return (switch and torch.is_grad_enabled() and FUSE_ACT_BWD and first.act != ACT_NONE and first.mfma_dtype == 0
+                and second.mfma_dtype == 0 and second.weight.is_cuda
+                and ops.bwd_data_mask_fused((n, first.out_channels, h, w), second.weight, pad=second._pad()))
+
+    def _head_in_link(self, last, t):
+        """May `last`, the convolution in front of the head (same-size, on t), leave its activation backward to
+        output_block[0]?  (Not under no_grad: ops.head1x1 may then run the head.)"""
+        return self._mask_link(FUSE_HEAD_MASK_IN, last, self.output_block[0], t.shape[0], t.shape[2], t.shape[3])
+
+    def _head(self, t, x_act=ACT_NONE):
+        """output_block (two 1x1 convolutions) + output_conv: in inference one fused launch (ops.head1x1).
+        x_act: t is the output of a layer that was called with premasked (_head_in_link)."""
         c1, c2, c3 = self.output_block[0], self.output_block[2], self.output_conv
         if FUSED_HEAD and ops.head1x1_eligible(t, c1, c2, c3):
             return ops.head1x1(t, c1, c2, c3)
-        return c3(c2(c1(t)))
+        n, _, h, w = t.shape
+        f12 = self._mask_link(FUSE_HEAD_MASK_12, c1, c2, n, h, w)
+        f23 = self._mask_link(FUSE_HEAD_MASK_23, c2, c3, n, h, w)
+        t = c1(t, x_act=x_act, premasked=f12)
+        t = c2(t, x_act=c1.act if f12 else ACT_NONE, premasked=f23)
+        return c3(t, x_act=c2.act if f23 else ACT_NONE)
 
     @property
     def blindspot(self):
@@ -315,7 +341,8 @@ class DualNetwork(_UNetBase):
                     unrot |= ops.UNROT_STORE
                 if FUSE_UNROT_BWD and ops.unrot_train_eligible(t, c.act, c.mfma_dtype):
                     unrot |= ops.UNROT_BWD
-            t = blk[2](t, up_out=up_out, x_act=blk[0].act if fuse_c else ACT_NONE, unrot_out=unrot)
+            head_in = not self._blindspot and not up_out and self._head_in_link(blk[2], t)
+            t = blk[2](t, up_out=up_out, x_act=blk[0].act if fuse_c else ACT_NONE, premasked=head_in, unrot_out=unrot)
         if self._blindspot and not unrot:
             c1, c2, c3 = self.output_block[0], self.output_block[2], self.output_conv
             if FUSED_HEAD and FUSED_UNROT and ops.head1x1_unrot_eligible(t, c1, c2, c3):
@@ -323,7 +350,7 @@ class DualNetwork(_UNetBase):
                 out = ops.head1x1_unrot(t, c1, c2, c3)
                 return (out, None) if self.detect else out
             t = ops.unrot4_shift_concat(t)
-        out = self._head(t)
+        out = self._head(t, blk[2].act if head_in else ACT_NONE)
         if self._blindspot and self.detect:
             return out, None
         return out
@@ -380,8 +407,9 @@ class DualNetworkShallow(_UNetBase):
                                   (self.decode_block_1, x, False)):
             fuse_c = self._fuse_chain(blk[0], blk[2])
             t = blk[0](t, skip=skip, premasked=fuse_c)
-            t = blk[2](t, up_out=up_out, x_act=blk[0].act if fuse_c else ACT_NONE)
-        return self._head(t)
+            head_in = not up_out and self._head_in_link(blk[2], t)
+            t = blk[2](t, up_out=up_out, x_act=blk[0].act if fuse_c else ACT_NONE, premasked=head_in)
+        return self._head(t, blk[2].act if head_in else ACT_NONE)
 
     @staticmethod
     def input_wh_mul():

@@ -447,6 +447,30 @@ def unrot_train_eligible(x, conv_act, dtype=0):
     return bool(_lib.lib().sprk_unrot_act_bwd_eligible(x.shape[0] // 4, 1, x.shape[2], int(conv_act)))
 
 
+_MASK_FUSED = {}
+
+
+def bwd_data_mask_fused(x_shape, w, stride=1, dil=1, pad=(0, 0, 0, 0), dtype=0):
+    """Will the masked backward-data of conv2d(x, w, ...) for an fp32 x of shape ``x_shape`` apply the mask inside its
+    kernel (sprk_conv2d_bwd_data_mask_fused: the Winograd kernel or the 1x1 kernel), rather than finish with the
+    in-place pass?  Asked by networks.py before it promises ``premasked`` / ``x_act`` on a link it may leave unfused.
+    Cached per geometry."""
+    N, C1, H, W = (int(v) for v in x_shape)
+    Cout, Cin, KH, KW = (int(v) for v in w.shape)
+    key = (N, C1, H, W, Cout, Cin, KH, KW, int(stride), int(dil), tuple(int(v) for v in pad), int(dtype) & 0xff)
+    r = _MASK_FUSED.get(key)
+    if r is None:
+        r = False
+        if Cin == C1:
+            pt, pb, pl, pr = key[10]
+            Hout, Wout = conv_out_size(H, KH, stride, dil, pt, pb), conv_out_size(W, KW, stride, dil, pl, pr)
+            if Hout > 0 and Wout > 0:
+                g = ConvGeom(N, C1, 0, H, W, 0, Cout, Hout, Wout, KH, KW, int(stride), int(dil), pt, pl, int(dtype) & 0xff)
+                r = bool(_lib.lib().sprk_conv2d_bwd_data_mask_fused(ctypes.byref(g)))
+        _MASK_FUSED[key] = r
+    return r
+
+
 # ---- U-Net plumbing -----------------------------------------------------------------------------
 class _ShiftMaxPoolFn(torch.autograd.Function):
     @staticmethod
