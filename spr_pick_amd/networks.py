@@ -141,6 +141,30 @@ FUSE_HEAD_MASK_12 = True    # output_block[0] -> output_block[2]
 FUSE_HEAD_MASK_23 = True    # output_block[2] -> output_conv
 
 
+def _act_link(producer, consumer, like=None, switch=True):
+    """consumer(producer(x)), `consumer` the only user of the intermediate tensor: may the activation backward of
+    `producer` run inside `consumer`'s backward (ops.conv2d: premasked / x_act)?  -> the activation code to hand to the
+    consumer as ``x_act`` (the producer gets ``premasked=bool(link)``), or ACT_NONE.  The ONE place where a fused link
+    is decided: every conv -> conv and conv -> pool link of the U-Nets qualifies structurally, and the consumer decides.
+      pool:             always (the pooling backward applies the mask);
+      3x3 convolution:  fp32 operands (its backward-data kernel applies the mask in its epilogue);
+      1x1 convolution of the head, on [like.shape[0], producer.out_channels, *like.shape[2:]], behind `switch` (one of
+                        FUSE_HEAD_MASK_*): both layers fp32 and only where that kernel applies the mask itself
+                        (ops.bwd_data_mask_fused): behind the in-place pass the bias sum the producer keeps would be one
+                        pass more than the unfused pair."""
+    if not (torch.is_grad_enabled() and FUSE_ACT_BWD and producer.act != ACT_NONE):
+        return ACT_NONE
+    if not isinstance(consumer, Conv2d):
+        ok = True
+    elif consumer.kernel_size[0] == 3:
+        ok = consumer.mfma_dtype == 0
+    else:
+        ok = (switch and producer.mfma_dtype == 0 and consumer.mfma_dtype == 0 and consumer.weight.is_cuda
+              and ops.bwd_data_mask_fused((like.shape[0], producer.out_channels, like.shape[2], like.shape[3]),
+                                          consumer.weight, pad=consumer._pad()))
+    return producer.act if ok else ACT_NONE
+
+
 def _kaiming_leaky(mod):
     for m in mod.modules():
         if isinstance(m, Conv2d):
@@ -181,54 +205,69 @@ class _UNetBase(nn.Module):
         p = block[-1]
         return (p[1] if isinstance(p, nn.Sequential) else p)(t, x_act)
 
-    # Activation backward fused into the neighbours (ops.conv2d: premasked / x_act).  Every conv -> conv and conv -> pool
-    # link of the U-Nets qualifies (the intermediate tensor has exactly one consumer); the convolution side is taken
-    # where the consumer's backward-data kernel applies the mask in its epilogue.
-    @staticmethod
-    def _fuse_chain(first, second):
-        """second(first(x)): may the LeakyReLU backward of `first` run inside `second`'s backward-data kernel?"""
-        return (torch.is_grad_enabled() and FUSE_ACT_BWD and first.act != ACT_NONE and second.kernel_size[0] == 3
-                and second.mfma_dtype == 0)
-
-    def _chain(self, first, second, x, skip=None, up_out=False):
-        """second(first(x, skip)).  (Callers in the decoders write the two calls out, rebinding their variable, so that
-        the block's input is released before the second convolution allocates its output: three 25.8 GB tensors
-        instead of four at 4096^2.)"""
-        fuse = self._fuse_chain(first, second)
-        t = first(x, skip=skip, premasked=fuse)
-        return second(t, up_out=up_out, x_act=first.act if fuse else ACT_NONE)
-
-    def _conv_pool(self, conv, block, x):
-        """pool(conv(x)): the LeakyReLU backward of `conv` runs inside the pooling backward."""
-        fuse = torch.is_grad_enabled() and FUSE_ACT_BWD and conv.act != ACT_NONE
-        return self._run_pool(block, conv(x, premasked=fuse), conv.act if fuse else ACT_NONE)
-
-    @staticmethod
-    def _mask_link(switch, first, second, n, h, w):
-        """second(first(x)), `second` a 1x1 layer of the head on [n, first.out_channels, h, w]: may the activation
-        backward of `first` run inside `second`'s backward-data kernel?  Only where that kernel applies the mask itself:
-        behind the in-place pass the bias sum `first` keeps would be one pass more than the unfused pair."""
-        return (switch and torch.is_grad_enabled() and FUSE_ACT_BWD and first.act != ACT_NONE and first.mfma_dtype == 0
-                and second.mfma_dtype == 0 and second.weight.is_cuda
-                and ops.bwd_data_mask_fused((n, first.out_channels, h, w), second.weight, pad=second._pad()))
-
-    def _head_in_link(self, last, t):
-        """May `last`, the convolution in front of the head (same-size, on t), leave its activation backward to
-        output_block[0]?  (Not under no_grad: ops.head1x1 may then run the head.)"""
-        return self._mask_link(FUSE_HEAD_MASK_IN, last, self.output_block[0], t.shape[0], t.shape[2], t.shape[3])
-
     def _head(self, t, x_act=ACT_NONE):
         """output_block (two 1x1 convolutions) + output_conv: in inference one fused launch (ops.head1x1).
-        x_act: t is the output of a layer that was called with premasked (_head_in_link)."""
+        x_act: t is the output of a layer that was called with premasked (forward)."""
         c1, c2, c3 = self.output_block[0], self.output_block[2], self.output_conv
         if FUSED_HEAD and ops.head1x1_eligible(t, c1, c2, c3):
             return ops.head1x1(t, c1, c2, c3)
-        n, _, h, w = t.shape
-        f12 = self._mask_link(FUSE_HEAD_MASK_12, c1, c2, n, h, w)
-        f23 = self._mask_link(FUSE_HEAD_MASK_23, c2, c3, n, h, w)
-        t = c1(t, x_act=x_act, premasked=f12)
-        t = c2(t, x_act=c1.act if f12 else ACT_NONE, premasked=f23)
-        return c3(t, x_act=c2.act if f23 else ACT_NONE)
+        l12 = _act_link(c1, c2, t, FUSE_HEAD_MASK_12)
+        l23 = _act_link(c2, c3, t, FUSE_HEAD_MASK_23)
+        t = c1(t, x_act=x_act, premasked=bool(l12))
+        t = c2(t, x_act=l12, premasked=bool(l23))
+        return c3(t, x_act=l23)
+
+    def forward(self, x):
+        """The walk both U-Nets share; a subclass declares at the end of its constructor
+        ``self._levels = (encoder blocks: convolutions, then a pool; the bottom block; ((decoder block, index of its
+        skip: 0 = the input, i = the output of encoder block i), ...))``
+        (a plain tuple, not a module container: no state_dict keys).  Every link whose activation backward may be fused
+        is decided once (_act_link) and the answer handed to both of its ends."""
+        encoders, bottom, decoders = self._levels
+        if self._blindspot:
+            if x.shape[-1] != x.shape[-2]:
+                raise ValueError("blind-spot network needs square inputs (4-rotation stack), got %s" % (tuple(x.shape),))
+            x = ops.rot4_stack(x)
+        skips = [x]
+        for blk in encoders:
+            convs = [m for m in blk if isinstance(m, Conv2d)]
+            t, x_act = skips[-1], ACT_NONE
+            for conv, consumer in zip(convs, convs[1:] + [blk[-1]]):
+                link = _act_link(conv, consumer)
+                t = conv(t, x_act=x_act, premasked=bool(link))
+                x_act = link
+            skips.append(self._run_pool(blk, t, x_act))
+        # every nn.Upsample of the reference is fused into the stores of the conv that feeds it
+        t = bottom[0](skips[-1], up_out=True)
+        for blk, skip in decoders:
+            first, second, up_out = blk[0], blk[2], len(blk) == 5
+            link = _act_link(first, second)
+            # (t is rebound between the two convolutions, so that the block's input is released before the second one
+            # allocates its output: three 25.8 GB tensors instead of four at 4096^2)
+            t = first(t, skip=skips[skip], premasked=bool(link))
+            unrot, head_in = 0, ACT_NONE
+            if not up_out and self._blindspot:
+                # training at P = 64: the last decoder convolution hands on the un-rotated tensor itself and keeps only
+                # that (its backward is one kernel for un-rotation backward + activation backward)
+                if FUSE_UNROT_STORE and ops.unrot_store_eligible(t, second.weight, second.bias, second._pad(), second.act,
+                                                                 second.mfma_dtype):
+                    unrot |= ops.UNROT_STORE
+                if FUSE_UNROT_BWD and ops.unrot_train_eligible(t, second.act, second.mfma_dtype):
+                    unrot |= ops.UNROT_BWD
+            elif not up_out:
+                # ... or feeds the head as it is (not under no_grad: ops.head1x1 may then run the head)
+                head_in = _act_link(second, self.output_block[0], t, FUSE_HEAD_MASK_IN)
+            t = second(t, up_out=up_out, x_act=link, premasked=bool(head_in), unrot_out=unrot)
+        if self._blindspot and not unrot:
+            c1, c2, c3 = self.output_block[0], self.output_block[2], self.output_conv
+            if FUSED_HEAD and FUSED_UNROT and ops.head1x1_unrot_eligible(t, c1, c2, c3):
+                # inference: Shift2d + un-rotation + concat are the input gather of the fused head
+                out = ops.head1x1_unrot(t, c1, c2, c3)
+            else:
+                out = self._head(ops.unrot4_shift_concat(t))
+        else:
+            out = self._head(t, head_in)
+        return (out, None) if self._blindspot and self.detect else out
 
     @property
     def blindspot(self):
@@ -308,52 +347,10 @@ class DualNetwork(_UNetBase):
             self.output_conv_f = self._conv(96, 1, 1, act=ACT_NONE)
         self.output_conv = self._conv(96, out_channels, 1, act=ACT_NONE)
         self.init_weights()
-
-    def forward(self, x):
-        if self._blindspot:
-            if x.shape[-1] != x.shape[-2]:
-                raise ValueError("blind-spot network needs square inputs (4-rotation stack), got %s" % (tuple(x.shape),))
-            x = ops.rot4_stack(x)
-        e1, e2, e3, e4, e5, e6 = (self.encode_block_1, self.encode_block_2, self.encode_block_3, self.encode_block_4,
-                                  self.encode_block_5, self.encode_block_6)
-        fuse = torch.is_grad_enabled() and FUSE_ACT_BWD
-        t = e1[0](x, premasked=fuse and e1[2].mfma_dtype == 0)
-        # encode_block_1 is conv -> conv -> pool
-        t = e1[2](t, x_act=ACT_LEAKY if fuse and e1[2].mfma_dtype == 0 else ACT_NONE, premasked=fuse)
-        pool1 = self._run_pool(e1, t, ACT_LEAKY if fuse else ACT_NONE)
-        pool2 = self._conv_pool(e2[0], e2, pool1)
-        pool3 = self._conv_pool(e3[0], e3, pool2)
-        pool4 = self._conv_pool(e4[0], e4, pool3)
-        pool5 = self._conv_pool(e5[0], e5, pool4)
-        # every nn.Upsample of the reference is fused into the stores of the conv that feeds it
-        t = e6[0](pool5, up_out=True)
-        for blk, skip, up_out in ((self.decode_block_5, pool4, True), (self.decode_block_4, pool3, True),
-                                  (self.decode_block_3, pool2, True), (self.decode_block_2, pool1, True),
-                                  (self.decode_block_1, x, False)):
-            fuse_c = self._fuse_chain(blk[0], blk[2])
-            t = blk[0](t, skip=skip, premasked=fuse_c)
-            # training at P = 64: the last decoder convolution hands on the un-rotated tensor itself and keeps only that
-            # (its backward is one kernel for un-rotation backward + activation backward)
-            unrot = 0
-            if self._blindspot and blk is self.decode_block_1 and (FUSE_UNROT_STORE or FUSE_UNROT_BWD):
-                c = blk[2]
-                if FUSE_UNROT_STORE and ops.unrot_store_eligible(t, c.weight, c.bias, c._pad(), c.act, c.mfma_dtype):
-                    unrot |= ops.UNROT_STORE
-                if FUSE_UNROT_BWD and ops.unrot_train_eligible(t, c.act, c.mfma_dtype):
-                    unrot |= ops.UNROT_BWD
-            head_in = not self._blindspot and not up_out and self._head_in_link(blk[2], t)
-            t = blk[2](t, up_out=up_out, x_act=blk[0].act if fuse_c else ACT_NONE, premasked=head_in, unrot_out=unrot)
-        if self._blindspot and not unrot:
-            c1, c2, c3 = self.output_block[0], self.output_block[2], self.output_conv
-            if FUSED_HEAD and FUSED_UNROT and ops.head1x1_unrot_eligible(t, c1, c2, c3):
-                # inference: Shift2d + un-rotation + concat are the input gather of the fused head
-                out = ops.head1x1_unrot(t, c1, c2, c3)
-                return (out, None) if self.detect else out
-            t = ops.unrot4_shift_concat(t)
-        out = self._head(t, blk[2].act if head_in else ACT_NONE)
-        if self._blindspot and self.detect:
-            return out, None
-        return out
+        self._levels = ((self.encode_block_1, self.encode_block_2, self.encode_block_3, self.encode_block_4,
+                         self.encode_block_5), self.encode_block_6,
+                        ((self.decode_block_5, 4), (self.decode_block_4, 3), (self.decode_block_3, 2),
+                         (self.decode_block_2, 1), (self.decode_block_1, 0)))
 
     @staticmethod
     def input_wh_mul():
@@ -390,26 +387,14 @@ class DualNetworkShallow(_UNetBase):
         self.output_conv = self._conv(96, out_channels, 1, act=ACT_NONE)
         self.output_conv_f = Conv2d(96, 1, 1)
         self.init_weights()
+        self._levels = ((self.encode_block_1, self.encode_block_2, self.encode_block_3), self.encode_block_6,
+                        ((self.decode_block_5, 2), (self.decode_block_2, 1), (self.decode_block_1, 0)))
 
     def forward(self, x):
         if self._blindspot:
             raise NotImplementedError("DualNetworkShallow(blindspot=True) is not on the joint pipeline's path "
                                       "(reference: denoiser_v2.py:129-137 always passes blindspot=False)")
-        e1, e2, e3, e6 = self.encode_block_1, self.encode_block_2, self.encode_block_3, self.encode_block_6
-        fuse = torch.is_grad_enabled() and FUSE_ACT_BWD
-        t = e1[0](x, premasked=fuse and e1[2].mfma_dtype == 0)
-        t = e1[2](t, x_act=ACT_LEAKY if fuse and e1[2].mfma_dtype == 0 else ACT_NONE, premasked=fuse)
-        pool1 = self._run_pool(e1, t, ACT_LEAKY if fuse else ACT_NONE)
-        pool2 = self._conv_pool(e2[0], e2, pool1)
-        pool3 = self._conv_pool(e3[0], e3, pool2)
-        t = e6[0](pool3, up_out=True)
-        for blk, skip, up_out in ((self.decode_block_5, pool2, True), (self.decode_block_2, pool1, True),
-                                  (self.decode_block_1, x, False)):
-            fuse_c = self._fuse_chain(blk[0], blk[2])
-            t = blk[0](t, skip=skip, premasked=fuse_c)
-            head_in = not up_out and self._head_in_link(blk[2], t)
-            t = blk[2](t, up_out=up_out, x_act=blk[0].act if fuse_c else ACT_NONE, premasked=head_in)
-        return self._head(t, blk[2].act if head_in else ACT_NONE)
+        return super().forward(x)
 
     @staticmethod
     def input_wh_mul():

@@ -53,13 +53,13 @@ def _grad_like(w):
 
 
 def _grad_dest(w):
-    """-> (tensor, defer).  defer: the operator may leave the second stage of its sum pending (torch_ops.reduce_pending
+    """-> (_grad_like(w), defer).  defer: the operator may leave the second stage of its sum pending (torch_ops.reduce_pending
     finishes all of them in one launch when the flat-gradient context closes).  Only the FIRST gradient of a parameter
     in a step is deferred: a second consumer makes autograd add the two at once, so what is pending is finished first."""
     if _GRAD_DEST is None:
-        return torch.empty_like(w), False
+        return _grad_like(w), False
     first = not _GRAD_DEST.handed_out(w)
-    t = _GRAD_DEST.dest(w)
+    t = _grad_like(w)
     if not first:
         flush_reductions(w)
     return t, first and _GRAD_DEST.defer
@@ -128,42 +128,25 @@ class WeightPrep:
 _WPREP = None
 
 
-def _prep_fwd(w, g, ep_key, ep):
+def _prep(prefix, stem, w, g, ep_key=(), ep=()):
     """-> (geometry to call with, workspace or None).  Inside a WeightPrep context: the kept workspace of this
-    (weights, geometry, epilogue shape), with SPRK_DT_WPREP set once its transform is part of begin_step()."""
+    (weights, geometry, epilogue shape), with SPRK_DT_WPREP set once its transform is part of begin_step().
+    prefix / stem: "f", "sprk_conv2d_fwd" (ep_key: the epilogue's shape, ep: its reference) or "b", "sprk_conv2d_bwd_data"
+    — the key's first field and the C entry points <stem>_ws_bytes and <stem>_wprep."""
     if _WPREP is None:
         return g, None
-    key = ("f", w.data_ptr(), tuple(geom_list(g)), ep_key)
+    key = (prefix, w.data_ptr(), tuple(geom_list(g))) + ep_key
     ws, bits = _WPREP.lookup(key)
     if ws is not None:
         gp = ConvGeom(*geom_list(g))
         gp.dtype = g.dtype | bits
         return gp, ws
     L = _lib.lib()
-    ws = _ws(L.sprk_conv2d_fwd_ws_bytes(ctypes.byref(g)), w)
+    ws = _ws(getattr(L, stem + "_ws_bytes")(ctypes.byref(g)), w)
     item = _lib.WprepItem()
-    check(L.sprk_conv2d_fwd_wprep(_p(w), ctypes.byref(g), ctypes.byref(ep), _p(ws), ws.numel(), ctypes.byref(item)),
-          "sprk_conv2d_fwd_wprep")
+    check(getattr(L, stem + "_wprep")(_p(w), ctypes.byref(g), *ep, _p(ws), ws.numel(), ctypes.byref(item)), stem + "_wprep")
     _WPREP.record(key, w, ws, item)
     return g, ws          # this first call still runs its own transform, into the kept workspace
-
-
-def _prep_bwd(w, g):
-    if _WPREP is None:
-        return g, None
-    key = ("b", w.data_ptr(), tuple(geom_list(g)))
-    ws, bits = _WPREP.lookup(key)
-    if ws is not None:
-        gp = ConvGeom(*geom_list(g))
-        gp.dtype = g.dtype | bits
-        return gp, ws
-    L = _lib.lib()
-    ws = _ws(L.sprk_conv2d_bwd_data_ws_bytes(ctypes.byref(g)), w)
-    item = _lib.WprepItem()
-    check(L.sprk_conv2d_bwd_data_wprep(_p(w), ctypes.byref(g), _p(ws), ws.numel(), ctypes.byref(item)),
-          "sprk_conv2d_bwd_data_wprep")
-    _WPREP.record(key, w, ws, item)
-    return g, ws
 
 
 def conv_out_size(n, k, stride, dil, pad_lo, pad_hi):
@@ -200,7 +183,7 @@ def conv2d_forward(x, x2, w, g, bias=None, act=ACT_NONE, scale=None, shift=None,
     ws = None
     if _WPREP is not None:
         ep = torch_ops._epilogue(bias, scale, shift, res, int(res_off), int(act), up_out)
-        g, ws = _prep_fwd(w, g, (bool(up_out), res is not None), ep)
+        g, ws = _prep("f", "sprk_conv2d_fwd", w, g, ((bool(up_out), res is not None),), (ctypes.byref(ep),))
     if unrot:
         return _S.conv2d_fwd_unrot(x, x2, w, bias, geom_list(g), int(act), ws)
     return _S.conv2d_fwd(x, x2, w, bias, scale, shift, res, geom_list(g), int(res_off), int(act), 1 if up_out else 0, ws)
@@ -234,11 +217,24 @@ def _with_dtype(g, dtype):
     return q
 
 
+def _storage_cast(cap, t16, *ts):
+    """The storage-type rule of a convolution call: cap — the call has a kernel for 16-bit activation tensors
+    (its storage16_caps bit); t16 — the torch dtype of the operand type (None: fp32 operands); ts — the activation
+    tensors the call reads (None allowed).  -> (fits, is16, tensors): fits — the kernel exists and every tensor is
+    fp32 or t16; the tensors come back in t16 if it fits and one of them is 16-bit (is16; a small fp32 companion is cast
+    up), else in fp32.  All-fp32 tensors are never touched."""
+    fits = bool(cap) and all(t is None or t.dtype in (_F32, t16) for t in ts)
+    is16 = fits and any(t is not None and t.dtype != _F32 for t in ts)
+    want = t16 if is16 else _F32
+    return fits, is16, tuple(t if t is None or t.dtype == want else t.to(want) for t in ts)
+
+
 class _Conv2dFn(torch.autograd.Function):
     """Storage types (round 4): with 16-bit operands (dtype bf16 / fp16) the activation tensors may themselves be 16-bit
     tensors.  A call whose kernel exists for them (storage16_caps) takes 16-bit inputs as they are and — store16 — writes
-    a 16-bit output; any other call converts what it is handed to fp32 first, so every combination of layers works and
-    the fast path is simply the one without conversions.  Gradients have the storage type of the tensor they belong to."""
+    a 16-bit output; any other call converts what it is handed to fp32 first (_storage_cast), so every combination of
+    layers works and the fast path is simply the one without conversions.  Gradients have the storage type of the tensor
+    they belong to."""
 
     @staticmethod
     def forward(ctx, x, x2, w, bias, up1, stride, dil, pad, act, up_out, dtype, x_act=ACT_NONE, premasked=False,
@@ -251,16 +247,8 @@ class _Conv2dFn(torch.autograd.Function):
         g = make_geom(x, x2, w, up1, stride, dil, pad, dtype=dtype)
         c16 = dtype & 0xff
         caps = storage16_caps(g, up_out) if c16 else 0
-        t16 = torch_ops.TORCH_OF[c16] if c16 else None
-        in16 = x.dtype != _F32 or (x2 is not None and x2.dtype != _F32)
-        if in16 and (caps & 1) and all(t is None or t.dtype in (_F32, t16) for t in (x, x2)):
-            # the kernel reads 16-bit tensors: both sources in that type (a small fp32 source — the raw image — is cast)
-            x = x if x.dtype == t16 else x.to(t16)
-            x2 = x2 if x2 is None or x2.dtype == t16 else x2.to(t16)
-        elif in16:
-            x = x.float()
-            x2 = None if x2 is None else x2.float()
-            in16 = False
+        # the kernel reads 16-bit tensors: both sources in that type (a small fp32 source — the raw image — is cast)
+        _, in16, (x, x2) = _storage_cast(caps & 1, torch_ops.TORCH_OF[c16] if c16 else None, x, x2)
         g.dtype |= (_lib.DT_X16 if in16 else 0) | (_lib.DT_Y16 if (store16 and (caps & 1)) else 0)
         if unrot_out:
             # the layer's output leaves as the un-rotated f [B,4*Cout,P,P]; f is also what backward keeps (it holds y at
@@ -285,118 +273,121 @@ class _Conv2dFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, x2, w, y, bias = ctx.saved_tensors
-        g = ctx.geom
-        base = g.dtype & ~_STORAGE                    # operand type + FORCE / NAIVE bits, no storage bits
-        c16 = base & 0xff
-        t16 = torch_ops.TORCH_OF[c16] if c16 else None
-        caps = ctx.caps
         _need_act(gy)
-        # a gradient that is a channel slice of a concat layer's input gradient (dense planes, strided images) is read
-        # in place by act_bwd; everything else wants it dense
-        if not (ctx.act != ACT_NONE or ctx.up_out):
-            gy = gy.contiguous()
-        gx = gx2 = gw = gb = None
-        need_b = ctx.has_bias and ctx.needs_input_grad[3]
-        # gradient w.r.t. the pre-activation output (+ bias gradient)
-        up2 = 1 if ctx.up_out else 0
-        # premasked: the consumer of this layer's output (the next convolution's backward-data, or the pooling backward)
-        # has already multiplied the gradient by act'(y): only the bias sum is left of the activation backward
-        act_here = ACT_NONE if ctx.premasked else ctx.act
-        if ctx.unrot_out:
-            # gy is the gradient of f, y is f
-            defer_b = False
-            if need_b:
-                gb, defer_b = _grad_dest(bias)
-            if ctx.unrot_out & UNROT_BWD:
-                # un-rotation backward + activation backward (+ bias sum) in one kernel
-                gpre = _S.unrot_act_bwd(gy.contiguous(), y, act_here, gb, defer_b)
-            else:
-                # two kernels (debug / A-B): the un-rotation backward of f gives the stack tensor back, but for its
-                # dropped last row, whose gradient is +0 whatever the mask says
-                gd = _S.unrot4_shift_concat_bwd(gy.contiguous())
-                gpre = _S.act_bwd(gd, _S.unrot4_shift_concat_bwd(y), act_here, [g.N, g.Cout, g.Hout, g.Wout], 0, True, gb, defer_b, 0)
-        elif act_here != ACT_NONE or need_b or up2:
-            want_gpre = act_here != ACT_NONE or bool(up2)
-            defer_b = False
-            if need_b:
-                gb, defer_b = _grad_dest(bias)
-            if not want_gpre:
-                gy = gy.contiguous()
-            out = _S.act_bwd(gy, y, act_here, [g.N, g.Cout, g.Hout, g.Wout], up2, want_gpre, gb, defer_b, torch_ops.code(gy))
-            gpre = out if want_gpre else gy
-        else:
-            gpre = gy.contiguous()
-        if ctx.needs_input_grad[2]:
-            gw, defer_w = _grad_dest(w)
-            xs, x2s, gs, gq = x, x2, gpre, _with_dtype(g, base)
-            if any(t is not None and t.dtype != _F32 for t in (xs, x2s, gs)):
-                if (caps & 4) and all(t is None or t.dtype in (_F32, t16) for t in (xs, x2s, gs)):
-                    xs, gs = (t if t.dtype == t16 else t.to(t16) for t in (xs, gs))
-                    x2s = x2s if x2s is None or x2s.dtype == t16 else x2s.to(t16)
-                    gq.dtype = base | _lib.DT_X16
-                else:       # no 16-bit-storage kernel for this layer's backward-weight: fp32 tensors
-                    xs, gs = xs.float(), gs.float()
-                    x2s = None if x2s is None else x2s.float()
-            _S.conv2d_bwd_weight(xs, x2s, gs, geom_list(gq), gw, defer_w)
-        need0 = ctx.needs_input_grad[0]
+        gpre, gb = _conv_bwd_preact(ctx, gy, y, bias)
+        gw = _conv_bwd_weight(ctx, x, x2, gpre, w) if ctx.needs_input_grad[2] else None
         need1 = x2 is not None and ctx.needs_input_grad[1]
-        if need0 or need1:
-            gd, wd = _with_dtype(g, base), w
-            if g.C2 and not need1:
-                # the skip source needs no gradient (the raw image x0 of decode_block_1): only the
-                # first C1 input channels are back-propagated
-                gd = ConvGeom(g.N, g.C1, 0, g.Hin, g.Win, g.up1, g.Cout, g.Hout, g.Wout, g.KH, g.KW, g.stride, g.dil,
-                              g.pad_top, g.pad_left, base)
-                wd = w[:, :g.C1].contiguous()
-            gsrc = gpre
-            if gd.stride > 1 and gd.C1 + gd.C2 >= 16 and not (gd.dtype & _lib.DT_NAIVE):
-                # strided layers (the detector's down-sampling convolutions): the gradient w.r.t. the input is the
-                # stride-1 backward-data of gy with stride - 1 zeros between its samples — the MFMA kernel on a
-                # zero-stuffed copy (tiny tensors) instead of the direct kernel (which stays for the 7x7 stem: one
-                # input channel would leave 15 of 16 MFMA columns empty)
-                st = gd.stride
-                H1, W1 = (gd.Hout - 1) * st + 1, (gd.Wout - 1) * st + 1
-                gsrc = gpre.new_zeros((gd.N, gd.Cout, H1, W1))
-                gsrc[:, :, ::st, ::st] = gpre
-                gd = ConvGeom(gd.N, gd.C1, gd.C2, gd.Hin, gd.Win, gd.up1, gd.Cout, H1, W1, gd.KH, gd.KW, 1, gd.dil,
-                              gd.pad_top, gd.pad_left, gd.dtype)
-            # storage types of this call: the gradient it reads as it is (if a kernel exists for that), the gradient it
-            # writes in the type of the tensor it belongs to
-            want16 = t16 is not None and ctx.in_dtypes[0] == t16
-            if (caps & 2) and gd.stride == 1 and gsrc.dtype in (_F32, t16):
-                gd.dtype = base | (_lib.DT_X16 if gsrc.dtype == t16 else 0) | (_lib.DT_Y16 if want16 else 0)
-            elif gsrc.dtype != _F32:
-                gsrc = gsrc.float()
-            # x_act: x is the output of an activated layer that this convolution alone consumes — its activation
-            # backward is fused into this backward-data call (the saved input is the mask)
-            masked = ctx.x_act != ACT_NONE and gd.C2 == 0 and not gd.up1
-            ws_b = None
-            if wd is w:      # (a sliced weight is a new tensor every step: nothing to keep)
-                gd, ws_b = _prep_bwd(w, gd)
-            mask = None
-            if masked:
-                mt = t16 if (gd.dtype & _lib.DT_Y16) else _F32
-                mask = x if x.dtype == mt else x.to(mt)
-            gin = _S.conv2d_bwd_data(gsrc, wd, geom_list(gd), mask, ctx.x_act if masked else ACT_NONE, ws_b)
-            if ctx.x_act != ACT_NONE and not masked:
-                raise _lib.SprkError("conv2d: x_act needs a single, full-resolution input source")
-            if gd.C2 == 0 and not gd.up1:
-                gx = gin
-            elif not gd.up1:
-                # concat without upsampling on load: the two halves are handed on as views of gin (their consumers —
-                # act_bwd of the producing layers, autograd's accumulation — read strided images in place)
-                gx, gx2 = gin[:, :gd.C1], gin[:, gd.C1:]
-            else:
-                gx, gx2 = _S.concat_up_bwd(gin.float() if gin.dtype != _F32 else gin, gd.C1, gd.C2, gd.up1, list(x.shape),
-                                           list(x2.shape) if gd.C2 else [0])
-                if not gd.C2:
-                    gx2 = None
-            # (a source that arrived in another storage type than the kernel's gets its gradient in ITS type)
-            if gx is not None and gx.dtype != ctx.in_dtypes[0]:
-                gx = gx.to(ctx.in_dtypes[0])
-            if gx2 is not None and ctx.in_dtypes[1] is not None and gx2.dtype != ctx.in_dtypes[1]:
-                gx2 = gx2.to(ctx.in_dtypes[1])
+        gx, gx2 = _conv_bwd_input(ctx, x, x2, w, gpre, need1) if ctx.needs_input_grad[0] or need1 else (None, None)
         return gx, gx2, gw, gb, None, None, None, None, None, None, None, None, None, None, None
+
+
+def _operand_types(g):
+    """-> (the geometry's dtype without its storage bits: operand type + FORCE / NAIVE bits; torch dtype of 16-bit
+    operands, or None)"""
+    base = g.dtype & ~_STORAGE
+    return base, (torch_ops.TORCH_OF[base & 0xff] if base & 0xff else None)
+
+
+def _conv_bwd_preact(ctx, gy, y, bias):
+    """Step 1 of _Conv2dFn.backward -> (gradient w.r.t. the pre-activation output, bias gradient or None)."""
+    g = ctx.geom
+    # a gradient that is a channel slice of a concat layer's input gradient (dense planes, strided images) is read
+    # in place by act_bwd; everything else wants it dense
+    if not (ctx.act != ACT_NONE or ctx.up_out):
+        gy = gy.contiguous()
+    up2 = 1 if ctx.up_out else 0
+    # premasked: the consumer of this layer's output (the next convolution's backward-data, or the pooling backward)
+    # has already multiplied the gradient by act'(y): only the bias sum is left of the activation backward
+    act_here = ACT_NONE if ctx.premasked else ctx.act
+    need_b = ctx.has_bias and ctx.needs_input_grad[3]
+    if not (ctx.unrot_out or act_here != ACT_NONE or need_b or up2):
+        return gy.contiguous(), None
+    gb, defer_b = _grad_dest(bias) if need_b else (None, False)
+    if ctx.unrot_out & UNROT_BWD:
+        # gy is the gradient of f, y is f: un-rotation backward + activation backward (+ bias sum) in one kernel
+        return _S.unrot_act_bwd(gy.contiguous(), y, act_here, gb, defer_b), gb
+    if ctx.unrot_out:
+        # two kernels (debug / A-B): the un-rotation backward of f gives the stack tensor back, but for its
+        # dropped last row, whose gradient is +0 whatever the mask says
+        gd = _S.unrot4_shift_concat_bwd(gy.contiguous())
+        return _S.act_bwd(gd, _S.unrot4_shift_concat_bwd(y), act_here, [g.N, g.Cout, g.Hout, g.Wout], 0, True, gb, defer_b, 0), gb
+    want_gpre = act_here != ACT_NONE or bool(up2)
+    if not want_gpre:
+        gy = gy.contiguous()
+    out = _S.act_bwd(gy, y, act_here, [g.N, g.Cout, g.Hout, g.Wout], up2, want_gpre, gb, defer_b, torch_ops.code(gy))
+    return (out if want_gpre else gy), gb
+
+
+def _conv_bwd_weight(ctx, x, x2, gpre, w):
+    """Step 2 -> weight gradient (16-bit tensors where this layer's backward-weight has a kernel for them)."""
+    base, t16 = _operand_types(ctx.geom)
+    gw, defer_w = _grad_dest(w)
+    _, in16, (xs, x2s, gs) = _storage_cast(ctx.caps & 4, t16, x, x2, gpre)
+    _S.conv2d_bwd_weight(xs, x2s, gs, geom_list(_with_dtype(ctx.geom, base | (_lib.DT_X16 if in16 else 0))), gw, defer_w)
+    return gw
+
+
+def _conv_bwd_input(ctx, x, x2, w, gpre, need1):
+    """Step 3 -> (gx, gx2): backward-data (+ the fused activation backward of the producer of x), then the split of a
+    concatenated / up-sampled input's gradient."""
+    g = ctx.geom
+    base, t16 = _operand_types(g)
+    gd, wd = _with_dtype(g, base), w
+    if g.C2 and not need1:
+        # the skip source needs no gradient (the raw image x0 of decode_block_1): only the
+        # first C1 input channels are back-propagated
+        gd = ConvGeom(g.N, g.C1, 0, g.Hin, g.Win, g.up1, g.Cout, g.Hout, g.Wout, g.KH, g.KW, g.stride, g.dil,
+                      g.pad_top, g.pad_left, base)
+        wd = w[:, :g.C1].contiguous()
+    gsrc = gpre
+    if gd.stride > 1 and gd.C1 + gd.C2 >= 16 and not (gd.dtype & _lib.DT_NAIVE):
+        # strided layers (the detector's down-sampling convolutions): the gradient w.r.t. the input is the
+        # stride-1 backward-data of gy with stride - 1 zeros between its samples — the MFMA kernel on a
+        # zero-stuffed copy (tiny tensors) instead of the direct kernel (which stays for the 7x7 stem: one
+        # input channel would leave 15 of 16 MFMA columns empty)
+        st = gd.stride
+        H1, W1 = (gd.Hout - 1) * st + 1, (gd.Wout - 1) * st + 1
+        gsrc = gpre.new_zeros((gd.N, gd.Cout, H1, W1))
+        gsrc[:, :, ::st, ::st] = gpre
+        gd = ConvGeom(gd.N, gd.C1, gd.C2, gd.Hin, gd.Win, gd.up1, gd.Cout, H1, W1, gd.KH, gd.KW, 1, gd.dil,
+                      gd.pad_top, gd.pad_left, gd.dtype)
+    # storage types of this call: the gradient it reads as it is (if a kernel exists for that; a single tensor: an fp32
+    # gradient is never cast up), the gradient it writes in the type of the tensor it belongs to
+    fits, in16, (gsrc,) = _storage_cast((ctx.caps & 2) and gd.stride == 1, t16, gsrc)
+    if fits:
+        want16 = t16 is not None and ctx.in_dtypes[0] == t16
+        gd.dtype = base | (_lib.DT_X16 if in16 else 0) | (_lib.DT_Y16 if want16 else 0)
+    # x_act: x is the output of an activated layer that this convolution alone consumes — its activation
+    # backward is fused into this backward-data call (the saved input is the mask)
+    masked = ctx.x_act != ACT_NONE and gd.C2 == 0 and not gd.up1
+    ws_b = None
+    if wd is w:      # (a sliced weight is a new tensor every step: nothing to keep)
+        gd, ws_b = _prep("b", "sprk_conv2d_bwd_data", w, gd)
+    mask = None
+    if masked:
+        mt = t16 if (gd.dtype & _lib.DT_Y16) else _F32
+        mask = x if x.dtype == mt else x.to(mt)
+    gin = _S.conv2d_bwd_data(gsrc, wd, geom_list(gd), mask, ctx.x_act if masked else ACT_NONE, ws_b)
+    if ctx.x_act != ACT_NONE and not masked:
+        raise _lib.SprkError("conv2d: x_act needs a single, full-resolution input source")
+    gx2 = None
+    if gd.C2 == 0 and not gd.up1:
+        gx = gin
+    elif not gd.up1:
+        # concat without upsampling on load: the two halves are handed on as views of gin (their consumers —
+        # act_bwd of the producing layers, autograd's accumulation — read strided images in place)
+        gx, gx2 = gin[:, :gd.C1], gin[:, gd.C1:]
+    else:
+        gx, gx2 = _S.concat_up_bwd(gin.float() if gin.dtype != _F32 else gin, gd.C1, gd.C2, gd.up1, list(x.shape),
+                                   list(x2.shape) if gd.C2 else [0])
+        if not gd.C2:
+            gx2 = None
+    # (a source that arrived in another storage type than the kernel's gets its gradient in ITS type)
+    if gx.dtype != ctx.in_dtypes[0]:
+        gx = gx.to(ctx.in_dtypes[0])
+    if gx2 is not None and ctx.in_dtypes[1] is not None and gx2.dtype != ctx.in_dtypes[1]:
+        gx2 = gx2.to(ctx.in_dtypes[1])
+    return gx, gx2
 
 
 def conv2d(x, w, bias=None, x2=None, up1=False, stride=1, dil=1, pad=(0, 0, 0, 0), act=ACT_NONE, up_out=False,
@@ -422,6 +413,7 @@ def conv2d(x, w, bias=None, x2=None, up1=False, stride=1, dil=1, pad=(0, 0, 0, 0
 
 
 UNROT_STORE, UNROT_BWD = 1, 2
+_HAS_BIAS = 0x100000      # eligibility queries plan on the host: "there is a bias" without reading a data pointer
 
 
 def unrot_store_eligible(x, w, bias, pad, act, dtype=0, x2=None):
@@ -432,7 +424,7 @@ def unrot_store_eligible(x, w, bias, pad, act, dtype=0, x2=None):
     if x.dim() != 4 or x.shape[0] % 4 or (x2 is not None and x2.dtype != _F32):
         return False
     g = make_geom(x, x2, w, False, 1, 1, pad, dtype=dtype)
-    ep = torch_ops._epilogue(bias, None, None, None, 0, int(act), False)
+    ep = ConvEpilogue(_HAS_BIAS if bias is not None else None, None, None, None, 0, 0, 0, int(act), 0)
     return bool(_lib.lib().sprk_conv2d_fwd_unrot_eligible(ctypes.byref(g), ctypes.byref(ep)))
 
 
@@ -752,15 +744,23 @@ def ssdn_nll_pme(x, out_stats, noise_std, style=NOISE_GAUSSIAN):
     return _SsdnFn.apply(x, out_stats, noise_std, int(style))
 
 
-def head1x1_eligible(f, c1, c2, c3):
-    """The fused inference head (sprk_head1x1_fwd) covers 384 -> 384 -> 96 -> {1, 2} and 96 -> 96 -> 96 -> {1, 2} with
-    LeakyReLU(0.1), fp32 operands, planes whose pixel count is a multiple of 128."""
+def _head_fusable(t, c1, c2, c3, shapes):
+    """What the two fused inference heads share: no autograd, an fp32 tensor on the GPU, three biased fp32 1x1 layers
+    with LeakyReLU(0.1) after the first two, (input, output) channels of the first layer in ``shapes``, 96 channels after
+    the second, 1 or 2 outputs, planes below 2^25 pixels."""
     K0, N1 = c1.weight.shape[1], c1.weight.shape[0]
-    return (not torch.is_grad_enabled() and f.is_cuda and f.dtype == torch.float32 and (K0, N1) in ((384, 384), (96, 96))
+    return (not torch.is_grad_enabled() and t.is_cuda and t.dtype == torch.float32 and (K0, N1) in shapes
             and tuple(c2.weight.shape[:2]) == (96, N1) and c3.weight.shape[1] == 96 and c3.weight.shape[0] in (1, 2)
             and c1.kernel_size == (1, 1) and c1.act == ACT_LEAKY and c2.act == ACT_LEAKY and c3.act == ACT_NONE
             and all(c.bias is not None and (c.mfma_dtype_nograd & 0xff) == 0 for c in (c1, c2, c3))
-            and (f.shape[2] * f.shape[3]) % 128 == 0 and f.shape[2] * f.shape[3] < (1 << 25) and f.shape[1] == K0)
+            and t.shape[2] * t.shape[3] < (1 << 25))
+
+
+def head1x1_eligible(f, c1, c2, c3):
+    """The fused inference head (sprk_head1x1_fwd) covers 384 -> 384 -> 96 -> {1, 2} and 96 -> 96 -> 96 -> {1, 2} with
+    LeakyReLU(0.1), fp32 operands, planes whose pixel count is a multiple of 128."""
+    return (_head_fusable(f, c1, c2, c3, ((384, 384), (96, 96))) and (f.shape[2] * f.shape[3]) % 128 == 0
+            and f.shape[1] == c1.weight.shape[1])
 
 
 def head1x1(f, c1, c2, c3):
@@ -774,12 +774,7 @@ def head1x1_unrot_eligible(d, c1, c2, c3):
     """Blind-spot head straight from the rotated stack d [4B,96,P,P] (no [B,384,P,P] tensor): sprk_head1x1_unrot_fwd."""
     if d.dim() != 4 or d.shape[0] % 4 or d.shape[1] != 96 or d.shape[2] != d.shape[3] or d.shape[2] % 16:
         return False
-    K0, N1 = c1.weight.shape[1], c1.weight.shape[0]
-    return (not torch.is_grad_enabled() and d.is_cuda and d.dtype == torch.float32 and (K0, N1) == (384, 384)
-            and tuple(c2.weight.shape[:2]) == (96, 384) and c3.weight.shape[1] == 96 and c3.weight.shape[0] in (1, 2)
-            and c1.kernel_size == (1, 1) and c1.act == ACT_LEAKY and c2.act == ACT_LEAKY and c3.act == ACT_NONE
-            and all(c.bias is not None and (c.mfma_dtype_nograd & 0xff) == 0 for c in (c1, c2, c3))
-            and d.shape[2] * d.shape[3] < (1 << 25))
+    return _head_fusable(d, c1, c2, c3, ((384, 384),))
 
 
 def head1x1_unrot(d, c1, c2, c3):

@@ -315,20 +315,10 @@ _register("concat_up_bwd", "(Tensor gin, int C1, int C2, int up1, int[] x_shape,
 
 
 # ---- U-Net plumbing ----------------------------------------------------------------------------------------------------
-def _simple(name, schema, cfn, out_shape, args):
-    """Register an operator whose C function takes (inputs..., output, ints..., stream)."""
-    def impl(*a):
-        L = _lib.lib()
-        tensors = [t for t in a if torch.is_tensor(t)]
-        y = _f32(tensors[0], out_shape(*a))
-        check(getattr(L, cfn)(*args(a, y), _stream(tensors[0])), cfn)
-        return y
-    _register(name, schema, impl, lambda *a: [t for t in a if torch.is_tensor(t)][0].new_empty(out_shape(*a)))
-
-
 def _typed(name, schema, cfn, out_shape, out_dtype, args):
-    """Like _simple for the operators whose tensors may be fp32 or 16-bit: out_dtype(*a) -> torch dtype of the output,
-    args(a, y) -> C arguments incl. the io word."""
+    """Register an operator whose C function takes (inputs..., output, ints..., stream): out_shape(*a), out_dtype(*a) ->
+    shape and torch dtype of the output (the operators whose tensors may be fp32 or 16-bit), args(a, y) -> C arguments
+    incl. the io word."""
     def impl(*a):
         L = _lib.lib()
         tensors = [t for t in a if torch.is_tensor(t)]
@@ -336,6 +326,11 @@ def _typed(name, schema, cfn, out_shape, out_dtype, args):
         check(getattr(L, cfn)(*args(a, y), _stream(tensors[0])), cfn)
         return y
     _register(name, schema, impl, lambda *a: [t for t in a if torch.is_tensor(t)][0].new_empty(out_shape(*a), dtype=out_dtype(*a)))
+
+
+def _simple(name, schema, cfn, out_shape, args):
+    """_typed with an fp32 output."""
+    _typed(name, schema, cfn, out_shape, lambda *a: torch.float32, args)
 
 
 _typed("shift_maxpool2_fwd", "(Tensor x, int shift) -> Tensor", "sprk_shift_maxpool2_fwd",
