@@ -109,7 +109,7 @@ typedef struct sprk_conv_epilogue {
  * written against, and may compare sprk_struct_bytes(0 | 1 | 2) with its own sizeof(sprk_conv_geom |
  * sprk_conv_epilogue | sprk_reduce_item). */
 #define SPRK_ABI_VERSION 430   /* 430: sprk_contam_*; sprk_ingest_*, sprk_extract_boxes, sprk_conv2d_fwd_unrot[_eligible] and
-                                * sprk_unrot_act_bwd[_eligible] joined it compatibly (no signature or struct changed:
+                                * sprk_unrot_act_bwd[_eligible], sprk_conv2d_[last_]variant joined it compatibly (no signature or struct changed:
                                 * a binding that needs them finds a library without them by the missing symbol) */
 const char *sprk_last_error(void);
 int sprk_version(void);
@@ -182,6 +182,37 @@ int sprk_conv2d_storage16(const sprk_conv_geom *g, const sprk_conv_epilogue *ep)
 size_t sprk_conv2d_bwd_weight_ws_bytes(const sprk_conv_geom *g);
 int sprk_conv2d_bwd_weight(const float *x, const float *x2, const float *gy, float *gw,
                            const sprk_conv_geom *g, void *ws, size_t ws_bytes, void *stream);
+/* ---- which kernel variant a convolution call takes (host only, no launch; tests and diagnostics) -------------------
+ * The fp32 MFMA kernels are template families (conv_mfma_kernel<MT, NT, RB, XTAB>: 60 instantiations;
+ * conv_wgrad_mfma_kernel<IT, NT, WJ, MODE>: 85) that also branch at run time on flags derived from the geometry and from
+ * the tensors' alignment.  sprk_conv2d_variant runs the dispatcher's own routing (the function the dispatcher itself
+ * acts on) for call `which` — 0 forward, 1 backward-data (unmasked), 2 backward-weight — of layer g and returns it as
+ * SPRK_VARIANT_INTS integers.  x, x2: the layer's inputs (backward-data: x is gin, the tensor written); y_or_gy: y for
+ * the forward call, gy otherwise.  The pointers are tested for 16-byte alignment only, never dereferenced.  Without a
+ * device the plans are those of a 256-CU device (the MI355X).
+ *   out[0] = stage, SPRK_STAGE_*; the other fields are filled by the stages that plan (MASK1X1, MFMA), else 0
+ *   which 0 / 1: [1] MT [2] NT [3] RB [4] XTAB [5] chunk_mma_small [6] K stages (1 | 2) [7] ragged last K-chunk
+ *                [8] latency-bound re-chunking of K [9] vec1 [10] vec2 [11] vec4 [12] colOff != 0 [13] up1 [14] C2 > 0
+ *                [15] taps (1: backward-data weight layout) [16] channels per K-chunk [17] K-chunks
+ *                [18] workgroups of the launch (what the planner's 512-workgroup thresholds compare)
+ *   which 2:     [1] IT [2] NT [3] WJ [4] MODE [5] xrow [6] xtab [7] g4 [8] vec1 [9] vec2 [10] nChunks > 1
+ *                [11] groups > 1 [12] up1 [13] C2 > 0 [14] 64-pixel tiles one workgroup sums over
+ * sprk_conv2d_last_variant returns the same record for the calling THREAD's last call of that kind as it was routed
+ * (stage SPRK_STAGE_NONE before the first one; prepared-weight describe calls are not recorded).  Backward calls made
+ * by an autograd engine run on its threads. */
+#define SPRK_VARIANT_INTS 24
+#define SPRK_STAGE_NONE (-2)     /* sprk_conv2d_last_variant: no call yet */
+#define SPRK_STAGE_REFUSED (-1)  /* the call is refused: storage guard, no plan fits LDS, unaligned 1x1 row staging */
+#define SPRK_STAGE_DIRECT 0
+#define SPRK_STAGE_STEM 1
+#define SPRK_STAGE_16BIT 2
+#define SPRK_STAGE_WINOGRAD 3
+#define SPRK_STAGE_MASK1X1 4
+#define SPRK_STAGE_MFMA 5
+int sprk_conv2d_variant(int which, const sprk_conv_geom *g, const sprk_conv_epilogue *ep, const void *x, const void *x2,
+                        const void *y_or_gy, int32_t *out);
+int sprk_conv2d_last_variant(int which, int32_t *out);
+
 /* ---- prepared weights: one launch per training step instead of one per convolution call ------------------------
  * Every convolution call re-lays its weights out in its workspace before the main kernel (k-chunked slabs, Winograd
  * G g G^T, 16-bit slabs): ~100 small launches per training step, 2-3 % of it.  A caller whose weights change once per

@@ -88,6 +88,9 @@ _SIGS = {
     "sprk_unrot_act_bwd_eligible": (c_i, [c_i, c_i, c_i, c_i]),
     "sprk_conv2d_fwd_unrot_eligible": (c_i, [ctypes.POINTER(ConvGeom), ctypes.POINTER(ConvEpilogue)]),
     "sprk_conv2d_bwd_data_mask_fused": (c_i, [ctypes.POINTER(ConvGeom)]),
+    "sprk_conv2d_variant": (c_i, [c_i, ctypes.POINTER(ConvGeom), ctypes.POINTER(ConvEpilogue), c_vp, c_vp, c_vp,
+                                  ctypes.POINTER(ctypes.c_int32)]),
+    "sprk_conv2d_last_variant": (c_i, [c_i, ctypes.POINTER(ctypes.c_int32)]),
     "sprk_conv2d_fwd_unrot": (c_i, [c_f, c_f, c_f, c_f, ctypes.POINTER(ConvGeom), ctypes.POINTER(ConvEpilogue), c_vp, c_sz, c_vp]),
     "sprk_unrot_act_bwd": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_vp, c_sz, ctypes.POINTER(ReduceItem), c_vp]),
     "sprk_bn_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),

@@ -1175,8 +1175,35 @@ struct FwdPlan {
     int CK, R4, rows;
     int inRows, inCols, pitch, cplane, colOff, ldw, NI;
     int xtab, nG1, nG2;   // table-driven input staging (conv_mfma_kernel): groups per plane, source 1 / 2
+    int latency;          // the latency-bound branch below re-chunked K (fewer, longer chunks than the throughput rule)
+    long blocks;
     size_t ldsBytes, wsBytes;
 };
+
+// The stage of conv_dispatch / wgrad_dispatch that takes a call (sprk.h: SPRK_STAGE_*), and everything the MFMA
+// launchers and the kernels' run-time branches are chosen by.  One function per family fills it (fwd_route /
+// wg_route): the dispatchers, the launchers, the argument blocks and sprk_conv2d_variant all read it and decide
+// nothing themselves.
+struct FwdVariant {
+    int stage;
+    int MT, NT, RB, XTAB;            // conv_mfma_kernel<MT, NT, RB, XTAB>
+    int small;                       // chunk_mma_small (MT == 1 and NT <= 3) instead of chunk_mma
+    int stages, ragged_k, latency;   // K stages in LDS (1: all of K in one chunk), a shorter last chunk, FwdPlan::latency
+    int vec1, vec2, vec4;            // 16-byte DMA of source 1 / 2, 16-byte stores
+    int colOff, up1, c2, taps;       // colOff != 0, source 1 up-sampled on load, a second source, Corr::taps
+    int CK, nChunks;                 // channels per K-chunk, K-chunks
+    int blocks;                      // workgroups of the launch (FwdPlan::blocks: what plan_fwd's thresholds compare)
+};
+struct WgVariant {
+    int stage;
+    int IT, NT, WJ, MODE;            // conv_wgrad_mfma_kernel<IT, NT, WJ, MODE>, MODE as the tensors allow it
+    int xrow, xtab, g4, vec1, vec2;
+    int chunks, groups;              // nChunks > 1, groups > 1
+    int up1, c2;
+    int tiles;                       // 64-pixel tiles one workgroup sums over (WgPlan::tilesPerGroup)
+};
+thread_local FwdVariant t_last_fwd[2] = {{SPRK_STAGE_NONE}, {SPRK_STAGE_NONE}};   // [0] forward, [1] backward-data
+thread_local WgVariant t_last_wg = {SPRK_STAGE_NONE};
 
 int pad_to_residue(int raw, int residue) {  // smallest v >= raw with v % 32 == residue
     return raw + ((residue - raw % 32) + 32) % 32;
@@ -1229,6 +1256,7 @@ bool plan_fwd(const sprk::Corr &c, FwdPlan *p) {
         return (long)p->imgGroups * p->tilesX * p->tilesY * p->nblkN;
     };
     long blocks = geometry(MT, NT);
+    p->latency = 0;
     while (blocks < 512 && MT > 1) {
         MT >>= 1;
         blocks = geometry(MT, NT);
@@ -1272,12 +1300,14 @@ bool plan_fwd(const sprk::Corr &c, FwdPlan *p) {
             if (ck <= CK) break;
             if (lds(ck) <= room) {
                 CK = ck;
+                p->latency = 1;
                 break;
             }
         }
     }
     if (lds(CK) > kLdsLimit) return false;
     p->CK = CK;
+    p->blocks = blocks;
     p->R4 = sprk::roundup(CK * KHW, rowUnit);
     p->rows = sprk::cdiv(Ck, CK) * p->R4;
     p->ldsBytes = lds(CK);
@@ -1286,37 +1316,34 @@ bool plan_fwd(const sprk::Corr &c, FwdPlan *p) {
 }
 
 template <int MT, int NT, int RB>
-int launch_fwd_one(const ConvArgs &a, const FwdPlan &p, dim3 grid, hipStream_t s) {
+int launch_fwd_one(const ConvArgs &a, const FwdPlan &p, const FwdVariant &v, dim3 grid, hipStream_t s) {
     auto go = [&](auto kernel) {
         if (int rc = sprk::lds_optin(kernel, p.ldsBytes, "conv_mfma")) return rc;
         hipLaunchKernelGGL(kernel, grid, dim3(kBlock), p.ldsBytes, s, a);
         return (int)SPRK_OK;
     };
-    return a.xtab ? go(conv_mfma_kernel<MT, NT, RB, true>) : go(conv_mfma_kernel<MT, NT, RB, false>);
+    return v.XTAB ? go(conv_mfma_kernel<MT, NT, RB, true>) : go(conv_mfma_kernel<MT, NT, RB, false>);
 }
 
 template <int MT, int RB>
-int launch_fwd_nt(const ConvArgs &a, const FwdPlan &p, dim3 grid, hipStream_t s) {
-    switch (p.NT) {
-        case 1: return launch_fwd_one<MT, 1, RB>(a, p, grid, s);
-        case 2: return launch_fwd_one<MT, 2, RB>(a, p, grid, s);
-        case 3: return launch_fwd_one<MT, 3, RB>(a, p, grid, s);
-        case 4: return launch_fwd_one<MT, 4, RB>(a, p, grid, s);
-        default: return launch_fwd_one<MT, 6, RB>(a, p, grid, s);
+int launch_fwd_nt(const ConvArgs &a, const FwdPlan &p, const FwdVariant &v, dim3 grid, hipStream_t s) {
+    switch (v.NT) {
+        case 1: return launch_fwd_one<MT, 1, RB>(a, p, v, grid, s);
+        case 2: return launch_fwd_one<MT, 2, RB>(a, p, v, grid, s);
+        case 3: return launch_fwd_one<MT, 3, RB>(a, p, v, grid, s);
+        case 4: return launch_fwd_one<MT, 4, RB>(a, p, v, grid, s);
+        default: return launch_fwd_one<MT, 6, RB>(a, p, v, grid, s);
     }
 }
 
-int launch_fwd(const ConvArgs &a, const FwdPlan &p, hipStream_t s) {
+int launch_fwd(const ConvArgs &a, const FwdPlan &p, const FwdVariant &v, hipStream_t s) {
     dim3 grid(p.imgGroups * p.tilesX * p.tilesY, p.nblkN);
-    // pixel tiles of a wave that lie in one tile row are 16 floats apart in LDS (stride 1): one address
-    // base per row instead of one per tile
-    const int rows = (a.stride == 1) ? std::max(1, (p.MT * 16) >> p.lgTC) : p.MT;
-    switch (p.MT) {
-        case 1: return launch_fwd_nt<1, 1>(a, p, grid, s);
-        case 2: return rows == 1 ? launch_fwd_nt<2, 1>(a, p, grid, s) : launch_fwd_nt<2, 2>(a, p, grid, s);
+    switch (v.MT) {
+        case 1: return launch_fwd_nt<1, 1>(a, p, v, grid, s);
+        case 2: return v.RB == 1 ? launch_fwd_nt<2, 1>(a, p, v, grid, s) : launch_fwd_nt<2, 2>(a, p, v, grid, s);
         default:
-            return rows == 1 ? launch_fwd_nt<4, 1>(a, p, grid, s)
-                             : rows == 2 ? launch_fwd_nt<4, 2>(a, p, grid, s) : launch_fwd_nt<4, 4>(a, p, grid, s);
+            return v.RB == 1 ? launch_fwd_nt<4, 1>(a, p, v, grid, s)
+                             : v.RB == 2 ? launch_fwd_nt<4, 2>(a, p, v, grid, s) : launch_fwd_nt<4, 4>(a, p, v, grid, s);
     }
 }
 
@@ -1325,9 +1352,49 @@ bool aligned16(const void *p) {
     return !novec && (((uintptr_t)p) & 15) == 0;
 }
 
-// conv_mfma_kernel's argument block for correlation c under plan p; wsf: the call's workspace (zero block, then the
-// transformed weights)
-ConvArgs conv_args(const sprk::Corr &c, const FwdPlan &p, const float *x, const float *x2, float *wsf, float *y) {
+// The variant of conv_mfma_kernel that correlation c takes under plan p with these tensors (only their alignment is
+// looked at); `stage` is left to fwd_route.
+FwdVariant fwd_variant(const sprk::Corr &c, const FwdPlan &p, const void *x, const void *x2, const void *y) {
+    FwdVariant v{};
+    v.MT = p.MT;
+    v.NT = p.NT;
+    // pixel tiles of a wave that lie in one tile row are 16 floats apart in LDS (stride 1): one address
+    // base per row instead of one per tile
+    const int rows = (c.stride == 1) ? std::max(1, (p.MT * 16) >> p.lgTC) : p.MT;
+    v.RB = p.MT == 1 ? 1 : p.MT == 2 ? (rows == 1 ? 1 : 2) : (rows == 1 ? 1 : rows == 2 ? 2 : 4);
+    v.small = (p.MT == 1 && p.NT <= 3) ? 1 : 0;
+    const int Ck = c.C1 + c.C2;
+    v.CK = p.CK;
+    v.nChunks = sprk::cdiv(Ck, p.CK);
+    v.blocks = (int)std::min<long>(p.blocks, 1L << 30);
+    v.stages = p.CK >= Ck ? 1 : 2;
+    v.ragged_k = (Ck % p.CK) ? 1 : 0;
+    v.latency = p.latency;
+    v.colOff = p.colOff != 0;
+    v.up1 = c.up1 ? 1 : 0;
+    v.c2 = c.C2 > 0;
+    v.taps = c.taps;
+    v.vec4 = ((c.Wout % 4 == 0) && (p.lgTC >= 2) && (((uintptr_t)y & 15) == 0)) ? 1 : 0;
+    // 16-byte DMA: tile origins on 4-column boundaries, rows 16-byte aligned, source at full resolution
+    const bool geo = ((1 << p.lgTC) * c.stride) % 4 == 0 && (c.Win % 4) == 0;
+    v.vec1 = (geo && !c.up1 && aligned16(x)) ? 1 : 0;
+    v.vec2 = (geo && x2 && aligned16(x2)) ? 1 : 0;
+    // the tables hold byte offsets (image within the tile's group + in-plane part) below 2^31 and were sized
+    // for the expected DMA widths; a chunk's channel offset (soffset) stays below 2^32 bytes
+    const long H1 = c.up1 ? c.Hin / 2 : c.Hin, W1 = c.up1 ? c.Win / 2 : c.Win;
+    const long NIm1 = p.NI - 1;
+    const bool small1 = (NIm1 * c.C1 + 1) * H1 * W1 < (1L << 29) && (long)p.CK * H1 * W1 < (1L << 29);
+    const bool small2 = (NIm1 * c.C2 + 1) * c.Hin * c.Win < (1L << 29) && (long)p.CK * c.Hin * c.Win < (1L << 29);
+    static const int tabmode = sprk::knob_env("SPRK_XTAB", 2);   // 0 = pointer-arithmetic staging, 1 = not for 1x1
+    const bool want = tabmode == 2 || (tabmode == 1 && c.KH * c.KW > 1);
+    v.XTAB = (p.xtab && want && small1 && small2 && (c.up1 || v.vec1) && (c.C2 == 0 || v.vec2)) ? 1 : 0;
+    return v;
+}
+
+// conv_mfma_kernel's argument block for correlation c under plan p and variant v; wsf: the call's workspace (zero
+// block, then the transformed weights)
+ConvArgs conv_args(const sprk::Corr &c, const FwdPlan &p, const FwdVariant &v, const float *x, const float *x2, float *wsf,
+                   float *y) {
     ConvArgs a{};
     a.x = x; a.x2 = x2; a.zeros = wsf; a.wT = wsf + kZeroFloats;
     a.bias = c.ep.bias; a.scale = c.ep.scale; a.shift = c.ep.shift; a.res = c.ep.res;
@@ -1340,7 +1407,7 @@ ConvArgs conv_args(const sprk::Corr &c, const FwdPlan &p, const float *x, const 
     a.act = c.ep.act;
     a.resH = c.ep.res_h; a.resW = c.ep.res_w; a.resOff = c.ep.res_off;
     a.up2 = c.ep.up2;
-    a.vec4 = (c.Wout % 4 == 0) && (p.lgTC >= 2) && (((uintptr_t)y & 15) == 0);
+    a.vec4 = v.vec4;
     a.lgTC = p.lgTC;
     a.lgTR = p.lgTR;
     a.tilesX = p.tilesX;
@@ -1356,20 +1423,11 @@ ConvArgs conv_args(const sprk::Corr &c, const FwdPlan &p, const float *x, const 
     a.ldw = p.ldw;
     a.invImg = 1.0f / (float)(p.inRows * p.pitch);
     a.invPitch = 1.0f / (float)p.pitch;
-    // 16-byte DMA: tile origins on 4-column boundaries, rows 16-byte aligned, source at full resolution
-    const bool geo = ((1 << p.lgTC) * a.stride) % 4 == 0 && (a.Win % 4) == 0;
-    a.vec1 = (geo && !a.up1 && aligned16(a.x)) ? 1 : 0;
-    a.vec2 = (geo && a.x2 && aligned16(a.x2)) ? 1 : 0;
+    a.vec1 = v.vec1;
+    a.vec2 = v.vec2;
     a.deal = 1;
     a.xcdRemap = 1;
-    // the tables hold byte offsets (image within the tile's group + in-plane part) below 2^31 and were sized
-    // for the expected DMA widths; a chunk's channel offset (soffset) stays below 2^32 bytes
-    const long NIm1 = p.NI - 1;
-    const bool small1 = (NIm1 * a.C1 + 1) * a.H1 * a.W1 < (1L << 29) && (long)a.CK * a.H1 * a.W1 < (1L << 29);
-    const bool small2 = (NIm1 * a.C2 + 1) * a.Hin * a.Win < (1L << 29) && (long)a.CK * a.Hin * a.Win < (1L << 29);
-    static const int tabmode = sprk::knob_env("SPRK_XTAB", 2);   // 0 = pointer-arithmetic staging, 1 = not for 1x1
-    const bool want = tabmode == 2 || (tabmode == 1 && a.KH * a.KW > 1);
-    a.xtab = (p.xtab && want && small1 && small2 && (a.up1 || a.vec1) && (a.C2 == 0 || a.vec2)) ? 1 : 0;
+    a.xtab = v.XTAB;
     a.nG1 = p.nG1;
     a.nG2 = p.nG2;
     return a;
@@ -1492,15 +1550,15 @@ bool plan_wgrad(const sprk_conv_geom *g, WgPlan *p) {
 
 template <int IT, int NT, int MODE>
 int launch_wg_one(const WgArgs &a, const WgPlan &p, dim3 grid, hipStream_t s) {
-    constexpr int WJ = (NT % 2 == 0) ? 2 : 1;   // two waves per SIMD whenever the cout tiles split evenly
+    constexpr int WJ = (NT % 2 == 0) ? 2 : 1;   // two waves per SIMD whenever the cout tiles split evenly (wg_variant: WJ)
     if (int rc = sprk::lds_optin(conv_wgrad_mfma_kernel<IT, NT, WJ, MODE>, p.ldsBytes, "conv_wgrad_mfma")) return rc;
     hipLaunchKernelGGL((conv_wgrad_mfma_kernel<IT, NT, WJ, MODE>), grid, dim3(256 * WJ), p.ldsBytes, s, a);
     return SPRK_OK;
 }
 
 template <int IT, int MODE>
-int launch_wg_nt(const WgArgs &a, const WgPlan &p, dim3 grid, hipStream_t s) {
-    switch (p.NT) {
+int launch_wg_nt(const WgArgs &a, const WgPlan &p, const WgVariant &v, dim3 grid, hipStream_t s) {
+    switch (v.NT) {
         case 1: return launch_wg_one<IT, 1, MODE>(a, p, grid, s);
         case 2: return launch_wg_one<IT, 2, MODE>(a, p, grid, s);
         case 3: return launch_wg_one<IT, 3, MODE>(a, p, grid, s);
@@ -1510,35 +1568,76 @@ int launch_wg_nt(const WgArgs &a, const WgPlan &p, dim3 grid, hipStream_t s) {
 }
 
 template <int MODE>
-int launch_wg(const WgArgs &a, const WgPlan &p, dim3 grid, hipStream_t s) {
-    switch (p.IT) {
-        case 1: return launch_wg_nt<1, MODE>(a, p, grid, s);
-        case 2: return launch_wg_nt<2, MODE>(a, p, grid, s);
-        case 3: return launch_wg_nt<3, MODE>(a, p, grid, s);
+int launch_wg_it(const WgArgs &a, const WgPlan &p, const WgVariant &v, dim3 grid, hipStream_t s) {
+    switch (v.IT) {
+        case 1: return launch_wg_nt<1, MODE>(a, p, v, grid, s);
+        case 2: return launch_wg_nt<2, MODE>(a, p, v, grid, s);
+        case 3: return launch_wg_nt<3, MODE>(a, p, v, grid, s);
     }
     if constexpr (MODE != 1) {   // the row-staged 1x1 form never needs more than 192 channels = 3 k-tiles per wave
-        switch (p.IT) {
-            case 4: return launch_wg_nt<4, MODE>(a, p, grid, s);
-            case 5: return launch_wg_nt<5, MODE>(a, p, grid, s);
-            case 6: return launch_wg_nt<6, MODE>(a, p, grid, s);
-            case 7: return launch_wg_nt<7, MODE>(a, p, grid, s);
+        switch (v.IT) {
+            case 4: return launch_wg_nt<4, MODE>(a, p, v, grid, s);
+            case 5: return launch_wg_nt<5, MODE>(a, p, v, grid, s);
+            case 6: return launch_wg_nt<6, MODE>(a, p, v, grid, s);
+            case 7: return launch_wg_nt<7, MODE>(a, p, v, grid, s);
         }
     }
-    sprk::set_error("conv2d_bwd_weight: no kernel for %d k-tiles per wave", p.IT);
+    sprk::set_error("conv2d_bwd_weight: no kernel for %d k-tiles per wave", v.IT);
     return SPRK_EINVAL;
 }
 
-// conv_wgrad_mfma_kernel's argument block for layer g under plan p, and the kernel's MODE for these tensors (the plan's,
-// or the general kernel's 0 where their alignment or size rules the plan's staging out); wsf: the call's workspace (a
+int launch_wg(const WgArgs &a, const WgPlan &p, const WgVariant &v, hipStream_t s) {
+    dim3 grid(p.groups, p.nChunks, p.nblkN);
+    return v.MODE == 1 ? launch_wg_it<1>(a, p, v, grid, s)
+                       : v.MODE == 2 ? launch_wg_it<2>(a, p, v, grid, s) : launch_wg_it<0>(a, p, v, grid, s);
+}
+
+// The variant of conv_wgrad_mfma_kernel that layer g takes under plan p with these tensors (only their alignment is
+// looked at): the kernel's MODE is the plan's, or the general kernel's 0 where the tensors' alignment or size rules the
+// plan's staging out.  `stage` is left to wg_route; *refused: the 1x1 row form has no staging for these tensors.
+WgVariant wg_variant(const sprk_conv_geom *g, const WgPlan &p, const void *x, const void *x2, const void *gy, bool *refused) {
+    WgVariant v{};
+    const int Cin = g->C1 + g->C2;
+    v.IT = p.IT;
+    v.NT = p.NT;
+    v.WJ = (p.NT % 2 == 0) ? 2 : 1;
+    {
+        const bool geo = ((1 << p.lgTC) * g->stride) % 4 == 0 && (g->Win % 4) == 0;
+        v.vec1 = (geo && !g->up1 && aligned16(x)) ? 1 : 0;
+        v.vec2 = (geo && x2 && aligned16(x2)) ? 1 : 0;
+    }
+    v.xrow = p.xrow;
+    v.g4 = (p.lgTC >= 2 && (g->Wout % 4) == 0 && ((uintptr_t)gy & 15) == 0) ? 1 : 0;
+    // buffer-load staging of the row tiles needs 16-byte aligned rows and 32-bit byte offsets inside one tile
+    // group and one channel block; otherwise the general kernel (MODE 0) runs
+    const long planeI = (long)g->Hin * g->Win, planeO = (long)g->Hout * g->Wout;
+    const int NIw = 64 >> (p.lgTC + p.lgTR);
+    const bool fits = (long)NIw * Cin * planeI < (1L << 28) && (long)NIw * g->Cout * planeO < (1L << 28) &&
+                      (long)p.CKW * planeI < (1L << 28) && (long)p.NT * 16 * planeO < (1L << 28);
+    static const int rowbuf = sprk::knob_env("SPRK_WG_ROWBUF", 1);
+    const bool fast = rowbuf && fits && v.g4;
+    v.xtab = fast ? 1 : 0;
+    *refused = v.xrow && (!fast || (((uintptr_t)x & 15) != 0));
+    // MODE 2 additionally needs 16-byte aligned x / x2 (the general kernel ignores the table area in LDS)
+    const bool planesOk = v.vec1 && (g->C2 == 0 || v.vec2);
+    v.MODE = !fast ? 0 : (p.mode == 2 && !planesOk) ? 0 : p.mode;
+    v.chunks = p.nChunks > 1;
+    v.groups = p.groups > 1;
+    v.up1 = g->up1 ? 1 : 0;
+    v.c2 = g->C2 > 0;
+    v.tiles = p.tilesPerGroup;
+    return v;
+}
+
+// conv_wgrad_mfma_kernel's argument block for layer g under plan p and variant v; wsf: the call's workspace (a
 // zero-block-sized gap, then the partial sums)
-int wgrad_args(const sprk_conv_geom *g, const WgPlan &p, const float *x, const float *x2, const float *gy, float *wsf,
-               WgArgs &a, int *mode) {
+int wgrad_args(const sprk_conv_geom *g, const WgPlan &p, const WgVariant &v, const float *x, const float *x2,
+               const float *gy, float *wsf, WgArgs &a) {
     const float *zeros = nullptr;  // device-resident, never written: no per-call memset
     if (hipGetSymbolAddress((void **)&zeros, HIP_SYMBOL(g_zero_block)) != hipSuccess || !zeros) {
         sprk::set_error("conv2d_bwd_weight: zero block unavailable");
         return SPRK_ELAUNCH;
     }
-    const int Cin = g->C1 + g->C2;
     a = WgArgs{};
     a.x = x; a.x2 = x2; a.gy = gy; a.zeros = zeros; a.partial = wsf + kZeroFloats;
     a.N = g->N; a.C1 = g->C1; a.C2 = g->C2; a.Hin = g->Hin; a.Win = g->Win; a.up1 = g->up1;
@@ -1552,30 +1651,12 @@ int wgrad_args(const sprk_conv_geom *g, const WgPlan &p, const float *x, const f
     a.inRows = p.inRows; a.inCols = p.inCols; a.pitch = p.pitch; a.cplane = p.cplane; a.colOff = p.colOff;
     a.invImg = 1.0f / (float)(p.inRows * p.pitch);
     a.invPitch = 1.0f / (float)p.pitch;
-    {
-        const bool geo = ((1 << p.lgTC) * g->stride) % 4 == 0 && (g->Win % 4) == 0;
-        a.vec1 = (geo && !g->up1 && aligned16(x)) ? 1 : 0;
-        a.vec2 = (geo && x2 && aligned16(x2)) ? 1 : 0;
-        a.deal = 1;
-    }
-    a.xrow = p.xrow;
-    a.g4 = (p.lgTC >= 2 && (g->Wout % 4) == 0 && ((uintptr_t)gy & 15) == 0) ? 1 : 0;
-    // buffer-load staging of the row tiles needs 16-byte aligned rows and 32-bit byte offsets inside one tile
-    // group and one channel block; otherwise the general kernel (MODE 0) runs
-    const long planeI = (long)g->Hin * g->Win, planeO = (long)g->Hout * g->Wout;
-    const int NIw = 64 >> (p.lgTC + p.lgTR);
-    const bool fits = (long)NIw * Cin * planeI < (1L << 28) && (long)NIw * g->Cout * planeO < (1L << 28) &&
-                      (long)p.CKW * planeI < (1L << 28) && (long)p.NT * 16 * planeO < (1L << 28);
-    static const int rowbuf = sprk::knob_env("SPRK_WG_ROWBUF", 1);
-    const bool fast = rowbuf && fits && a.g4;
-    a.xtab = fast ? 1 : 0;
-    if (a.xrow && (!fast || (((uintptr_t)x & 15) != 0))) {
-        sprk::set_error("conv2d_bwd_weight: 1x1 row staging needs 16-byte aligned x / gy and < 2^28-element tiles");
-        return SPRK_EINVAL;
-    }
-    // MODE 2 additionally needs 16-byte aligned x / x2 (the general kernel ignores the table area in LDS)
-    const bool planesOk = a.vec1 && (g->C2 == 0 || a.vec2);
-    *mode = !fast ? 0 : (p.mode == 2 && !planesOk) ? 0 : p.mode;
+    a.vec1 = v.vec1;
+    a.vec2 = v.vec2;
+    a.deal = 1;
+    a.xrow = v.xrow;
+    a.g4 = v.g4;
+    a.xtab = v.xtab;
     static const int wg_diag = sprk::diag_env("SPRK_WG_DIAG");
     a.diag = wg_diag;
     a.nG1 = p.nG1;
@@ -1668,9 +1749,40 @@ static bool mask1x1_takes(const sprk_conv_geom *g, const sprk::Corr &c, const Fw
            sprk::mask1x1_steps(g->Cout, p.CK) > 0;
 }
 
+// Which stage of conv_dispatch takes the call, by the stages' own predicates in the dispatcher's order, and for the
+// stages that plan (mask1x1, MFMA) the plan and the kernel variant.  The dispatcher acts on this answer and
+// sprk_conv2d_variant returns it; the tensors are looked at for their alignment only.  x / x2 / y as conv_dispatch
+// takes them (backward-data: x = gy, y = gin); mask_y null: an unmasked call.
+static FwdVariant fwd_route(bool bwd, const sprk_conv_geom *g, const sprk_conv_epilogue *ep, const void *x, const void *x2,
+                            const void *y, const void *mask_y, FwdPlan *p) {
+    FwdVariant v{};
+    if (naive_of(g) || (bwd && g->stride != 1)) {
+        StemPlan sp;
+        v.stage = (bwd && !naive_of(g) && plan_stem_bwd(g, &sp)) ? SPRK_STAGE_STEM : SPRK_STAGE_DIRECT;
+        return v;
+    }
+    const sprk::Corr c = bwd ? sprk::Corr(*g) : sprk::Corr(*g, ep);
+    if (c.dt() != SPRK_DT_F32 && sprk::conv16_eligible(c)) {
+        v.stage = SPRK_STAGE_16BIT;
+    } else if (c.dtype & (SPRK_DT_X16 | SPRK_DT_Y16)) {
+        v.stage = SPRK_STAGE_REFUSED;   // the storage guard
+    } else if (sprk::wino_eligible(c)) {
+        v.stage = SPRK_STAGE_WINOGRAD;
+    } else if (!plan_fwd(c, p)) {
+        v.stage = SPRK_STAGE_REFUSED;   // no plan fits LDS
+    } else {
+        v = fwd_variant(c, *p, x, x2, y);
+        v.stage = (bwd && mask_y && mask1x1_takes(g, c, *p) && aligned16(x) && aligned16(y) && aligned16(mask_y))
+                      ? SPRK_STAGE_MASK1X1
+                      : SPRK_STAGE_MFMA;
+    }
+    return v;
+}
+
 // The one place where a forward or (bwd) backward-data call meets its kernel; a new convolution kernel is plugged in
-// here ("The convolution dispatcher").  g / ep: the layer as the caller gave it; for backward-data x = gy,
-// x2 = null, y = gin, and mask_y / mask_act the optional mask of sprk_conv2d_bwd_data_masked.  The stages, in order:
+// here and in fwd_route ("The convolution dispatcher").  g / ep: the layer as the caller gave it; for
+// backward-data x = gy, x2 = null, y = gin, and mask_y / mask_act the optional mask of sprk_conv2d_bwd_data_masked.
+// The stages, in order:
 //   direct kernels (SPRK_DT_NAIVE; strided backward-data) -> 16-bit operands -> storage guard -> Winograd -> MFMA
 // unrot (forward only): y is the un-rotated tensor f [N/4, 4*Cout, H, W] of sprk_unrot4_shift_concat_fwd, stored by the
 // kernel itself (sprk_conv2d_fwd_unrot); only the fp32 Winograd stage has such a store, any other stage refuses.
@@ -1692,12 +1804,16 @@ static int conv_dispatch(bool bwd, const float *x, const float *x2, const float 
     // the kernels without a masked epilogue: the mask is an in-place pass over the finished gradient
     auto masked = [&](int rc) { return (rc || !mask_y) ? rc : mask_in_place(y, mask_y, mask_act, g, s); };
 
-    if (naive_of(g) || (bwd && g->stride != 1)) {
+    FwdPlan p;
+    const FwdVariant v = fwd_route(bwd, g, ep, x, x2, y, mask_y, &p);
+    if (!sprk::wprep_describing()) t_last_fwd[bwd ? 1 : 0] = v;   // (a describing call launches nothing)
+
+    if (v.stage == SPRK_STAGE_DIRECT || v.stage == SPRK_STAGE_STEM) {
         if (sprk::wprep_describing()) return SPRK_OK;   // no weight transform on this path
         if (bwd) {
             DirectArgs a{nullptr, nullptr, w, x, y, *g, sprk::kNoEpilogue};
             StemPlan sp;
-            if (!naive_of(g) && plan_stem_bwd(g, &sp)) {   // the same sums from LDS copies of both operands
+            if (v.stage == SPRK_STAGE_STEM && plan_stem_bwd(g, &sp)) {   // the same sums from LDS copies of both operands
                 hipLaunchKernelGGL(conv_bwd_data_stem_kernel, dim3(g->N * sp.tilesX * sp.tilesY), dim3(kStemTW * kStemTH),
                                    sp.ldsBytes, s, a, sp.wr, sp.wc, sp.tilesX, sp.tilesY);
                 return masked(sprk::check_launch("conv_bwd_data_stem"));
@@ -1715,10 +1831,10 @@ static int conv_dispatch(bool bwd, const float *x, const float *x2, const float 
 
     // (a masked epilogue in conv16_tile_kernel<6> takes it from 231 to 256 VGPRs + 92 bytes of scratch — the next
     // tile's fetch is in flight during the stores — and the bf16 step from 11.22 to 11.27 ms: in-place pass)
-    if (c.dt() != SPRK_DT_F32 && sprk::conv16_eligible(c)) return masked(sprk::conv16_run(c, x, x2, w, y, ws, ws_bytes, s));
+    if (v.stage == SPRK_STAGE_16BIT) return masked(sprk::conv16_run(c, x, x2, w, y, ws, ws_bytes, s));
     if (int rc = check_storage32(who, c.dtype)) return rc;
 
-    if (sprk::wino_eligible(c)) {
+    if (v.stage == SPRK_STAGE_WINOGRAD) {
         if (int rc = sprk::check_ws(who, ws, ws_bytes, sprk::wino_ws_bytes(c))) return rc;
         // the mask is d act / d y of the layer that produced this conv's input, applied in the output transform: gin
         // leaves the kernel as that layer's pre-activation gradient
@@ -1727,24 +1843,23 @@ static int conv_dispatch(bool bwd, const float *x, const float *x2, const float 
     }
     SPRK_REQUIRE(!unrot, "conv2d_fwd_unrot: the call left the Winograd stage");
 
-    FwdPlan p;
-    SPRK_REQUIRE(plan_fwd(c, &p), "%s: geometry does not fit LDS", who);
+    SPRK_REQUIRE(v.stage != SPRK_STAGE_REFUSED, "%s: geometry does not fit LDS", who);
     if (int rc = sprk::check_ws(who, ws, ws_bytes, p.wsBytes)) return rc;
     float *wsf = (float *)ws;
     if (int rc = transform_weights(w, wsf, g->Cout, g->C1 + g->C2, g->KH * g->KW, c.taps, p, s)) return rc;
-    if (bwd && mask_y && mask1x1_takes(g, c, p) && aligned16(x) && aligned16(y) && aligned16(mask_y)) {
+    if (v.stage == SPRK_STAGE_MASK1X1) {
         // few reduced channels, 1x1: a streaming kernel of its own with the mask in its store, on the same slabs
         const sprk::Mask1x1Call m{x, wsf + kZeroFloats, mask_y, y, g->N, g->Cout, g->C1, g->Hin * g->Win,
                                   p.CK, p.R4, p.rows, p.ldw, p.NT, p.nblkN, mask_act};
         if (int rc = sprk::mask1x1_run(m, s)) return rc;
         return sprk::check_launch("mask1x1(bwd_data)");
     }
-    const ConvArgs a = conv_args(c, p, x, x2, wsf, y);
+    const ConvArgs a = conv_args(c, p, v, x, x2, wsf, y);
     // (a masked epilogue in this kernel costs 26 VGPRs — 160 -> 186, two workgroups per CU instead of three — for
     // every call, masked or not: measured in round 1 and again in round 3; the mask is applied by an in-place pass)
-    const int kclass = (p.MT == 4 && p.NT == 6) ? 0 : 2;   // 0: the dominant instantiation conv_mfma_kernel<4, 6>
+    const int kclass = (v.MT == 4 && v.NT == 6) ? 0 : 2;   // 0: the dominant instantiation conv_mfma_kernel<4, 6>
     sprk::prof_begin(kclass, c.flops, s);
-    if (int rc = launch_fwd(a, p, s)) return rc;
+    if (int rc = launch_fwd(a, p, v, s)) return rc;
     sprk::prof_end(kclass, s);
     return masked(sprk::check_launch(bwd ? "conv_mfma(bwd_data)" : "conv_mfma"));
 }
@@ -1827,6 +1942,27 @@ static size_t wgrad_ws_bytes(const sprk_conv_geom &g) {
 
 size_t sprk_conv2d_bwd_weight_ws_bytes(const sprk_conv_geom *g) { return g ? wgrad_ws_bytes(*g) : 0; }
 
+// Which stage of wgrad_dispatch takes the call, by the stages' own predicates in the dispatcher's order, and for the
+// MFMA stage the plan and the kernel variant: the twin of fwd_route.
+static WgVariant wg_route(const sprk_conv_geom *g, const void *x, const void *x2, const void *gy, WgPlan *p) {
+    WgVariant v{};
+    const bool naive = naive_of(g);   // skips the kernels, not the storage guard: the direct kernel reads fp32 tensors
+    if (!naive && sprk::wgrad16_ws_bytes(*g)) {   // eligible (never with fp32 operands)
+        v.stage = SPRK_STAGE_16BIT;
+    } else if (g->dtype & (SPRK_DT_X16 | SPRK_DT_Y16)) {
+        v.stage = SPRK_STAGE_REFUSED;   // the storage guard
+    } else if (!naive && sprk::wino_wgrad_eligible(*g)) {
+        v.stage = SPRK_STAGE_WINOGRAD;
+    } else if (naive || !plan_wgrad(g, p)) {
+        v.stage = SPRK_STAGE_DIRECT;
+    } else {
+        bool refused;
+        v = wg_variant(g, *p, x, x2, gy, &refused);
+        v.stage = refused ? SPRK_STAGE_REFUSED : SPRK_STAGE_MFMA;
+    }
+    return v;
+}
+
 // The one place where a backward-weight call meets its kernel, the twin of conv_dispatch; the layer's sprk_conv_geom is
 // the common description, and a kernel family is a predicate, a workspace size and a run function over it (DESIGN.md,
 // "The convolution dispatcher").  item == nullptr: finish the sum over the partial buffers now; otherwise describe it in
@@ -1840,39 +1976,77 @@ static int wgrad_dispatch(const float *x, const float *x2, const float *gy, floa
     SPRK_REQUIRE(x && gy && gw, "conv2d_bwd_weight: null tensor");
     SPRK_REQUIRE(g->C2 == 0 || x2, "conv2d_bwd_weight: C2 > 0 but x2 is null");
     hipStream_t s = (hipStream_t)stream;
-    const bool naive = naive_of(g);   // skips the kernels, not the storage guard: the direct kernel reads fp32 tensors
 
-    if (const size_t need16 = naive ? 0 : sprk::wgrad16_ws_bytes(*g)) {   // eligible (never with fp32 operands)
-        if (int rc = sprk::check_ws(who, ws, ws_bytes, need16)) return rc;
+    WgPlan p;
+    const WgVariant v = wg_route(g, x, x2, gy, &p);
+    t_last_wg = v;
+
+    if (v.stage == SPRK_STAGE_16BIT) {
+        if (int rc = sprk::check_ws(who, ws, ws_bytes, sprk::wgrad16_ws_bytes(*g))) return rc;
         return sprk::wgrad16_run(*g, x, x2, gy, gw, ws, item, s);
     }
     if (int rc = check_storage32(who, g->dtype)) return rc;
 
-    if (!naive && sprk::wino_wgrad_eligible(*g)) {
+    if (v.stage == SPRK_STAGE_WINOGRAD) {
         if (int rc = sprk::check_ws(who, ws, ws_bytes, sprk::wino_wgrad_ws_bytes(*g))) return rc;
         return sprk::wino_wgrad(*g, x, x2, gy, gw, ws, item, s);
     }
 
-    WgPlan p;
-    if (naive || !plan_wgrad(g, &p)) {
+    if (v.stage == SPRK_STAGE_DIRECT) {
         DirectArgs a{x, x2, nullptr, gy, gw, *g, sprk::kNoEpilogue};
         hipLaunchKernelGGL(conv_bwd_weight_direct_kernel, dim3(g->Cout * (g->C1 + g->C2)), dim3(256), 0, s, a);
         return sprk::check_launch("conv_bwd_weight_direct");
     }
     if (int rc = sprk::check_ws(who, ws, ws_bytes, p.wsBytes)) return rc;
+    SPRK_REQUIRE(v.stage != SPRK_STAGE_REFUSED,
+                 "conv2d_bwd_weight: 1x1 row staging needs 16-byte aligned x / gy and < 2^28-element tiles");
     float *wsf = (float *)ws;
     WgArgs a;
-    int mode;
-    if (int rc = wgrad_args(g, p, x, x2, gy, wsf, a, &mode)) return rc;
-    dim3 grid(p.groups, p.nChunks, p.nblkN);
+    if (int rc = wgrad_args(g, p, v, x, x2, gy, wsf, a)) return rc;
     sprk::prof_begin(1, sprk::conv_flops(*g), s);
-    const int rc = mode == 1 ? launch_wg<1>(a, p, grid, s) : mode == 2 ? launch_wg<2>(a, p, grid, s) : launch_wg<0>(a, p, grid, s);
-    if (rc) return rc;
+    if (int rc = launch_wg(a, p, v, s)) return rc;
     sprk::prof_end(1, s);
     if (int rc2 = sprk::check_launch("conv_wgrad_mfma")) return rc2;
     const int K = (g->C1 + g->C2) * g->KH * g->KW;
     const sprk_reduce_item it{wsf + kZeroFloats, gw, SPRK_RED_WGRAD, p.groups, 0, K, g->Cout, p.CoutP};
     return sprk::finish_or_defer(it, item, s);
+}
+
+// ---- which kernel variant: the query and the record of the last call --------------------------------------------------
+static void variant_out(const FwdVariant &v, int32_t *out) {
+    const int f[] = {v.stage, v.MT, v.NT, v.RB, v.XTAB, v.small, v.stages, v.ragged_k, v.latency, v.vec1, v.vec2, v.vec4,
+                     v.colOff, v.up1, v.c2, v.taps, v.CK, v.nChunks, v.blocks};
+    for (int i = 0; i < SPRK_VARIANT_INTS; ++i) out[i] = i < (int)(sizeof(f) / sizeof(f[0])) ? f[i] : 0;
+}
+static void variant_out(const WgVariant &v, int32_t *out) {
+    const int f[] = {v.stage, v.IT, v.NT, v.WJ, v.MODE, v.xrow, v.xtab, v.g4, v.vec1, v.vec2, v.chunks, v.groups, v.up1, v.c2,
+                     v.tiles};
+    for (int i = 0; i < SPRK_VARIANT_INTS; ++i) out[i] = i < (int)(sizeof(f) / sizeof(f[0])) ? f[i] : 0;
+}
+
+int sprk_conv2d_variant(int which, const sprk_conv_geom *g, const sprk_conv_epilogue *ep, const void *x, const void *x2,
+                        const void *y_or_gy, int32_t *out) {
+    SPRK_REQUIRE(out && which >= 0 && which <= 2, "conv2d_variant: which is 0 (forward), 1 (backward-data) or 2 (backward-weight)");
+    if (int rc = check_geom(g)) return rc;
+    if (which == 2) {
+        WgPlan p;
+        variant_out(wg_route(g, x, x2, y_or_gy, &p), out);
+    } else {
+        FwdPlan p;
+        // backward-data: the correlation reads gy and writes gin (here: x)
+        variant_out(which == 0 ? fwd_route(false, g, ep, x, x2, y_or_gy, nullptr, &p)
+                               : fwd_route(true, g, nullptr, y_or_gy, nullptr, x, nullptr, &p), out);
+    }
+    return SPRK_OK;
+}
+
+int sprk_conv2d_last_variant(int which, int32_t *out) {
+    SPRK_REQUIRE(out && which >= 0 && which <= 2, "conv2d_last_variant: which is 0 (forward), 1 (backward-data) or 2 (backward-weight)");
+    if (which == 2)
+        variant_out(t_last_wg, out);
+    else
+        variant_out(t_last_fwd[which], out);
+    return SPRK_OK;
 }
 
 int sprk_conv2d_bwd_weight(const float *x, const float *x2, const float *gy, float *gw, const sprk_conv_geom *g,

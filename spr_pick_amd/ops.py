@@ -327,6 +327,18 @@ def _conv_bwd_weight(ctx, x, x2, gpre, w):
     return gw
 
 
+def stuffed_bwd_data_geom(gd):
+    """Strided layers (the detector's down-sampling convolutions): the gradient w.r.t. the input is the stride-1
+    backward-data of gy with stride - 1 zeros between its samples — the MFMA kernel on a zero-stuffed copy (tiny
+    tensors) instead of the direct kernel (which stays for the 7x7 stem: one input channel would leave 15 of 16 MFMA
+    columns empty).  -> the geometry of that stride-1 call, or None where the layer's own geometry is the call's."""
+    if not (gd.stride > 1 and gd.C1 + gd.C2 >= 16 and not (gd.dtype & _lib.DT_NAIVE)):
+        return None
+    H1, W1 = (gd.Hout - 1) * gd.stride + 1, (gd.Wout - 1) * gd.stride + 1
+    return ConvGeom(gd.N, gd.C1, gd.C2, gd.Hin, gd.Win, gd.up1, gd.Cout, H1, W1, gd.KH, gd.KW, 1, gd.dil,
+                    gd.pad_top, gd.pad_left, gd.dtype)
+
+
 def _conv_bwd_input(ctx, x, x2, w, gpre, need1):
     """Step 3 -> (gx, gx2): backward-data (+ the fused activation backward of the producer of x), then the split of a
     concatenated / up-sampled input's gradient."""
@@ -340,17 +352,11 @@ def _conv_bwd_input(ctx, x, x2, w, gpre, need1):
                       g.pad_top, g.pad_left, base)
         wd = w[:, :g.C1].contiguous()
     gsrc = gpre
-    if gd.stride > 1 and gd.C1 + gd.C2 >= 16 and not (gd.dtype & _lib.DT_NAIVE):
-        # strided layers (the detector's down-sampling convolutions): the gradient w.r.t. the input is the
-        # stride-1 backward-data of gy with stride - 1 zeros between its samples — the MFMA kernel on a
-        # zero-stuffed copy (tiny tensors) instead of the direct kernel (which stays for the 7x7 stem: one
-        # input channel would leave 15 of 16 MFMA columns empty)
-        st = gd.stride
-        H1, W1 = (gd.Hout - 1) * st + 1, (gd.Wout - 1) * st + 1
-        gsrc = gpre.new_zeros((gd.N, gd.Cout, H1, W1))
+    gs = stuffed_bwd_data_geom(gd)
+    if gs is not None:
+        st, gd = gd.stride, gs
+        gsrc = gpre.new_zeros((gd.N, gd.Cout, gd.Hout, gd.Wout))
         gsrc[:, :, ::st, ::st] = gpre
-        gd = ConvGeom(gd.N, gd.C1, gd.C2, gd.Hin, gd.Win, gd.up1, gd.Cout, H1, W1, gd.KH, gd.KW, 1, gd.dil,
-                      gd.pad_top, gd.pad_left, gd.dtype)
     # storage types of this call: the gradient it reads as it is (if a kernel exists for that; a single tensor: an fp32
     # gradient is never cast up), the gradient it writes in the type of the tensor it belongs to
     fits, in16, (gsrc,) = _storage_cast((ctx.caps & 2) and gd.stride == 1, t16, gsrc)
