@@ -110,7 +110,8 @@ typedef struct sprk_conv_epilogue {
  * sprk_conv_epilogue | sprk_reduce_item). */
 #define SPRK_ABI_VERSION 430   /* 430: sprk_contam_*; sprk_ingest_*, sprk_extract_boxes, sprk_conv2d_fwd_unrot[_eligible] and
                                 * sprk_unrot_act_bwd[_eligible], sprk_conv2d_[last_]variant joined it compatibly (no signature or struct changed:
-                                * a binding that needs them finds a library without them by the missing symbol) */
+                                * a binding that needs them finds a library without them by the missing symbol); so did the
+                                * Winograd fields of the variant record, in slots that were documented as 0 */
 const char *sprk_last_error(void);
 int sprk_version(void);
 size_t sprk_struct_bytes(int which);
@@ -190,13 +191,30 @@ int sprk_conv2d_bwd_weight(const float *x, const float *x2, const float *gy, flo
  * SPRK_VARIANT_INTS integers.  x, x2: the layer's inputs (backward-data: x is gin, the tensor written); y_or_gy: y for
  * the forward call, gy otherwise.  The pointers are tested for 16-byte alignment only, never dereferenced.  Without a
  * device the plans are those of a 256-CU device (the MI355X).
- *   out[0] = stage, SPRK_STAGE_*; the other fields are filled by the stages that plan (MASK1X1, MFMA), else 0
+ *   out[0] = stage, SPRK_STAGE_*; the other fields are filled by the stages that plan (MASK1X1, MFMA: the two lists that
+ *   follow) and by the Winograd stage (the two lists after them), else 0
  *   which 0 / 1: [1] MT [2] NT [3] RB [4] XTAB [5] chunk_mma_small [6] K stages (1 | 2) [7] ragged last K-chunk
  *                [8] latency-bound re-chunking of K [9] vec1 [10] vec2 [11] vec4 [12] colOff != 0 [13] up1 [14] C2 > 0
  *                [15] taps (1: backward-data weight layout) [16] channels per K-chunk [17] K-chunks
  *                [18] workgroups of the launch (what the planner's 512-workgroup thresholds compare)
  *   which 2:     [1] IT [2] NT [3] WJ [4] MODE [5] xrow [6] xtab [7] g4 [8] vec1 [9] vec2 [10] nChunks > 1
  *                [11] groups > 1 [12] up1 [13] C2 > 0 [14] 64-pixel tiles one workgroup sums over
+ *   stage SPRK_STAGE_WINOGRAD, which 0 / 1 (wino_conv_kernel<NT, SQ, UNROT>, csrc/wino.hip):
+ *                [1] NT [2] SQ (1: 16 x 16-pixel workgroup tiles, 0: 8 x 32) [3] UNROT (sprk_conv2d_last_variant only: the
+ *                query knows no un-rotated store) [4] channel groups of NT * 16 (grid.y) [5] output channels in the last
+ *                group [6] 4-channel K chunks of source 1 [7] ... of both sources [8] C1 % 4 [9] C2 % 4 [10] pairs of
+ *                unchecked (steady-state) K iterations per tile [11] the issue that moves the cursor to source 2: 0 no
+ *                second source, 1 first_loads, 2 iteration 0, 3 a checked iteration, 4 an unchecked one [12] grid.x
+ *                [13] tiles [14] fewest and [15] most tiles of a persistent workgroup [16] XCD order in effect (grid.x % 8
+ *                == 0) [17] tilesX [18] tilesY [19] padT [20] padL (backward-data: mirrored) [21] reader of the output
+ *                transform: 0 plain, 1 mask (sprk_conv2d_last_variant only: the query is the unmasked call), 2 up2,
+ *                3 un-rotated store
+ *   stage SPRK_STAGE_WINOGRAD, which 2 (wino_wgrad_kernel<MT>):
+ *                [1] launches = column ranges of the reduction (1..4) [2 + 3 i] MT of launch i (3: groups of 48 input
+ *                channels, 1: a tail of <= 16) [3 + 3 i] its groups (MT 3) or tail channels (MT 1) [4 + 3 i] its parts
+ *                (grid.x: the K split) [14] regionsX [15] regionsY (regions of 4 x 16 pixels) [16] bit i: a workgroup of
+ *                launch i carries its region cursor over a region row (cx) [17] ... over an image (cy) [18] padT [19] padL
+ *                [20] Cout [21] bit i: launch i walks its regions in XCD order [22] bit i: launch i reads source 2
  * sprk_conv2d_last_variant returns the same record for the calling THREAD's last call of that kind as it was routed
  * (stage SPRK_STAGE_NONE before the first one; prepared-weight describe calls are not recorded).  Backward calls made
  * by an autograd engine run on its threads. */

@@ -88,6 +88,8 @@ _SIGS = {
     "sprk_unrot_act_bwd_eligible": (c_i, [c_i, c_i, c_i, c_i]),
     "sprk_conv2d_fwd_unrot_eligible": (c_i, [ctypes.POINTER(ConvGeom), ctypes.POINTER(ConvEpilogue)]),
     "sprk_conv2d_bwd_data_mask_fused": (c_i, [ctypes.POINTER(ConvGeom)]),
+    # out[24]: out[0] the stage; the MFMA stages and the Winograd stage fill the rest, each with its own fields
+    # (include/sprk.h lists them; tests/conv_variant_cases.py and tests/wino_variant_cases.py name them)
     "sprk_conv2d_variant": (c_i, [c_i, ctypes.POINTER(ConvGeom), ctypes.POINTER(ConvEpilogue), c_vp, c_vp, c_vp,
                                   ctypes.POINTER(ctypes.c_int32)]),
     "sprk_conv2d_last_variant": (c_i, [c_i, ctypes.POINTER(ctypes.c_int32)]),

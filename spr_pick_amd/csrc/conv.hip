@@ -1193,6 +1193,7 @@ struct FwdVariant {
     int colOff, up1, c2, taps;       // colOff != 0, source 1 up-sampled on load, a second source, Corr::taps
     int CK, nChunks;                 // channels per K-chunk, K-chunks
     int blocks;                      // workgroups of the launch (FwdPlan::blocks: what plan_fwd's thresholds compare)
+    sprk::WinoVariant wino;          // stage SPRK_STAGE_WINOGRAD: the kernel, grid and loop shapes of wino.hip (wino.h)
 };
 struct WgVariant {
     int stage;
@@ -1201,6 +1202,7 @@ struct WgVariant {
     int chunks, groups;              // nChunks > 1, groups > 1
     int up1, c2;
     int tiles;                       // 64-pixel tiles one workgroup sums over (WgPlan::tilesPerGroup)
+    sprk::WinoWgVariant wino;        // stage SPRK_STAGE_WINOGRAD: the launches of wino_wgrad (wino.h)
 };
 thread_local FwdVariant t_last_fwd[2] = {{SPRK_STAGE_NONE}, {SPRK_STAGE_NONE}};   // [0] forward, [1] backward-data
 thread_local WgVariant t_last_wg = {SPRK_STAGE_NONE};
@@ -1754,7 +1756,7 @@ static bool mask1x1_takes(const sprk_conv_geom *g, const sprk::Corr &c, const Fw
 // sprk_conv2d_variant returns it; the tensors are looked at for their alignment only.  x / x2 / y as conv_dispatch
 // takes them (backward-data: x = gy, y = gin); mask_y null: an unmasked call.
 static FwdVariant fwd_route(bool bwd, const sprk_conv_geom *g, const sprk_conv_epilogue *ep, const void *x, const void *x2,
-                            const void *y, const void *mask_y, FwdPlan *p) {
+                            const void *y, const void *mask_y, FwdPlan *p, bool unrot = false) {
     FwdVariant v{};
     if (naive_of(g) || (bwd && g->stride != 1)) {
         StemPlan sp;
@@ -1768,6 +1770,7 @@ static FwdVariant fwd_route(bool bwd, const sprk_conv_geom *g, const sprk_conv_e
         v.stage = SPRK_STAGE_REFUSED;   // the storage guard
     } else if (sprk::wino_eligible(c)) {
         v.stage = SPRK_STAGE_WINOGRAD;
+        v.wino = sprk::wino_variant(c, mask_y != nullptr, unrot ? g->N / 4 : 0);
     } else if (!plan_fwd(c, p)) {
         v.stage = SPRK_STAGE_REFUSED;   // no plan fits LDS
     } else {
@@ -1805,7 +1808,7 @@ static int conv_dispatch(bool bwd, const float *x, const float *x2, const float 
     auto masked = [&](int rc) { return (rc || !mask_y) ? rc : mask_in_place(y, mask_y, mask_act, g, s); };
 
     FwdPlan p;
-    const FwdVariant v = fwd_route(bwd, g, ep, x, x2, y, mask_y, &p);
+    const FwdVariant v = fwd_route(bwd, g, ep, x, x2, y, mask_y, &p, unrot);
     if (!sprk::wprep_describing()) t_last_fwd[bwd ? 1 : 0] = v;   // (a describing call launches nothing)
 
     if (v.stage == SPRK_STAGE_DIRECT || v.stage == SPRK_STAGE_STEM) {
@@ -1838,7 +1841,7 @@ static int conv_dispatch(bool bwd, const float *x, const float *x2, const float 
         if (int rc = sprk::check_ws(who, ws, ws_bytes, sprk::wino_ws_bytes(c))) return rc;
         // the mask is d act / d y of the layer that produced this conv's input, applied in the output transform: gin
         // leaves the kernel as that layer's pre-activation gradient
-        if (int rc = sprk::wino_conv(c, x, x2, w, y, (float *)ws, mask_y, mask_act, s, unrot ? g->N / 4 : 0)) return rc;
+        if (int rc = sprk::wino_conv(c, v.wino, x, x2, w, y, (float *)ws, mask_y, mask_act, s)) return rc;
         return sprk::check_launch(bwd ? "wino_conv(bwd_data)" : "wino_conv");
     }
     SPRK_REQUIRE(!unrot, "conv2d_fwd_unrot: the call left the Winograd stage");
@@ -1953,6 +1956,7 @@ static WgVariant wg_route(const sprk_conv_geom *g, const void *x, const void *x2
         v.stage = SPRK_STAGE_REFUSED;   // the storage guard
     } else if (!naive && sprk::wino_wgrad_eligible(*g)) {
         v.stage = SPRK_STAGE_WINOGRAD;
+        v.wino = sprk::wino_wgrad_variant(*g);
     } else if (naive || !plan_wgrad(g, p)) {
         v.stage = SPRK_STAGE_DIRECT;
     } else {
@@ -1989,7 +1993,7 @@ static int wgrad_dispatch(const float *x, const float *x2, const float *gy, floa
 
     if (v.stage == SPRK_STAGE_WINOGRAD) {
         if (int rc = sprk::check_ws(who, ws, ws_bytes, sprk::wino_wgrad_ws_bytes(*g))) return rc;
-        return sprk::wino_wgrad(*g, x, x2, gy, gw, ws, item, s);
+        return sprk::wino_wgrad(*g, v.wino, x, x2, gy, gw, ws, item, s);
     }
 
     if (v.stage == SPRK_STAGE_DIRECT) {
@@ -2014,11 +2018,31 @@ static int wgrad_dispatch(const float *x, const float *x2, const float *gy, floa
 
 // ---- which kernel variant: the query and the record of the last call --------------------------------------------------
 static void variant_out(const FwdVariant &v, int32_t *out) {
+    if (v.stage == SPRK_STAGE_WINOGRAD) {
+        const sprk::WinoVariant &w = v.wino;
+        const int f[] = {v.stage, w.NT, w.SQ, w.UNROT, w.groups, w.lastCh, w.nc1, w.nch, w.r1, w.r2, w.pairs, w.sw, w.gridX,
+                         w.ntiles, w.tpwMin, w.tpwMax, w.xcd, w.tilesX, w.tilesY, w.padT, w.padL, w.mode};
+        static_assert(sizeof(f) / sizeof(f[0]) <= SPRK_VARIANT_INTS, "the record fits");
+        for (int i = 0; i < SPRK_VARIANT_INTS; ++i) out[i] = i < (int)(sizeof(f) / sizeof(f[0])) ? f[i] : 0;
+        return;
+    }
     const int f[] = {v.stage, v.MT, v.NT, v.RB, v.XTAB, v.small, v.stages, v.ragged_k, v.latency, v.vec1, v.vec2, v.vec4,
                      v.colOff, v.up1, v.c2, v.taps, v.CK, v.nChunks, v.blocks};
     for (int i = 0; i < SPRK_VARIANT_INTS; ++i) out[i] = i < (int)(sizeof(f) / sizeof(f[0])) ? f[i] : 0;
 }
 static void variant_out(const WgVariant &v, int32_t *out) {
+    if (v.stage == SPRK_STAGE_WINOGRAD) {
+        const sprk::WinoWgVariant &w = v.wino;
+        int f[SPRK_VARIANT_INTS] = {v.stage, w.launches};
+        for (int i = 0; i < w.launches; ++i) f[2 + 3 * i] = w.l[i].MT, f[3 + 3 * i] = w.l[i].ch, f[4 + 3 * i] = w.l[i].parts;
+        int srcMask = 0;
+        for (int i = 0; i < w.launches; ++i) srcMask |= w.l[i].src << i;
+        const int t[] = {w.regionsX, w.regionsY, w.cx, w.cy, w.padT, w.padL, w.Cout, w.xcdMask, srcMask};
+        static_assert(14 + sizeof(t) / sizeof(t[0]) <= SPRK_VARIANT_INTS, "the record fits");
+        for (int i = 0; i < (int)(sizeof(t) / sizeof(t[0])); ++i) f[14 + i] = t[i];
+        for (int i = 0; i < SPRK_VARIANT_INTS; ++i) out[i] = f[i];
+        return;
+    }
     const int f[] = {v.stage, v.IT, v.NT, v.WJ, v.MODE, v.xrow, v.xtab, v.g4, v.vec1, v.vec2, v.chunks, v.groups, v.up1, v.c2,
                      v.tiles};
     for (int i = 0; i < SPRK_VARIANT_INTS; ++i) out[i] = i < (int)(sizeof(f) / sizeof(f[0])) ? f[i] : 0;

@@ -900,13 +900,54 @@ bool wino_unrot_eligible(const Corr &c) {
     return wino_eligible(c) && nt_of(c.Cout) == 6 && c.Hin == 64 && c.Win == 64 && c.N % 4 == 0 && !c.ep.up2 && c.taps == 0;
 }
 
-int wino_conv(const Corr &w, const float *x, const float *x2, const float *taps, float *y, float *U, const float *mask,
-              int mask_act, hipStream_t s, int unrotB) {
-    const int NT = nt_of(w.Cout), groups = cdiv(w.Cout, NT * 16);
+// The one place where a call on this stage gets its kernel, its grid and its chunk counts (wino.h).  The K loop of
+// wino_conv_kernel is walked here in its own terms: how many unchecked pairs a tile runs, and which kind of iteration
+// issues chunk nc1, the first of source 2.
+WinoVariant wino_variant(const Corr &w, bool masked, int unrotB) {
+    WinoVariant v{};
+    v.NT = nt_of(w.Cout);
+    v.groups = cdiv(w.Cout, v.NT * 16);
+    v.lastCh = w.Cout - (v.groups - 1) * v.NT * 16;
+    v.UNROT = unrotB ? 1 : 0;
+    v.unrotB = unrotB;
+    // (un-rotated store: 4 x 16 tiles give 32-byte runs along the output row for 90 / 270 degrees and 128-byte runs for
+    // 0 / 180, 8 x 8 tiles 64-byte runs for all four; SPRK_WINO_UNROT_SQ=1 in a diagnostic build takes the latter)
+    static const int unrot_sq = knob_env("SPRK_WINO_UNROT_SQ", 0);
+    v.SQ = (unrotB && unrot_sq) ? 1 : wino_square(w.Hin, w.Win);
+    v.tilesX = w.Win / (v.SQ ? Geo<1>::TC : Geo<0>::TC);
+    v.tilesY = w.Hin / (v.SQ ? Geo<1>::TR : Geo<0>::TR);
+    v.ntiles = v.tilesX * v.tilesY * w.N;
+    v.nc1 = cdiv(w.C1, CK);
+    v.nch = v.nc1 + cdiv(w.C2, CK);
+    v.r1 = w.C1 % CK;
+    v.r2 = w.C2 % CK;
+    v.padT = w.padT;
+    v.padL = w.padL;
+    v.mode = v.UNROT ? 3 : w.ep.up2 ? 2 : masked ? 1 : 0;
+    // persistent workgroups, one per CU: each walks tiles blockIdx.x, + gridDim.x, ... and starts the next tile's
+    // loads under its output transform (same-box A/B: +5..7 % on the 48-channel layers with their short K loops,
+    // +1.5 % on the 96-channel ones).  SPRK_WINO_PERSIST=0: one workgroup per tile.
+    static const int persist = knob_env("SPRK_WINO_PERSIST", 1);
+    v.gridX = persist ? std::min(v.ntiles, std::max(1, num_cus() / v.groups)) : v.ntiles;
+    v.tpwMin = v.ntiles / v.gridX;
+    v.tpwMax = cdiv(v.ntiles, v.gridX);
+    v.xcd = (xcd_on() && (v.gridX & 7) == 0) ? 1 : 0;
+    // the kernel's K loop: iteration c issues chunk c + 2 (first_loads: chunks 0 and 1)
+    int c = 2;
+    if (v.r1 == 0)
+        for (; c + 4 < v.nch; c += 2) ++v.pairs;
+    if (w.C2 > 0)
+        v.sw = v.nc1 == 1 ? 1 : v.nc1 == 2 ? 2 : (v.nc1 >= 4 && v.nc1 < 4 + 2 * v.pairs) ? 4 : 3;
+    return v;
+}
+
+int wino_conv(const Corr &w, const WinoVariant &v, const float *x, const float *x2, const float *taps, float *y, float *U,
+              const float *mask, int mask_act, hipStream_t s) {
+    const int NT = v.NT, groups = v.groups, unrotB = v.unrotB, sq = v.SQ;
     const int kclass = w.Cout > 48 ? kClassWino : 2;
     KArgs a{};
     a.x = x; a.x2 = x2; a.U = U; a.bias = w.ep.bias; a.scale = w.ep.scale; a.shift = w.ep.shift; a.y = y;
-    a.N = w.N; a.C1 = w.C1; a.C2 = w.C2; a.H = w.Hin; a.W = w.Win; a.Cout = w.Cout; a.padT = w.padT; a.padL = w.padL;
+    a.N = w.N; a.C1 = w.C1; a.C2 = w.C2; a.H = w.Hin; a.W = w.Win; a.Cout = w.Cout; a.padT = v.padT; a.padL = v.padL;
     a.act = w.ep.act;
     a.up2 = w.ep.up2 ? 1 : 0;
     a.mask = a.up2 ? nullptr : mask;
@@ -919,14 +960,10 @@ int wino_conv(const Corr &w, const float *x, const float *x2, const float *taps,
         set_error("wino_conv: no un-rotated store for this call");
         return SPRK_EINVAL;
     }
-    // (un-rotated store: 4 x 16 tiles give 32-byte runs along the output row for 90 / 270 degrees and 128-byte runs for
-    // 0 / 180, 8 x 8 tiles 64-byte runs for all four; SPRK_WINO_UNROT_SQ=1 in a diagnostic build takes the latter)
-    static const int unrot_sq = knob_env("SPRK_WINO_UNROT_SQ", 0);
-    const int sq = (unrotB && unrot_sq) ? 1 : wino_square(a.H, a.W);
-    a.tilesX = a.W / (sq ? Geo<1>::TC : Geo<0>::TC); a.tilesY = a.H / (sq ? Geo<1>::TR : Geo<0>::TR);
-    a.ntiles = a.tilesX * a.tilesY * w.N;
-    a.nc1 = cdiv(w.C1, CK);
-    a.nch = a.nc1 + cdiv(w.C2, CK);
+    a.tilesX = v.tilesX; a.tilesY = v.tilesY;
+    a.ntiles = v.ntiles;
+    a.nc1 = v.nc1;
+    a.nch = v.nch;
     if ((((uintptr_t)x | (uintptr_t)x2 | (uintptr_t)y | (uintptr_t)U) & 15) != 0) {
         set_error("wino_conv: tensors must be 16-byte aligned");
         return SPRK_EINVAL;
@@ -934,11 +971,7 @@ int wino_conv(const Corr &w, const float *x, const float *x2, const float *taps,
     const long total = (long)groups * a.nch * NT * CK * 16;
     if (int rc = wprep_site(wprep_item(WPREP_WINO, taps, U, total, {w.Cout, w.C1, w.C2, a.nc1, a.nch, NT, groups, w.taps}), s))
         return rc;
-    // persistent workgroups, one per CU: each walks tiles blockIdx.x, + gridDim.x, ... and starts the next tile's
-    // loads under its output transform (same-box A/B: +5..7 % on the 48-channel layers with their short K loops,
-    // +1.5 % on the 96-channel ones).  SPRK_WINO_PERSIST=0: one workgroup per tile.
-    static const int persist = knob_env("SPRK_WINO_PERSIST", 1);
-    const dim3 grid(persist ? std::min(a.ntiles, std::max(1, num_cus() / groups)) : a.ntiles, groups);
+    const dim3 grid(v.gridX, groups);
     const size_t lds = lds_bytes_of(NT);
     auto launch = [&](auto kernel) {
         if (int rc = lds_optin(kernel, lds, "wino_conv")) return rc;
@@ -1008,8 +1041,57 @@ size_t wino_wgrad_ws_bytes(const sprk_conv_geom &g) {
     return (size_t)kWgParts * g.Cout * (g.C1 + g.C2) * 9 * sizeof(float);
 }
 
-int wino_wgrad(const sprk_conv_geom &g, const float *x, const float *x2, const float *gy, float *gw, void *ws,
-               sprk_reduce_item *, hipStream_t s) {
+// The launches of a call (wino.h), and for each whether a workgroup's region cursor ever carries: the kernel's cursor
+// is walked here as the kernel walks it (issue() advances it once per region after the workgroup's first).
+WinoWgVariant wino_wgrad_variant(const sprk_conv_geom &g) {
+    WinoWgVariant v{};
+    v.regionsX = g.Win / WRW;
+    v.regionsY = g.Hin / WRH;
+    v.padT = g.pad_top;
+    v.padL = g.pad_left;
+    v.Cout = g.Cout;
+    const int cus = std::min(kWgParts, num_cus());
+    for (int src = 0; src < (g.C2 > 0 ? 2 : 1); ++src) {
+        int g48, tail;
+        wg_split(src ? g.C2 : g.C1, &g48, &tail);
+        // K split: one workgroup per CU over all channel groups
+        if (g48 > 0) v.l[v.launches++] = {3, g48, cus / g48, src, 0};
+        if (tail > 0) v.l[v.launches++] = {1, tail, cus, src, 0};
+    }
+    const int RX = v.regionsX, RY = v.regionsY, nregions = g.N * RY * RX;
+    for (int i = 0; i < v.launches; ++i) {
+        const int st = v.l[i].parts, t0 = st / RX;
+        const int d_rx = st - t0 * RX, d_ry = t0 - (t0 / RY) * RY;
+        v.l[i].xcd = (xcd_on() && (st & 7) == 0) ? 1 : 0;
+        v.xcdMask |= v.l[i].xcd << i;
+        if (d_rx == 0 && d_ry == 0) continue;   // the cursor moves by whole images
+        // (rx, ry) has RX * RY states and moves by a fixed step: what ever happens, happens within one period, and of
+        // the workgroups that start in the same state the first one walks the most regions — at most period^2 steps,
+        // and the walk ends as soon as both answers are known (cx needs d_rx != 0)
+        const int period = RX * RY;
+        const bool nox = d_rx == 0;
+        bool cx = false, cy = false;
+        for (int r0 = 0; r0 < st && r0 < nregions && r0 < period && !((cx || nox) && cy); ++r0) {
+            int rx = r0 % RX, ry = (r0 / RX) % RY, left = period;
+            for (int r = r0 + st; r < nregions && left-- > 0 && !((cx || nox) && cy); r += st) {
+                rx += d_rx;
+                const int kx = rx >= RX;
+                rx -= kx ? RX : 0;
+                ry += d_ry + kx;
+                const int ky = ry >= RY;
+                ry -= ky ? RY : 0;
+                cx |= kx != 0;
+                cy |= ky != 0;
+            }
+        }
+        v.cx |= (cx ? 1 : 0) << i;
+        v.cy |= (cy ? 1 : 0) << i;
+    }
+    return v;
+}
+
+int wino_wgrad(const sprk_conv_geom &g, const WinoWgVariant &v, const float *x, const float *x2, const float *gy, float *gw,
+               void *ws, sprk_reduce_item *, hipStream_t s) {
     float *partial = (float *)ws;
     if ((((uintptr_t)x | (uintptr_t)x2 | (uintptr_t)gy | (uintptr_t)partial) & 15) != 0) {
         set_error("wino_wgrad: tensors must be 16-byte aligned");
@@ -1019,37 +1101,29 @@ int wino_wgrad(const sprk_conv_geom &g, const float *x, const float *x2, const f
     const int CinTot = g.C1 + g.C2;
     WgRanges rg{};
     int nr = 0;
-    auto launch = [&](const float *src, int Csrc, int ci0) -> int {
-        int g48, tail;
-        wg_split(Csrc, &g48, &tail);
-        WgKArgs a{src, gy, partial, g.N, Csrc, 0, ci0, CinTot, g.Hin, g.Win, g.Cout, g.pad_top, g.pad_left, g.Win / WRW,
-                  g.Hin / WRH, xcd_on()};
-        if (g48 > 0) {
+    for (int i = 0; i < v.launches; ++i) {
+        const WinoWgVariant::Launch &l = v.l[i];
+        const int Csrc = l.src ? g.C2 : g.C1, ci0 = l.src ? g.C1 : 0;
+        WgKArgs a{l.src ? x2 : x, gy, partial, g.N, Csrc, 0, ci0, CinTot, g.Hin, g.Win, g.Cout, v.padT, v.padL, v.regionsX,
+                  v.regionsY, xcd_on()};
+        if (l.MT == 3) {
             if (int rc = lds_optin(wino_wgrad_kernel<3>, kWgLdsBytes, "wino_wgrad")) return rc;
-            const int parts = std::min(kWgParts, num_cus()) / g48;   // K split: one workgroup per CU over all channel groups
-            prof_begin(kClassWinoW, flops * (48.0 * g48) / CinTot, s);
-            hipLaunchKernelGGL(wino_wgrad_kernel<3>, dim3(parts, g48), dim3(kThreads), kWgLdsBytes, s, a);
+            prof_begin(kClassWinoW, flops * (48.0 * l.ch) / CinTot, s);
+            hipLaunchKernelGGL(wino_wgrad_kernel<3>, dim3(l.parts, l.ch), dim3(kThreads), kWgLdsBytes, s, a);
             prof_end(kClassWinoW, s);
             if (int rc = check_launch("wino_wgrad<3>")) return rc;
-            rg.end[nr] = ci0 + 48 * g48;
-            rg.parts[nr++] = parts;
-        }
-        if (tail > 0) {
+            rg.end[nr] = ci0 + 48 * l.ch;
+        } else {
             if (int rc = lds_optin(wino_wgrad_kernel<1>, kWgLdsBytes, "wino_wgrad")) return rc;
-            WgKArgs t = a;
-            t.cbase = 48 * g48;   // the tail group sits after the 48-channel groups
-            prof_begin(kClassWinoW, flops * (double)tail / CinTot, s);
-            hipLaunchKernelGGL(wino_wgrad_kernel<1>, dim3(std::min(kWgParts, num_cus()), 1), dim3(kThreads), kWgLdsBytes, s, t);
+            a.cbase = Csrc - l.ch;   // the tail group sits after the 48-channel groups
+            prof_begin(kClassWinoW, flops * (double)l.ch / CinTot, s);
+            hipLaunchKernelGGL(wino_wgrad_kernel<1>, dim3(l.parts, 1), dim3(kThreads), kWgLdsBytes, s, a);
             prof_end(kClassWinoW, s);
             if (int rc = check_launch("wino_wgrad<1>")) return rc;
             rg.end[nr] = ci0 + Csrc;
-            rg.parts[nr++] = std::min(kWgParts, num_cus());
         }
-        return SPRK_OK;
-    };
-    if (int rc = launch(x, g.C1, 0)) return rc;
-    if (g.C2 > 0)
-        if (int rc = launch(x2, g.C2, g.C1)) return rc;
+        rg.parts[nr++] = l.parts;
+    }
     for (int i = nr; i < 4; ++i) rg.end[i] = CinTot, rg.parts[i] = rg.parts[nr - 1];
     const long n = (long)g.Cout * CinTot * 9;
     hipLaunchKernelGGL(wino_wgrad_reduce_kernel, dim3(cdiv(n, 32)), dim3(256), 0, s, partial, gw, n, CinTot, rg);
