@@ -557,6 +557,29 @@ int sprk_ingest_finish(const float *binned, int by, int bx, const float *range, 
 size_t sprk_ingest_clip_ws_bytes(int by, int bx);
 int sprk_ingest_clip(const float *binned_in, float *binned_out, int by, int bx, long long k_lo, long long k_hi,
                      const float *range_in, float *range_out, void *ws, size_t ws_bytes, void *stream);
+/* sprk_ingest_flatten (optional, before sprk_ingest_finish; with sprk_ingest_clip: clip, flatten, clip again): the mean
+ * over a (2R+1) x (2R+1) window, clamped at the image's edges, subtracted from every pixel, so that a slow intensity
+ * gradient (ice wedge, carbon edge, uneven illumination) no longer takes the levels of the 8-bit range.
+ *   binned_in [by,bx] fp32 (finite), n = by*bx < 2^31; range_in float[2] device = (lo, hi) with lo <= x <= hi for every
+ *   pixel (sprk_ingest_bin's or sprk_ingest_clip's range_out); radius 1 <= R <= SPRK_INGEST_MAX_FLATTEN binned pixels.
+ *   span = double(hi) - double(lo).  span == 0: binned_out = +0.0f everywhere, range_out = (0, 0).  Else e = ilogb(span),
+ *   d = double(x) - double(lo)                       (one rounding),
+ *   t = (int64) floor(ldexp(d, 30 - e))              (0 <= t < 2^31; the scaling is exact),
+ *   window of (r, c): rows max(0, r-R) .. min(by-1, r+R), columns likewise, cnt its size,
+ *   S = the sum of t over the window, in integers: exact, whatever the order.  S < 2^31 * 2047^2 < 2^53, so double(S)
+ *       is exact too — that is the limit on R,
+ *   bg = ldexp(double(S) / double(cnt), e - 30)      (one correctly rounded division; the ldexp exact),
+ *   binned_out = float(d - bg)                       (a double subtraction, then one conversion; no fma);
+ *   range_out float[2] device = the exact min and max of binned_out.  binned_out may be binned_in, range_out may be
+ *   range_in.  Spans below 2^-60 can give fp32 subnormals; they follow the formula.
+ * A row pass writes the horizontal window sums of t as uint64 into the workspace (an LDS prefix sum per segment of 1024
+ * columns plus the R columns either side), a column pass moves a running integer sum down each column in chunks of
+ * rows that prime their own window, forms binned_out and leaves per-workgroup ranges, which the range kernel of
+ * sprk_ingest_bin reduces.  Three launches on `stream`, no host synchronisation, no atomics. */
+#define SPRK_INGEST_MAX_FLATTEN 1023
+size_t sprk_ingest_flatten_ws_bytes(int by, int bx, int R);
+int sprk_ingest_flatten(const float *binned_in, float *binned_out, int by, int bx, int R, const float *range_in,
+                        float *range_out, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- particle extraction (`joint extract`) -----------------------------------------------
  * Boxes cut out of ONE raw micrograph (the buffer sprk_ingest_bin takes: [ny,nx] samples of mode 0 / 1 / 2 / 6, 16-byte

@@ -54,6 +54,15 @@ def _clip(text):
         raise argparse.ArgumentTypeError(str(e))
 
 
+def _flatten(text):
+    """--flatten R: ingest.check_flatten of an integer, its ValueError as the parser's usage error."""
+    from .ingest import check_flatten
+    try:
+        return check_flatten(int(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 class _Parser(argparse.ArgumentParser):
     """A (sub-)parser may carry ``check``: arguments validated against each other at parse time (ValueError -> the
     parser's usage error), so that `--box 100 --bin 3` is refused like any other bad value and not by a traceback."""
@@ -72,6 +81,8 @@ class _Parser(argparse.ArgumentParser):
 def _check_eval(ns):
     if ns.clip is not None and ns.bin is None:
         raise ValueError("--clip belongs to the raw-micrograph ingest: give --bin N as well (N = 1 for unbinned files)")
+    if ns.flatten is not None and ns.bin is None:
+        raise ValueError("--flatten belongs to the raw-micrograph ingest: give --bin N as well (N = 1 for unbinned files)")
 
 
 def _check_extract(ns):
@@ -120,6 +131,10 @@ def build_parser():
                     help="with --bin: clamp each binned micrograph to its LO %% / (100 - HI) %% order statistics before the "
                          "min-max normalisation, so that hot pixels and black spots do not set the range (HI = LO when "
                          "omitted; 0 changes nothing)")
+    ev.add_argument("--flatten", type=_flatten, metavar="R",
+                    help="with --bin: subtract from each binned micrograph its mean over a (2R+1) x (2R+1) window (R in "
+                         "binned pixels, 1..1023) before the min-max normalisation, so that a slow gradient does not take "
+                         "the grey levels; with --clip: clip, flatten, clip again")
     ev.check = _check_eval
 
     bn = cmds.add_parser("bin", help="Bin raw micrographs N x N on the GPU (replaces the `newstack -bin N` preparation).")
@@ -130,6 +145,9 @@ def build_parser():
     bn.add_argument("--clip", type=_clip, metavar="LO[,HI]",
                     help="write the block means clamped to their LO %% / (100 - HI) %% order statistics (as `joint eval "
                          "--bin N --clip` sees them); HI = LO when omitted")
+    bn.add_argument("--flatten", type=_flatten, metavar="R",
+                    help="write the block means minus their mean over a (2R+1) x (2R+1) window (as `joint eval --bin N "
+                         "--flatten R` sees them); with --clip: clip, flatten, clip again")
 
     ex = cmds.add_parser("extract", help="Cut normalised particle stacks out of raw micrographs on the GPU "
                                          "(replaces the relion_preprocess step after picking).")
@@ -196,7 +214,7 @@ def run_train(args, parser):
 def run_eval(args):
     from .eval import DenoiserEvaluator
     evaluator = DenoiserEvaluator(args["model"], runs_dir=args["runs_dir"], contamination=args.get("contamination", False),
-                                  bin=args.get("bin"), clip=args.get("clip"))
+                                  bin=args.get("bin"), clip=args.get("clip"), flatten=args.get("flatten"))
     for flag, key in (("batch_size", ConfigValue.TEST_MINIBATCH_SIZE), ("nms", ConfigValue.NMS),
                       ("num", ConfigValue.NUM_EVAL)):
         if args.get(flag) is not None:
@@ -209,7 +227,8 @@ def run_eval(args):
 
 def run_bin(args):
     from . import ingest
-    return ingest.bin_dataset(args["dataset"], args["bin"], args["out"], labels=args.get("labels"), clip=args.get("clip"))
+    return ingest.bin_dataset(args["dataset"], args["bin"], args["out"], labels=args.get("labels"), clip=args.get("clip"),
+                              flatten=args.get("flatten"))
 
 
 def run_extract(args):

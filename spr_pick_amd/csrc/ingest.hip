@@ -37,6 +37,14 @@
 // (prefix, k) in the workspace.  Then the clamp x < lo ? lo : (x > hi ? hi : x) and the new range.  Exact: lo and hi are
 // elements of the image.  No host synchronisation.
 //
+// Optional too (sprk_ingest_flatten; with the clip: clip, flatten, clip again): the mean over a (2R+1)^2 window, clamped
+// at the edges, subtracted from every pixel — a slow gradient across the micrograph otherwise takes most of the 256
+// levels.  The window sums are integers: t = floor((x - lo) * 2^(30 - ilogb(hi - lo))) < 2^31, summed in uint64, so that
+// any order of summation, running updates included, gives the same bits as the NumPy model (include/sprk.h has the
+// contract).  A row pass (LDS prefix sums per row segment, windows reaching across segment boundaries) writes the
+// horizontal sums, a column pass runs a window sum down each column, lanes on adjacent columns, and stores
+// float((x - lo) - mean) with per-workgroup ranges for ingest_range_kernel.  Three launches, no host synchronisation.
+//
 // No a*b+c of this file may be contracted into an FMA.  hipcc contracts by default, and HIP's __fmul_rn / __fadd_rn are
 // plain operators that it contracts all the same (x*scale + shift came out as one v_fma_f32, and a file-scope
 // `#pragma clang fp contract(off)` did not stop it), so the Makefile compiles this translation unit with
@@ -447,6 +455,156 @@ __global__ __launch_bounds__(kThreads) void clip_clamp_kernel(const float *x, fl
     }
 }
 
+// ---- sprk_ingest_flatten: the mean over a clamped (2R+1)^2 window subtracted, in exact integer sums ------------------
+constexpr int kFlatSeg = 1024;                        // output columns of one row segment
+constexpr int kFlatRowBlocks = 2048;                  // grid cap of the row pass (grid-stride over the segments)
+constexpr int kFlatStrip = 64;                        // columns of a column-pass tile: one per lane of a wave
+constexpr int kFlatBatch = 8;                         // rows the column pass fetches ahead of their use
+
+// workspace: Part [kMaxBlocks] | H [by, bx] uint64, the horizontal window sums
+struct FlatScale {
+    double lo;
+    int e;          // ilogb(hi - lo)
+    bool flat;      // hi == lo: the output is +0.0f everywhere
+};
+__device__ __forceinline__ FlatScale flat_scale(const float *range) {
+    FlatScale s;
+    s.lo = (double)range[0];
+    const double span = (double)range[1] - s.lo;      // >= 2^-149 or 0: never a subnormal double
+    s.flat = !(span > 0.0);
+    s.e = s.flat ? 0 : (int)((__double_as_longlong(span) >> 52) & 0x7ff) - 1023;
+    return s;
+}
+// t = floor((x - lo) * 2^(30 - e)): 0 <= t < 2^31 for lo <= x <= hi, the scaling exact
+__device__ __forceinline__ unsigned int flat_fixed(float x, const FlatScale &s) {
+    return (unsigned int)(long long)floor(ldexp((double)x - s.lo, 30 - s.e));
+}
+
+// Row pass.  A workgroup takes row segments of kFlatSeg columns: t of the segment and of the R columns either side of
+// it (as far as the row goes) into LDS, an exclusive prefix sum P over them (thread i sums `per` consecutive elements,
+// the threads' totals are scanned through the waves), then H[r][c] = P[right end of c's window + 1] - P[left end].
+// Dynamic LDS, flatten_row_lds(R) bytes for span = kFlatSeg + 2R elements: P [span + 1] | wtot [4] | t [span] — a small
+// radius leaves room for eight workgroups on a CU, the largest (36.9 KB) for four.
+__global__ __launch_bounds__(kThreads) void flatten_row_kernel(const float *__restrict__ x, int by, int bx, int R,
+                                                               const float *__restrict__ range,
+                                                               unsigned long long *__restrict__ H) {
+    extern __shared__ unsigned long long flat_lds[];
+    const int span = kFlatSeg + 2 * R;
+    unsigned long long *P = flat_lds, *wtot = P + span + 1;
+    unsigned int *t = (unsigned int *)(wtot + kThreads / 64);
+    const FlatScale sc = flat_scale(range);
+    const int nseg = (bx + kFlatSeg - 1) / kFlatSeg;
+    const long total = (long)by * nseg;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (long w = blockIdx.x; w < total; w += gridDim.x) {
+        const int r = (int)(w / nseg), c0 = (int)(w - (long)r * nseg) * kFlatSeg;
+        const int cols = min(kFlatSeg, bx - c0);
+        const int base = max(c0 - R, 0);
+        const int len = min(c0 + cols - 1 + R, bx - 1) - base + 1;        // <= span
+        const float *row = x + (long)r * bx;
+        for (int i = threadIdx.x; i < len; i += kThreads) t[i] = sc.flat ? 0u : flat_fixed(row[base + i], sc);
+        __syncthreads();
+        const int per = (len + kThreads - 1) / kThreads;
+        const int first = min((int)threadIdx.x * per, len), last = min(first + per, len);
+        unsigned long long mine = 0;
+        for (int i = first; i < last; ++i) mine += t[i];
+        unsigned long long inc = mine;                                    // inclusive scan over the wave
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long u = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += u;
+        }
+        if (lane == 63) wtot[wave] = inc;
+        __syncthreads();
+        unsigned long long run = inc - mine;
+        for (int k = 0; k < wave; ++k) run += wtot[k];
+        if (threadIdx.x == 0) P[0] = 0;
+        for (int i = first; i < last; ++i) {
+            run += t[i];
+            P[i + 1] = run;
+        }
+        __syncthreads();
+        unsigned long long *out = H + (long)r * bx + c0;
+        for (int i = threadIdx.x; i < cols; i += kThreads) {
+            const int c = c0 + i;
+            out[i] = P[min(c + R, bx - 1) - base + 1] - P[max(c - R, 0) - base];
+        }
+        __syncthreads();                                                  // t, P and wtot are free again
+    }
+}
+
+// Column pass.  A wave takes tiles of kFlatStrip columns (one per lane: adjacent lanes on adjacent columns) by `chunk`
+// rows.  It primes S with the window of the tile's first row and then moves it down a row at a time: + the row that
+// enters, - the row that leaves.  Integers: the running sum is the window's sum, exactly.  y may be x (an element is
+// read and written by the same lane, and H holds everything else this pass reads).
+__global__ __launch_bounds__(kThreads) void flatten_col_kernel(const float *x, float *y, int by, int bx, int R, int chunk,
+                                                               const float *__restrict__ range,
+                                                               const unsigned long long *__restrict__ H,
+                                                               Part *__restrict__ parts) {
+    const FlatScale sc = flat_scale(range);
+    const int strips = (bx + kFlatStrip - 1) / kFlatStrip, chunks = (by + chunk - 1) / chunk;
+    const long tiles = (long)strips * chunks;
+    const int lane = threadIdx.x & 63;
+    const long nwaves = (long)gridDim.x * (kThreads / 64);
+    unsigned int lo = 0xffffffffu, hi = 0u;
+    for (long tile = (long)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); tile < tiles; tile += nwaves) {
+        const int c = (int)(tile % strips) * kFlatStrip + lane;           // neighbouring waves: neighbouring strips
+        const int r0 = (int)(tile / strips) * chunk, r1 = min(r0 + chunk, by);
+        if (c >= bx) continue;
+        const unsigned long long *Hc = H + c;
+        const int ncols = min(c + R, bx - 1) - max(c - R, 0) + 1;
+        unsigned long long S = 0;
+#pragma unroll 8
+        for (int q = max(r0 - R, 0); q <= min(r0 + R, by - 1); ++q) S += Hc[(long)q * bx];
+        // kFlatBatch rows at a time: their pixels and the rows that enter and leave are all fetched before the first
+        // is used (every load unconditional, from a clamped row; what lies outside the image is dropped afterwards),
+        // or each row would wait a whole memory latency for its own three loads
+        for (int rb = r0; rb < r1; rb += kFlatBatch) {
+            float px[kFlatBatch];
+            unsigned long long in[kFlatBatch], out[kFlatBatch];
+#pragma unroll
+            for (int j = 0; j < kFlatBatch; ++j) {
+                const int r = rb + j;
+                px[j] = x[(long)min(r, r1 - 1) * bx + c];
+                in[j] = Hc[(long)min(r + 1 + R, by - 1) * bx];
+                out[j] = Hc[(long)max(r - R, 0) * bx];
+            }
+#pragma unroll
+            for (int j = 0; j < kFlatBatch; ++j) {
+                const int r = rb + j;
+                if (r < r1) {
+                    float f = 0.0f;
+                    if (!sc.flat) {
+                        const int cnt = (min(r + R, by - 1) - max(r - R, 0) + 1) * ncols;    // <= 2047^2
+                        const double bg = ldexp((double)S / (double)cnt, sc.e - 30);          // S < 2^53: exact
+                        f = (float)(((double)px[j] - sc.lo) - bg);
+                    }
+                    y[(long)r * bx + c] = f;
+                    const unsigned int k = enc(f);
+                    lo = min(lo, k);
+                    hi = max(hi, k);
+                }
+                S += r + 1 + R <= by - 1 ? in[j] : 0ull;
+                S -= r - R >= 0 ? out[j] : 0ull;
+            }
+        }
+    }
+    block_range(lo, hi, parts);
+}
+
+size_t flatten_row_lds(int R) {
+    const size_t span = kFlatSeg + 2 * (size_t)R;
+    return (span + 1 + kThreads / 64) * sizeof(unsigned long long) + span * sizeof(unsigned int);
+}
+
+// Rows of a column-pass tile.  Priming reads 2R+1 rows of H per tile, so R rows and more keep H's traffic at most four
+// times its size; an image too small to give 2048 such tiles takes shorter ones, down to 32 rows (its H stays in the
+// L2).  Speed only: the sums are integers, any tiling gives the same bits.
+int flatten_chunk(int R, int by, int bx) {
+    const long fill = (long)by * sprk::cdiv(bx, kFlatStrip) / 2048;
+    return (int)std::max<long>(32, std::min<long>(R, fill));
+}
+constexpr size_t kFlatPartBytes = (size_t)kMaxBlocks * sizeof(Part);     // 16 KiB: H starts 16-byte aligned
+
 int clip_grid(long n) { return (int)std::min<long>(kClipBlocks, sprk::cdiv(sprk::cdiv(n, 4), kClipThreads)); }
 
 int sample_bytes(int mode) {
@@ -570,6 +728,36 @@ int sprk_ingest_clip(const float *binned_in, float *binned_out, int by, int bx, 
     hipLaunchKernelGGL(clip_clamp_kernel, dim3(grid_clamp), dim3(kThreads), 0, s, binned_in, binned_out, n, vec_out, st,
                        range_out);
     return sprk::check_launch("ingest_clip_clamp");
+}
+
+size_t sprk_ingest_flatten_ws_bytes(int by, int bx, int R) {
+    if (by < 1 || bx < 1 || (long)by * bx >= (1L << 31) || R < 1 || R > SPRK_INGEST_MAX_FLATTEN) return 0;
+    return kFlatPartBytes + (size_t)by * bx * sizeof(unsigned long long);
+}
+
+int sprk_ingest_flatten(const float *binned_in, float *binned_out, int by, int bx, int R, const float *range_in,
+                        float *range_out, void *ws, size_t ws_bytes, void *stream) {
+    SPRK_REQUIRE(binned_in && binned_out && range_in && range_out, "ingest_flatten: null pointer");
+    SPRK_REQUIRE(by > 0 && bx > 0 && (long)by * bx < (1L << 31), "ingest_flatten: bad image size %dx%d", by, bx);
+    // a window holds at most 2047^2 values below 2^31: their integer sum stays below 2^53, exact as a double
+    SPRK_REQUIRE(R >= 1 && R <= SPRK_INGEST_MAX_FLATTEN, "ingest_flatten: radius %d (1..%d)", R, SPRK_INGEST_MAX_FLATTEN);
+    if (int rc = sprk::check_ws("ingest_flatten", ws, ws_bytes, sprk_ingest_flatten_ws_bytes(by, bx, R))) return rc;
+    SPRK_REQUIRE(((uintptr_t)ws & 15) == 0, "ingest_flatten: the workspace must start 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    Part *parts = (Part *)ws;
+    unsigned long long *H = (unsigned long long *)((char *)ws + kFlatPartBytes);
+    const int grid_row = (int)std::min<long>((long)by * sprk::cdiv(bx, kFlatSeg), kFlatRowBlocks);
+    hipLaunchKernelGGL(flatten_row_kernel, dim3(grid_row), dim3(kThreads), flatten_row_lds(R), s, binned_in, by, bx, R,
+                       range_in, H);
+    if (int rc = sprk::check_launch("ingest_flatten_row")) return rc;
+    const int chunk = flatten_chunk(R, by, bx);
+    const long tiles = (long)sprk::cdiv(bx, kFlatStrip) * sprk::cdiv(by, chunk);
+    const int grid = (int)std::min<long>(sprk::cdiv(tiles, kThreads / 64), kMaxBlocks);
+    hipLaunchKernelGGL(flatten_col_kernel, dim3(grid), dim3(kThreads), 0, s, binned_in, binned_out, by, bx, R, chunk,
+                       range_in, H, parts);
+    if (int rc = sprk::check_launch("ingest_flatten_col")) return rc;
+    hipLaunchKernelGGL(ingest_range_kernel, dim3(1), dim3(kThreads), 0, s, parts, grid, range_out);
+    return sprk::check_launch("ingest_flatten_range");
 }
 
 }  // extern "C"

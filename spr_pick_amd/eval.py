@@ -7,7 +7,9 @@ With WORLD_SIZE > 1 micrograph i is processed by rank i % world; there is no col
 laid out on the device (ingest.py); ``{name}_scores.txt`` stays in the binned frame and, for N > 1,
 ``{name}_scores_unbinned.txt`` holds the same picks in the raw micrograph's frame.  ``clip=(lo_pct, hi_pct)``
 (``--clip LO[,HI]``, with ``bin`` only) clamps each binned micrograph to two of its order statistics before the min-max
-normalisation (``ingest.clip_ranks``): the pixels a model trained on ``joint bin --clip`` output saw."""
+normalisation (``ingest.clip_ranks``): the pixels a model trained on ``joint bin --clip`` output saw.  ``flatten=R``
+(``--flatten R``, with ``bin`` only) subtracts each binned micrograph's mean over a (2R+1)^2 window first (with ``clip``:
+clip, flatten, clip), as ``joint bin --flatten R`` writes it."""
 import logging
 import os
 
@@ -24,9 +26,9 @@ logger = logging.getLogger("joint.eval")
 
 class DenoiserEvaluator(DenoiserTrainer):
     def __init__(self, target_path, runs_dir=cfg_mod.DEFAULT_RUN_DIR, run_dir=None, device=None, contamination=False,
-                 bin=None, clip=None):
+                 bin=None, clip=None, flatten=None):
         super().__init__({}, "joint", runs_dir=runs_dir, run_dir=run_dir, device=device, contamination=contamination,
-                         bin=bin, clip=clip)
+                         bin=bin, clip=clip, flatten=flatten)
         state_dict = checkpoint.load(target_path)
         if "denoiser" in state_dict:
             self.load_state_dict(state_dict, restore_optimizer=False)

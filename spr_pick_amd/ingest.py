@@ -12,6 +12,12 @@ min-max step (``torch.ops.sprk.ingest_clip``, an exact selection on the device),
 not set the 8-bit range; ``joint bin --clip`` writes the clamped block means, and the closure above holds with the flag
 on both sides.  ``None`` adds no launch and changes no byte.
 
+``flatten=R`` (``--flatten R``) subtracts from every binned pixel the mean over its (2R+1) x (2R+1) window, clamped at the
+edges (``torch.ops.sprk.ingest_flatten``, exact integer window sums on the device), so that a slow gradient across the
+micrograph does not take the levels of the 8-bit range.  With ``clip`` as well the order is clip, flatten, clip again
+by the same percentages: the background is estimated without the outliers, and the final range comes from the order
+statistics of the flattened image.  The closure holds with the flags on both sides; ``None`` adds no launch.
+
 Coordinates: x runs along nx (columns), y along ny (rows) — the frame of the label tables and of ``*_scores.txt``.
 Bin factor N keeps the centred area: binned pixel (x, y) covers samples ox + N*x .. ox + N*x + N-1 (oy likewise)."""
 import logging
@@ -25,6 +31,7 @@ from . import micrograph_io, sampler as sampler_mod, torch_ops
 from .datasets import DetectionDataset
 
 MAX_BIN = torch_ops.INGEST_MAX_BIN
+MAX_FLATTEN = torch_ops.INGEST_MAX_FLATTEN
 logger = logging.getLogger("joint.ingest")
 _HEADER_BYTES = 1024
 
@@ -173,37 +180,52 @@ def clip_ranks(n, clip):
     return int(math.floor(lo / 100 * (n - 1))), (n - 1) - int(math.floor(hi / 100 * (n - 1)))
 
 
-def _bin(path, N, device, clip=None):
+def check_flatten(R):
+    """The radius of ``--flatten R`` in binned pixels: an integer in 1..MAX_FLATTEN (SPRK_INGEST_MAX_FLATTEN)."""
+    if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or not 1 <= R <= MAX_FLATTEN:
+        raise ValueError("flatten radius must be an integer in 1..%d, got %r" % (MAX_FLATTEN, R))
+    return int(R)
+
+
+def _bin(path, N, device, clip=None, flatten=None):
     N = check_bin(N)
     if clip is not None:
         clip = check_clip(clip)
+    if flatten is not None:
+        flatten = check_flatten(flatten)
     raw, header = read_raw(path, device)
     geometry = binned_geometry(header.ny, header.nx, N)
     binned, rng = torch.ops.sprk.ingest_bin(raw, header.mode, header.ny, header.nx, N)
     if clip is not None:      # the image clamped to two of its order statistics, which become the range (csrc/ingest.hip)
         binned, rng = torch.ops.sprk.ingest_clip(binned, rng, *clip_ranks(binned.numel(), clip))
+    if flatten is not None:   # minus the local mean; the background of the clamped image, then the clip of the flat one
+        binned, rng = torch.ops.sprk.ingest_flatten(binned, rng, flatten)
+        if clip is not None:
+            binned, rng = torch.ops.sprk.ingest_clip(binned, rng, *clip_ranks(binned.numel(), clip))
     return binned, rng, geometry
 
 
-def binned(path, bin, device="cuda", clip=None):
+def binned(path, bin, device="cuda", clip=None, flatten=None):
     """-> (float32 CUDA tensor [by, bx]: the N x N block means, geometry) — what ``joint bin`` writes.  ``clip``
-    (lo_pct, hi_pct): clamped to the order statistics of ``clip_ranks``; None: as they are."""
-    b, _, geometry = _bin(path, bin, device, clip)
+    (lo_pct, hi_pct): clamped to the order statistics of ``clip_ranks``; ``flatten`` R: minus the mean over the
+    (2R+1)^2 window (with ``clip``: clip, flatten, clip); None: as they are."""
+    b, _, geometry = _bin(path, bin, device, clip, flatten)
     return b, geometry
 
 
-def binned_uint8(path, bin, device="cuda", clip=None):
-    """-> uint8 array [by, bx]: ``micrograph_io.load_image`` of the binned (and, with ``clip``, clamped) micrograph."""
-    b, rng, _ = _bin(path, bin, device, clip)
+def binned_uint8(path, bin, device="cuda", clip=None, flatten=None):
+    """-> uint8 array [by, bx]: ``micrograph_io.load_image`` of the binned (and, with ``clip`` / ``flatten``, clamped /
+    flattened) micrograph."""
+    b, rng, _ = _bin(path, bin, device, clip, flatten)
     u8, _ = torch.ops.sprk.ingest_finish(b, rng, True, False)
     return u8.cpu().numpy()
 
 
-def ingest(path, bin, device="cuda", clip=None):
+def ingest(path, bin, device="cuda", clip=None, flatten=None):
     """-> (network input float32 CUDA [1, 1, S, S], (by, bx), (by, bx, oy, ox)): the binned micrograph (with ``clip``:
-    clamped to its two order statistics first) min-max quantised, /255, transposed and reflect-padded, as
-    ``MicrographFeed`` hands it to the network."""
-    b, rng, geometry = _bin(path, bin, device, clip)
+    clamped to its two order statistics first; with ``flatten``: its local mean subtracted) min-max quantised, /255,
+    transposed and reflect-padded, as ``MicrographFeed`` hands it to the network."""
+    b, rng, geometry = _bin(path, bin, device, clip, flatten)
     _, net = torch.ops.sprk.ingest_finish(b, rng, False, True)
     return net[None, None], geometry[:2], geometry
 
@@ -214,9 +236,11 @@ class RawMicrographFeed:
     is held in memory) and its tensor comes from ``ingest``.  IMAGE_SHAPE is [1, bx, by] (tensors are transposed), the
     target is all zeros (evaluation has no labels to draw), BIN_GEOMETRY carries (by, bx, oy, ox)."""
 
-    def __init__(self, rows, bin, count=None, device="cuda", rank=0, world=1, gt=None, clip=None):
+    def __init__(self, rows, bin, count=None, device="cuda", rank=0, world=1, gt=None, clip=None,
+                 flatten=None):
         self.bin = check_bin(bin)
         self.clip = None if clip is None else check_clip(clip)
+        self.flatten = None if flatten is None else check_flatten(flatten)
         self.device = torch.device(device)
         self.gt = gt or {}
         images = {}
@@ -238,7 +262,7 @@ class RawMicrographFeed:
         M = DetectionDataset.Metadata
         for pos, k in self.order:
             path, name = self.items[k]
-            inp, (by, bx), geometry = ingest(path, self.bin, self.device, self.clip)
+            inp, (by, bx), geometry = ingest(path, self.bin, self.device, self.clip, self.flatten)
             md = {M.INDEXES: torch.tensor([k]), M.NAME: [name], M.IMAGE_SHAPE: torch.tensor([[1, bx, by]]), M.GT: [],
                   M.BIN_GEOMETRY: [geometry]}
             if name in self.gt:
@@ -256,24 +280,27 @@ def unbinned_map(N, ox, oy):
     return to_raw
 
 
-def bin_dataset(dataset, bin, out_dir, labels=None, device="cuda", clip=None):
+def bin_dataset(dataset, bin, out_dir, labels=None, device="cuda", clip=None, flatten=None):
     """``joint bin``: every micrograph of the table / directory ``dataset`` binned on the device and written as a
     float32 MRC ``out_dir/{name}.mrc``, plus ``out_dir/images.txt`` (image_name, path) and, with ``labels``,
     ``out_dir/labels.txt`` (coordinates through ``to_binned``, points outside the binned area dropped, other columns
     kept).  Label rows of images that are not in the dataset are dropped too, with a warning that names them.
+    ``clip`` / ``flatten``: the image ``binned`` returns for them — what ``joint eval --bin N`` with the same flags sees.
     -> {"images": path, "labels": path or None, "geometry": {name: (by, bx, oy, ox)},
         "label_rows": {"kept", "outside", "unknown_image"} or None}."""
     from . import coordinates
     bin = check_bin(bin)
     if clip is not None:
         clip = check_clip(clip)
+    if flatten is not None:
+        flatten = check_flatten(flatten)
     rows = micrograph_io.read_image_table(dataset)
     if not rows:
         raise ValueError("no micrographs found in %s" % dataset)
     os.makedirs(out_dir, exist_ok=True)
     geometry, lines = {}, ["image_name\tpath"]
     for _, name, path in rows:
-        b, geometry[name] = binned(path, bin, device, clip)
+        b, geometry[name] = binned(path, bin, device, clip, flatten)
         out = os.path.join(out_dir, name + ".mrc")
         with open(out, "wb") as f:
             micrograph_io.write_mrc(f, b.cpu().numpy())

@@ -657,6 +657,42 @@ def _ingest_clip_fake(binned, rng, k_lo, k_hi):
 _register("ingest_clip", "(Tensor binned, Tensor range, int k_lo, int k_hi) -> (Tensor, Tensor)", _ingest_clip,
           _ingest_clip_fake)
 
+INGEST_MAX_FLATTEN = 1023                        # SPRK_INGEST_MAX_FLATTEN: a window's integer sum stays below 2^53
+
+
+def _flatten_check(binned, rng, R):
+    if binned.dim() != 2 or binned.dtype != torch.float32 or binned.numel() < 1:
+        raise _lib.SprkError("ingest_flatten: binned must be a non-empty 2-D float32 tensor, got %s %s"
+                             % (binned.dtype, tuple(binned.shape)))
+    if rng.dtype != torch.float32 or rng.numel() != 2 or not rng.is_contiguous() or rng.device != binned.device:
+        raise _lib.SprkError("ingest_flatten: range must be a contiguous float32 tensor of 2 elements on %s, got %s %s on %s"
+                             % (binned.device, rng.dtype, tuple(rng.shape), rng.device))
+    if not 1 <= R <= INGEST_MAX_FLATTEN:
+        raise _lib.SprkError("ingest_flatten: radius %d (1..%d)" % (R, INGEST_MAX_FLATTEN))
+
+
+def _ingest_flatten(binned, rng, R):
+    """-> (binned minus its mean over the clamped (2R+1)^2 window, float32 [by, bx]; range float32 [2] = the result's min
+    and max).  ``rng`` must bound ``binned`` (ingest_bin's or ingest_clip's).  Functional: neither argument is written."""
+    _flatten_check(binned, rng, R)
+    binned = binned.contiguous()
+    by, bx = binned.shape
+    L = _lib.lib()
+    out, rng_out = _f32(binned, (by, bx)), _f32(binned, (2,))
+    ws = _ws(L.sprk_ingest_flatten_ws_bytes(by, bx, int(R)), binned)
+    check(L.sprk_ingest_flatten(_p(binned), _p(out), by, bx, int(R), _p(rng), _p(rng_out), _p(ws), ws.numel(),
+                                _stream(binned)), "sprk_ingest_flatten")
+    return out, rng_out
+
+
+def _ingest_flatten_fake(binned, rng, R):
+    _flatten_check(binned, rng, R)
+    return binned.new_empty(tuple(binned.shape), dtype=torch.float32), binned.new_empty((2,), dtype=torch.float32)
+
+
+_register("ingest_flatten", "(Tensor binned, Tensor range, int R) -> (Tensor, Tensor)", _ingest_flatten,
+          _ingest_flatten_fake)
+
 
 # ---- particle extraction (extract.py: raw MRC samples + pick coordinates -> normalised particle stack) ------------------------
 EXTRACT_MAX_BOX = 1024                           # sprk_extract_boxes: the int64 sum of squares stays below 2^63 up to here

@@ -61,7 +61,8 @@ tensor_to_png = outputs_mod.tensor_to_png      # save_tensor_image (utils/data.p
 
 class DenoiserTrainer:
     def __init__(self, cfg, mode, state=None, runs_dir=cfg_mod.DEFAULT_RUN_DIR, run_dir=None, alpha=0.5, tau=0.01,
-                 bb=32, device=None, seed=0, graph=True, loss_scale=None, contamination=False, bin=None, clip=None):
+                 bb=32, device=None, seed=0, graph=True, loss_scale=None, contamination=False, bin=None, clip=None,
+                 flatten=None):
         self.runs_dir = os.path.abspath(runs_dir)
         self._run_dir = run_dir
         self.cfg = cfg
@@ -94,6 +95,10 @@ class DenoiserTrainer:
         if clip is not None and bin is None:
             raise ValueError("clip belongs to the raw-micrograph ingest: give bin as well")
         self.clip = None if clip is None else ingest_mod.check_clip(clip)
+        # ... and / or with its local mean over a (2R+1)^2 window subtracted (joint eval --bin N --flatten R)
+        if flatten is not None and bin is None:
+            raise ValueError("flatten belongs to the raw-micrograph ingest: give bin as well")
+        self.flatten = None if flatten is None else ingest_mod.check_flatten(flatten)
         self._metrics_file = None
         self._eval_modes_logged = set()
         self.trainfeed, self.testfeed = None, None
@@ -666,7 +671,8 @@ class DenoiserTrainer:
         if self.bin is not None:
             return ingest_mod.RawMicrographFeed(micrograph_io.read_image_table(c[ConfigValue.TEST_DATA_PATH]), self.bin,
                                                 count=cfg_mod.test_length(c), device=self.device, rank=self.rank,
-                                                world=self.world, gt=gt, clip=self.clip)
+                                                world=self.world, gt=gt, clip=self.clip,
+                                                flatten=self.flatten)
         groups, names = feed_mod.load_micrographs(c[ConfigValue.TEST_DATA_PATH], c.get(ConfigValue.TEST_LABEL_PATH),
                                                   radius=3, bb=c[ConfigValue.BB])
         return feed_mod.MicrographFeed(groups, names, count=cfg_mod.test_length(c), device=self.device,
