@@ -18,6 +18,7 @@
 // cross-check (SPRK_DT_NAIVE in sprk_conv_geom.dtype).
 #include "common.h"
 #include "conv16.h"
+#include "gemm1x1.h"
 #include "mask1x1.h"
 #include "wgrad16.h"
 #include "wino.h"
@@ -1751,6 +1752,17 @@ static bool mask1x1_takes(const sprk_conv_geom *g, const sprk::Corr &c, const Fw
            sprk::mask1x1_steps(g->Cout, p.CK) > 0;
 }
 
+// Stage 6: may the unmasked call c, planned as p, run on gemm1x1_kernel (gemm1x1.hip) instead of conv_mfma_kernel?  A 1x1
+// GEMM over many reduced channels on the plan of the launches that fill the machine (MT = 4, NT = 6: slabs of 96
+// channels whose 16-row chunks make slab row = reduced channel), nothing fused that the streaming kernel has no code
+// for.  The one predicate of the dispatcher and of sprk_conv2d_variant; the tensors' alignment is the caller's part.
+static bool gemm1x1_takes(const sprk::Corr &c, const FwdPlan &p) {
+    return sprk::g_gemm1x1_on.load(std::memory_order_relaxed) && c.KH == 1 && c.KW == 1 && c.stride == 1 && c.dil == 1 &&
+           c.padT == 0 && c.padL == 0 && !c.up1 && !c.mfma_only && c.C2 == 0 && !c.ep.up2 && !c.ep.res &&
+           c.Hin == c.Hout && c.Win == c.Wout && c.dt() == SPRK_DT_F32 && !c.x16() && !c.y16() && p.MT == 4 && p.NT == 6 &&
+           p.CK == 16 && p.R4 == 16 && p.ldw == sprk::kGemm1x1Ldw && sprk::gemm1x1_fits(c.N, c.C1, c.Hin * c.Win);
+}
+
 // Which stage of conv_dispatch takes the call, by the stages' own predicates in the dispatcher's order, and for the
 // stages that plan (mask1x1, MFMA) the plan and the kernel variant.  The dispatcher acts on this answer and
 // sprk_conv2d_variant returns it; the tensors are looked at for their alignment only.  x / x2 / y as conv_dispatch
@@ -1778,6 +1790,8 @@ static FwdVariant fwd_route(bool bwd, const sprk_conv_geom *g, const sprk_conv_e
         v.stage = (bwd && mask_y && mask1x1_takes(g, c, *p) && aligned16(x) && aligned16(y) && aligned16(mask_y))
                       ? SPRK_STAGE_MASK1X1
                       : SPRK_STAGE_MFMA;
+        if (v.stage == SPRK_STAGE_MFMA && !mask_y && !unrot && gemm1x1_takes(c, *p) && aligned16(x) && aligned16(y))
+            v.stage = SPRK_STAGE_GEMM1X1;
     }
     return v;
 }
@@ -1856,6 +1870,15 @@ static int conv_dispatch(bool bwd, const float *x, const float *x2, const float 
                                   p.CK, p.R4, p.rows, p.ldw, p.NT, p.nblkN, mask_act};
         if (int rc = sprk::mask1x1_run(m, s)) return rc;
         return sprk::check_launch("mask1x1(bwd_data)");
+    }
+    if (v.stage == SPRK_STAGE_GEMM1X1) {
+        // many reduced channels, 1x1, nothing fused: the streaming GEMM on the same slabs (timed with conv_mfma_kernel<4, 6>)
+        const sprk::Gemm1x1Call m{x, wsf + kZeroFloats, wsf, c.ep.bias, c.ep.scale, c.ep.shift, y, c.N, c.C1, c.Cout,
+                                  c.Hin * c.Win, p.rows, p.ldw, p.nblkN, c.ep.act};
+        sprk::prof_begin(0, c.flops, s);
+        if (int rc = sprk::gemm1x1_run(m, s)) return rc;
+        sprk::prof_end(0, s);
+        return sprk::check_launch(bwd ? "gemm1x1(bwd_data)" : "gemm1x1");
     }
     const ConvArgs a = conv_args(c, p, v, x, x2, wsf, y);
     // (a masked epilogue in this kernel costs 26 VGPRs — 160 -> 186, two workgroups per CU instead of three — for

@@ -3,6 +3,7 @@
 #include "common.h"
 #include "wprep_dev.h"
 #include "conv16.h"
+#include "gemm1x1.h"
 #include "wgrad16.h"
 
 #include <mutex>
@@ -305,6 +306,8 @@ size_t sprk_struct_bytes(int which) {
 long sprk_launch_count(void) { return sprk::g_launches.load(); }
 long sprk_wino_launch_count(void) { return sprk::g_wino_launches.load(); }
 long sprk_mask1x1_launch_count(void) { return sprk::g_mask1x1_launches.load(); }
+long sprk_gemm1x1_launch_count(void) { return sprk::g_gemm1x1_launches.load(); }
+void sprk_gemm1x1_enable(int on) { sprk::g_gemm1x1_on.store(on ? 1 : 0); }
 long sprk_conv16_launch_count(void) { return sprk::conv16_launches() + sprk::wgrad16_launches(); }
 long sprk_wgrad16_launch_count(void) { return sprk::wgrad16_launches(); }
 
