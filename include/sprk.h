@@ -111,7 +111,7 @@ typedef struct sprk_conv_epilogue {
 #define SPRK_ABI_VERSION 430   /* 430: sprk_contam_*; sprk_ingest_*, sprk_extract_boxes, sprk_conv2d_fwd_unrot[_eligible] and
                                 * sprk_unrot_act_bwd[_eligible], sprk_conv2d_[last_]variant joined it compatibly (no signature or struct changed:
                                 * a binding that needs them finds a library without them by the missing symbol); so did the
-                                * Winograd fields of the variant record, in slots that were documented as 0 */
+                                * Winograd and the 16-bit fields of the variant record, in slots that were documented as 0 */
 const char *sprk_last_error(void);
 int sprk_version(void);
 size_t sprk_struct_bytes(int which);
@@ -198,7 +198,7 @@ int sprk_conv2d_bwd_weight(const float *x, const float *x2, const float *gy, flo
  * the forward call, gy otherwise.  The pointers are tested for 16-byte alignment only, never dereferenced.  Without a
  * device the plans are those of a 256-CU device (the MI355X).
  *   out[0] = stage, SPRK_STAGE_*; the other fields are filled by the stages that plan (MASK1X1, MFMA, GEMM1X1: the two lists that
- *   follow) and by the Winograd stage (the two lists after them), else 0
+ *   follow), by the Winograd stage (the two lists after them) and by the 16-bit stage (the last two), else 0
  *   which 0 / 1: [1] MT [2] NT [3] RB [4] XTAB [5] chunk_mma_small [6] K stages (1 | 2) [7] ragged last K-chunk
  *                [8] latency-bound re-chunking of K [9] vec1 [10] vec2 [11] vec4 [12] colOff != 0 [13] up1 [14] C2 > 0
  *                [15] taps (1: backward-data weight layout) [16] channels per K-chunk [17] K-chunks
@@ -221,6 +221,30 @@ int sprk_conv2d_bwd_weight(const float *x, const float *x2, const float *gy, flo
  *                (grid.x: the K split) [14] regionsX [15] regionsY (regions of 4 x 16 pixels) [16] bit i: a workgroup of
  *                launch i carries its region cursor over a region row (cx) [17] ... over an image (cy) [18] padT [19] padL
  *                [20] Cout [21] bit i: launch i walks its regions in XCD order [22] bit i: launch i reads source 2
+ *   stage SPRK_STAGE_16BIT, which 0 / 1 (csrc/conv16.hip; the plans that launch fill it, backward-data in the terms of its
+ *   correlation: C1 = the layer's Cout, pads mirrored): [1] kind: 1 conv16_mfma_kernel<T, MT, NT, RB>, 2 conv16_tile_kernel
+ *                <T, NT, X16, Y16>, 3 conv16_head_kernel<T, CQ, CK, X16, Y16> [2] T: 1 bf16, 2 f16 [3] X16 [4] Y16, then
+ *     kind 1:    [5] MT [6] NT [7] RB [8] CK [9] K chunks [10] channels and [11] 8-channel groups (c8) of the last chunk
+ *                [12] colOff [13] NI (images per tile) [14] tilesX [15] tilesY [16] image groups [17] output-channel blocks
+ *                (grid.y) [18] up2 [19] 1 + the chunk that takes channels of both sources (0: none) [20] a chunk comes from
+ *                source 2 alone [21] taps (1 | 9) [22] padT [23] padL
+ *     kind 2:    [5] NT [6] lgTC [7] lgTR [8] NI [9] tilesX [10] tilesY [11] image groups [12] output-channel blocks
+ *                [13] K chunks of 16 [14] c8 of the last chunk (1 | 2) [15] cshift + 16 padL + 256 padT [16] tiles [17] up2
+ *                [18] grid.x on 256 CUs [19] fewest and [20] most tiles of a persistent workgroup [21] 1 + the chunk that
+ *                straddles the sources (0: none) [22] bit 0: a chunk comes from source 2 alone, bit 1: some workgroup's
+ *                next tile lies in the same image group, bit 2: some workgroup's in another one [23] 16-bit output: the
+ *                tiles that take the LDS-transposed store: 0 none, 1 some (the others store directly), 2 all
+ *     kind 3:    [5] CQ [6] CK [7] K chunks [8] pixel tiles per image [9] pixels of an image's last tile [10] output-channel
+ *                quarters of 96 that store anything [11] channels of the last of them
+ *   stage SPRK_STAGE_16BIT, which 2 (csrc/wgrad16.hip): [1] kind: 1 wgrad16_kernel<T, MC, LGRW, X16, PL1>, 2 wgrad16_1x1_kernel
+ *                <T, .., X16> [2] T [3] X16, then
+ *     kind 1:    [4] MC [5] lgRW [6] PL1 [7] regX [8] regY [9] seg (vertical segments of a strip) [10] segLen [11] units
+ *                (N * regX * seg) [12] parts (grid.x) [13] input-channel blocks of 48 (grid.y) [14] tail (the 48 k + 1-th
+ *                channel rides in block 0) [15] fewest and [16] most units of a workgroup [17] a block holds channels of both
+ *                sources [18] the source of the tail channel (0: no tail) [19] padT [20] padL [21] XCD order in effect
+ *                [22] 16-channel tiles of the last block that hold channels (1..3)
+ *     kind 2:    [4] wide (192 x 192 blocks; 0: 96 x 384) [5] coBlocks [6] ciBlocks [7] parts [8] regions of 64 pixels per part
+ *                [9] ... of the last part [10] regions per image [11] output and [12] input channels of the last block
  * sprk_conv2d_last_variant returns the same record for the calling THREAD's last call of that kind as it was routed
  * (stage SPRK_STAGE_NONE before the first one; prepared-weight describe calls are not recorded).  Backward calls made
  * by an autograd engine run on its threads. */

@@ -1195,6 +1195,7 @@ struct FwdVariant {
     int CK, nChunks;                 // channels per K-chunk, K-chunks
     int blocks;                      // workgroups of the launch (FwdPlan::blocks: what plan_fwd's thresholds compare)
     sprk::WinoVariant wino;          // stage SPRK_STAGE_WINOGRAD: the kernel, grid and loop shapes of wino.hip (wino.h)
+    int32_t rec16[SPRK_VARIANT_INTS];   // stage SPRK_STAGE_16BIT: the record as conv16_variant fills it (conv16.h)
 };
 struct WgVariant {
     int stage;
@@ -1204,6 +1205,7 @@ struct WgVariant {
     int up1, c2;
     int tiles;                       // 64-pixel tiles one workgroup sums over (WgPlan::tilesPerGroup)
     sprk::WinoWgVariant wino;        // stage SPRK_STAGE_WINOGRAD: the launches of wino_wgrad (wino.h)
+    int32_t rec16[SPRK_VARIANT_INTS];   // stage SPRK_STAGE_16BIT: the record as wgrad16_variant fills it (wgrad16.h)
 };
 thread_local FwdVariant t_last_fwd[2] = {{SPRK_STAGE_NONE}, {SPRK_STAGE_NONE}};   // [0] forward, [1] backward-data
 thread_local WgVariant t_last_wg = {SPRK_STAGE_NONE};
@@ -1778,6 +1780,7 @@ static FwdVariant fwd_route(bool bwd, const sprk_conv_geom *g, const sprk_conv_e
     const sprk::Corr c = bwd ? sprk::Corr(*g) : sprk::Corr(*g, ep);
     if (c.dt() != SPRK_DT_F32 && sprk::conv16_eligible(c)) {
         v.stage = SPRK_STAGE_16BIT;
+        sprk::conv16_variant(c, v.rec16);
     } else if (c.dtype & (SPRK_DT_X16 | SPRK_DT_Y16)) {
         v.stage = SPRK_STAGE_REFUSED;   // the storage guard
     } else if (sprk::wino_eligible(c)) {
@@ -1975,6 +1978,7 @@ static WgVariant wg_route(const sprk_conv_geom *g, const void *x, const void *x2
     const bool naive = naive_of(g);   // skips the kernels, not the storage guard: the direct kernel reads fp32 tensors
     if (!naive && sprk::wgrad16_ws_bytes(*g)) {   // eligible (never with fp32 operands)
         v.stage = SPRK_STAGE_16BIT;
+        sprk::wgrad16_variant(*g, v.rec16);
     } else if (g->dtype & (SPRK_DT_X16 | SPRK_DT_Y16)) {
         v.stage = SPRK_STAGE_REFUSED;   // the storage guard
     } else if (!naive && sprk::wino_wgrad_eligible(*g)) {
@@ -2041,6 +2045,11 @@ static int wgrad_dispatch(const float *x, const float *x2, const float *gy, floa
 
 // ---- which kernel variant: the query and the record of the last call --------------------------------------------------
 static void variant_out(const FwdVariant &v, int32_t *out) {
+    if (v.stage == SPRK_STAGE_16BIT) {
+        out[0] = v.stage;
+        for (int i = 1; i < SPRK_VARIANT_INTS; ++i) out[i] = v.rec16[i];
+        return;
+    }
     if (v.stage == SPRK_STAGE_WINOGRAD) {
         const sprk::WinoVariant &w = v.wino;
         const int f[] = {v.stage, w.NT, w.SQ, w.UNROT, w.groups, w.lastCh, w.nc1, w.nch, w.r1, w.r2, w.pairs, w.sw, w.gridX,
@@ -2054,6 +2063,11 @@ static void variant_out(const FwdVariant &v, int32_t *out) {
     for (int i = 0; i < SPRK_VARIANT_INTS; ++i) out[i] = i < (int)(sizeof(f) / sizeof(f[0])) ? f[i] : 0;
 }
 static void variant_out(const WgVariant &v, int32_t *out) {
+    if (v.stage == SPRK_STAGE_16BIT) {
+        out[0] = v.stage;
+        for (int i = 1; i < SPRK_VARIANT_INTS; ++i) out[i] = v.rec16[i];
+        return;
+    }
     if (v.stage == SPRK_STAGE_WINOGRAD) {
         const sprk::WinoWgVariant &w = v.wino;
         int f[SPRK_VARIANT_INTS] = {v.stage, w.launches};

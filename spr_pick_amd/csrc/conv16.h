@@ -15,5 +15,8 @@ size_t conv16_ws_bytes(const Corr &c);
 int conv16_run(const Corr &c, const void *x, const void *x2, const float *w, void *y, void *ws,
                size_t ws_bytes, hipStream_t s);
 long conv16_launches();
+// rec[1 .. SPRK_VARIANT_INTS - 1] of sprk_conv2d_variant's record for stage SPRK_STAGE_16BIT (sprk.h): the kernel that
+// conv16_run launches for c and the loops it runs there, from the same plans; rec[0] is the caller's
+void conv16_variant(const Corr &c, int32_t *rec);
 
 }  // namespace sprk

@@ -956,10 +956,13 @@ int launch16_nt(const Conv16Args &k, const Plan16 &p, dim3 grid, hipStream_t s) 
     }
 }
 
+// RB of conv16_mfma_kernel<T, MT, NT, RB>: the tile rows a wave's pixel tiles span
+int rows16(const Plan16 &p) { return std::max(1, (p.MT * 16) >> p.lgTC); }
+
 template <typename T>
 int launch16(const Conv16Args &k, const Plan16 &p, hipStream_t s) {
     dim3 grid(p.imgGroups * p.tilesX * p.tilesY, p.nblkN);
-    const int rows = std::max(1, (p.MT * 16) >> p.lgTC);   // tile rows a wave's pixel tiles span
+    const int rows = rows16(p);
     if (p.MT == 4)
         return rows == 1 ? launch16_nt<T, 4, 1>(k, p, grid, s)
                          : rows == 2 ? launch16_nt<T, 4, 2>(k, p, grid, s) : launch16_nt<T, 4, 4>(k, p, grid, s);
@@ -1003,13 +1006,18 @@ bool plan_tile(int Nimg, int Ck, int Nn, int Ho, int Wo, int x16, int padL, Plan
     return true;
 }
 
-template <typename T, bool X16, bool Y16>
-int launch_tile(const Tile16Args &k, const PlanT &p, hipStream_t s) {
-    // persistent workgroups: one per CU (8 waves at 159-225 VGPRs fill it), shared among the output-channel blocks
+// grid.x of conv16_tile_kernel: persistent workgroups, one per CU (8 waves at 159-225 VGPRs fill it), shared among the
+// output-channel blocks
+int tile_grid_x(const PlanT &p) {
     const int ntiles = p.imgGroups * p.tilesX * p.tilesY;
     static const int persist = sprk::knob_env("SPRK_C16_PERSIST", 1);   // 0 = one tile each
     const int slots = std::max(1, sprk::num_cus() / p.nblkN);
-    dim3 grid(persist ? std::min(ntiles, slots) : ntiles, p.nblkN);
+    return persist ? std::min(ntiles, slots) : ntiles;
+}
+
+template <typename T, bool X16, bool Y16>
+int launch_tile(const Tile16Args &k, const PlanT &p, hipStream_t s) {
+    dim3 grid(tile_grid_x(p), p.nblkN);
     auto go = [&](auto kernel) {
         if (int rc = sprk::lds_optin(kernel, p.ldsBytes, "conv16")) return rc;
         hipLaunchKernelGGL(kernel, grid, dim3(kTileThreads), p.ldsBytes, s, k);
@@ -1095,6 +1103,75 @@ size_t conv16_ws_bytes(const Corr &c) {
 }
 
 long conv16_launches() { return g_conv16_launches.load(); }
+
+// ---- the record of a call: stage SPRK_STAGE_16BIT of sprk_conv2d_[last_]variant (sprk.h lists the fields) -------------
+// One function per planner states the loops its kernel then runs, in the kernel's own terms.
+static int type_code(const Corr &c) { return (c.dtype & SPRK_DT_MASK) == SPRK_DT_BF16 ? 1 : 2; }
+
+// Where a K loop of `ck`-channel chunks meets the second source: *straddle = 1 + the chunk that takes channels of both
+// (0: none: no second source, or C1 ends on a chunk boundary); *whole2: some chunk comes from source 2 alone
+static void source_switch(const Corr &c, int ck, int nchunks, int *straddle, int *whole2) {
+    *straddle = (c.C2 > 0 && c.C1 % ck != 0) ? c.C1 / ck + 1 : 0;
+    *whole2 = (c.C2 > 0 && cdiv(c.C1, ck) < nchunks) ? 1 : 0;
+}
+
+// conv16_mfma_kernel under plan16's plan
+static void describe16(const Corr &c, const Plan16 &p, int32_t *r) {
+    const int Cin = c.C1 + c.C2, ckeLast = Cin - (p.nchunks - 1) * p.CK;
+    int straddle, whole2;
+    source_switch(c, p.CK, p.nchunks, &straddle, &whole2);
+    const int f[] = {1, type_code(c), c.x16(), c.y16(), p.MT, p.NT, rows16(p), p.CK, p.nchunks, ckeLast, cdiv(ckeLast, 8),
+                     p.colOff, p.NI, p.tilesX, p.tilesY, p.imgGroups, p.nblkN, c.ep.up2 ? 1 : 0, straddle, whole2,
+                     c.KH * c.KW, c.padT, c.padL};
+    static_assert(sizeof(f) / sizeof(f[0]) < SPRK_VARIANT_INTS, "the record fits");
+    for (size_t i = 0; i < sizeof(f) / sizeof(f[0]); ++i) r[1 + i] = f[i];
+}
+
+// conv16_tile_kernel under plan_tile's plan, on the grid launch_tile gives it
+static void describe_tile(const Corr &c, const PlanT &p, int32_t *r) {
+    const int Cin = c.C1 + c.C2, ckeLast = Cin - (p.nchunks - 1) * kTileCK;
+    const int ntiles = p.imgGroups * p.tilesX * p.tilesY, gridX = tile_grid_x(p);
+    int straddle, whole2;
+    source_switch(c, kTileCK, p.nchunks, &straddle, &whole2);
+    // a workgroup's next tile (tile + grid.x, both through the kernel's XCD order over ntiles): in the same image group
+    // for some workgroup (2), in another one for some (4)
+    const int q = ntiles >> 3, rr = ntiles & 7, per = p.tilesX * p.tilesY;
+    auto group_of = [&](int t) {
+        const int xcd = t & 7;
+        return ((xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (t >> 3)) / per;
+    };
+    int walk = 0;
+    for (int t = 0; t + gridX < ntiles && (walk & 6) != 6; ++t) walk |= group_of(t) == group_of(t + gridX) ? 2 : 4;
+    // 16-bit output: the tiles wholly inside the tensor take the LDS-transposed store where Wout % 8 == 0 (ldsEp)
+    const int inside = c.Wout % 8 == 0 ? (c.N / p.NI) * (c.Hout >> p.lgTR) * (c.Wout >> p.lgTC) : 0;
+    const int store = !c.y16() || inside == 0 ? 0 : inside == ntiles ? 2 : 1;
+    const int f[] = {2, type_code(c), c.x16(), c.y16(), p.NT, p.lgTC, p.lgTR, p.NI, p.tilesX, p.tilesY, p.imgGroups, p.nblkN,
+                     p.nchunks, cdiv(ckeLast, 8), p.cshift | c.padL << 4 | c.padT << 8, ntiles, c.ep.up2 ? 1 : 0, gridX,
+                     ntiles / gridX, cdiv(ntiles, gridX), straddle, whole2 | walk, store};
+    static_assert(sizeof(f) / sizeof(f[0]) < SPRK_VARIANT_INTS, "the record fits");
+    for (size_t i = 0; i < sizeof(f) / sizeof(f[0]); ++i) r[1 + i] = f[i];
+}
+
+// conv16_head_kernel in head_shape's shape
+static void describe_head(const Corr &c, int32_t *r) {
+    int cq, ck;
+    head_shape(c, &cq, &ck);
+    const int pxt = 64 * (8 / cq), HW = c.Hin * c.Win, tiles = cdiv(HW, pxt);
+    const int quarters = cdiv(c.Cout, 96);          // output-channel quarters of 96 that store anything (of cq)
+    const int f[] = {3, type_code(c), c.x16(), c.y16(), cq, ck, c.C1 / ck, tiles, HW - (tiles - 1) * pxt, quarters,
+                     c.Cout - (quarters - 1) * 96};
+    for (size_t i = 0; i < sizeof(f) / sizeof(f[0]); ++i) r[1 + i] = f[i];
+}
+
+void conv16_variant(const Corr &c, int32_t *rec) {
+    Plan16 p;
+    PlanT pt;
+    const int which = plan_of(c, &p, &pt);
+    for (int i = 1; i < SPRK_VARIANT_INTS; ++i) rec[i] = 0;
+    if (which == 3) describe_head(c, rec);
+    else if (which == 2) describe_tile(c, pt, rec);
+    else if (which == 1) describe16(c, p, rec);
+}
 
 static int run_tile(const Corr &c, const PlanT &p, const void *x, const void *x2, const float *w, void *y,
                     void *ws, size_t ws_bytes, hipStream_t s) {

@@ -15,5 +15,8 @@ inline bool wgrad16_eligible(const sprk_conv_geom &c) { return wgrad16_ws_bytes(
 int wgrad16_run(const sprk_conv_geom &c, const void *x, const void *x2, const void *gy, float *gw, void *ws,
                 sprk_reduce_item *item, hipStream_t s);
 long wgrad16_launches();
+// rec[1 .. SPRK_VARIANT_INTS - 1] of sprk_conv2d_variant's record for stage SPRK_STAGE_16BIT, which 2 (sprk.h): the
+// kernel that wgrad16_run launches for c and the loops it runs there, from the same plans; rec[0] is the caller's
+void wgrad16_variant(const sprk_conv_geom &c, int32_t *rec);
 
 }  // namespace sprk

@@ -643,6 +643,37 @@ size_t wgrad16_ws_bytes(const sprk_conv_geom &c) {
 
 long wgrad16_launches() { return g_wgrad16_launches.load(); }
 
+// ---- the record of a call: stage SPRK_STAGE_16BIT, which 2, of sprk_conv2d_[last_]variant (sprk.h lists the fields) ---
+// wgrad16_kernel under plan_wg16's plan: workgroup b of a channel block walks the units b, b + parts, ...
+static void describe_wg16(const sprk_conv_geom &c, const PlanW &p, int32_t *r) {
+    const int CinTot = c.C1 + c.C2, blocked = CinTot - p.tail;      // the channels the blocks of kCB hold
+    // a block holds channels of both sources: C1 ends inside it (the tail channel is no block's)
+    const int straddle = (c.C2 > 0 && c.C1 % kCB != 0 && c.C1 < blocked) ? 1 : 0;
+    const int f[] = {1, (c.dtype & SPRK_DT_MASK) == SPRK_DT_BF16 ? 1 : 2, (c.dtype & SPRK_DT_X16) ? 1 : 0, p.MC, p.lgRW,
+                     c.pad_left == 1 ? 1 : 0, p.regX, p.regY, p.seg, p.segLen, p.nUnits, p.parts, p.nBlocks, p.tail,
+                     p.nUnits / p.parts, cdiv(p.nUnits, p.parts), straddle, p.tail ? (c.C2 > 0 ? 2 : 1) : 0, c.pad_top,
+                     c.pad_left, (xcd_on() && p.parts % 8 == 0) ? 1 : 0, cdiv(blocked - (p.nBlocks - 1) * kCB, 16)};
+    static_assert(sizeof(f) / sizeof(f[0]) < SPRK_VARIANT_INTS, "the record fits");
+    for (size_t i = 0; i < sizeof(f) / sizeof(f[0]); ++i) r[1 + i] = f[i];
+}
+
+// wgrad16_1x1_kernel under plan_wg1x1's plan: part b sums the regions b * perPart ... of the N * regPerImg
+static void describe_wg1x1(const sprk_conv_geom &c, const Plan1 &p, int32_t *r) {
+    const int CO = p.wide ? 192 : 96, CI = p.wide ? 192 : 384;
+    const int f[] = {2, (c.dtype & SPRK_DT_MASK) == SPRK_DT_BF16 ? 1 : 2, (c.dtype & SPRK_DT_X16) ? 1 : 0, p.wide, p.coBlocks,
+                     p.ciBlocks, p.parts, p.perPart, p.nRegions - (p.parts - 1) * p.perPart, p.regPerImg,
+                     c.Cout - (p.coBlocks - 1) * CO, c.C1 - (p.ciBlocks - 1) * CI};
+    for (size_t i = 0; i < sizeof(f) / sizeof(f[0]); ++i) r[1 + i] = f[i];
+}
+
+void wgrad16_variant(const sprk_conv_geom &c, int32_t *rec) {
+    PlanW p;
+    Plan1 p1;
+    for (int i = 1; i < SPRK_VARIANT_INTS; ++i) rec[i] = 0;
+    if (plan_wg16(c, &p)) describe_wg16(c, p, rec);
+    else if (plan_wg1x1(c, &p1)) describe_wg1x1(c, p1, rec);
+}
+
 template <typename K, typename A>
 static int launch_wg16(K kernel, dim3 grid, size_t ldsBytes, const A &a, const char *what, hipStream_t s) {
     if (int rc = lds_optin(kernel, ldsBytes, what)) return rc;
