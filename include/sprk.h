@@ -635,6 +635,25 @@ int sprk_ingest_flatten(const float *binned_in, float *binned_out, int by, int b
 int sprk_extract_boxes(const void *raw, int mode, int ny, int nx, const int *xy, int P, int box, int bin, int bg_radius,
                        int flags, float *out, int *status, void *stream);
 
+/* sprk_extract_scale: the same boxes Fourier-cropped to side x side pixels, any 2 <= side <= box <= 1024: out [P, side,
+ * side] = M D M^T, where M [side, box] is the real matrix IDFT_side . crop . DFT_box (spr_pick_amd.extract.crop_matrix:
+ * M[s, b] = (1/box) sum_{k=-h..h} w_k cos(2 pi k (s/side - b/box)), h = side/2, w = 1 except 1/2 at k = +-side/2 for even
+ * side; every row sums to 1, so the mean passes through as with `bin`).  m: fp32 on the device, row stride ldm floats, ldm %
+ * 4 == 0, ldm >= roundup(box, 4), 16-byte aligned, columns box .. roundup(box, 4)-1 exact zeros; rows 0 .. side-1 are read.
+ * Box placement, the inside test (64-bit, status 1, zeros, no sample read) and raw are those of sprk_extract_boxes.
+ * D: integer modes float(x - x[0,0]) (exact), float32 x.  The sums are fp32 fmaf chains in a fixed order, on
+ * v_mfma_f32_16x16x4_f32 (one accumulator per element and stage; data are taken to be finite):
+ *   U[r, j] = chain over c = 0 .. box-1 ascending of D[r, c] * M[j, c], from 0.0f;
+ *   Y[i, j] = chain over r = 0 .. box-1 ascending of M[i, r] * U[r, j], from 0.0f.
+ * flags = 0: out = Y + float(x[0,0]) (one fp32 add) for the integer modes, out = Y for float32; status 0.
+ * SPRK_EXTRACT_NORMALIZE, every mode: background = {(i,j): (i - side/2)^2 + (j - side/2)^2 > bg_radius^2}, n pixels;
+ *   mean = sum_bg Y / n and var = sum_bg (Y - mean)^2 / n in double (a fixed summation order: the same call gives the same
+ *   bytes); out = float((double(Y) - mean) / sqrt(var)); status 2 and all zeros when n == 0 or !(var > 0).
+ * SPRK_EXTRACT_INVERT: out is negated.
+ * P == 0 returns SPRK_OK without a launch.  One launch on `stream`, no workspace, no host synchronisation. */
+int sprk_extract_scale(const void *raw, int mode, int ny, int nx, const int *xy, int P, int box, int side, const float *m,
+                       int ldm, int bg_radius, int flags, float *out, int *status, void *stream);
+
 /* ---- in-library kernel timing (bench.py's roofline leg) --------------------------------
  * sprk_prof_enable(mask): bit k set = every launch of kernel class k is bracketed by HIP events
  * on its own stream (an event pair costs the GPU front end a few microseconds, so the timed

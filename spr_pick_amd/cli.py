@@ -86,8 +86,13 @@ def _check_eval(ns):
 
 
 def _check_extract(ns):
-    from .extract import check_box
-    check_box(ns.box, ns.bin, ns.bg_radius)
+    from .extract import check_box, check_scale
+    if ns.scale is None:
+        check_box(ns.box, ns.bin, ns.bg_radius)
+        return
+    if ns.bin > 1:
+        raise ValueError("--scale and --bin %d exclude one another (binning before the Fourier crop is not implemented)" % ns.bin)
+    check_scale(ns.box, ns.scale, ns.bg_radius)
 
 
 def build_parser():
@@ -158,10 +163,13 @@ def build_parser():
     ex.add_argument("--box", "-b", type=int, required=True, metavar="B", help="box side in raw samples (2..1024, a multiple of --bin)")
     ex.add_argument("--out", "-o", required=True, help="Directory for {name}.mrcs (float32 stacks) and particles.star.")
     ex.add_argument("--bin", type=_bin_factor, default=1, metavar="N", help="bin every box N x N: stacks of side B / N")
+    ex.add_argument("--scale", type=int, metavar="S",
+                    help="Fourier-crop every box to S x S pixels (any 2 <= S <= B; relion_preprocess --scale): no aliasing, "
+                         "no divisibility rule; excludes --bin N > 1")
     ex.add_argument("--picks_bin", type=_bin_factor, default=1, metavar="K",
                     help="the pick tables are in the frame of `joint eval --bin K` ({name}_scores.txt); default 1: raw samples")
     ex.add_argument("--bg_radius", type=int, metavar="R",
-                    help="background = output pixels farther than R from the box centre (default 3/8 of B / N)")
+                    help="background = output pixels farther than R from the box centre (default 3/8 of B / N, or of S)")
     ex.add_argument("--threshold", type=float, metavar="S", help="keep picks with score > S (default: all)")
     ex.add_argument("--invert", action="store_true", help="invert the contrast")
     ex.add_argument("--no_norm", action="store_true", help="block means only, no background normalisation")
@@ -236,7 +244,8 @@ def run_extract(args):
     from . import extract
     counts = extract.extract_dataset(args["dataset"], args["picks"], args["out"], args["box"], bin=args["bin"],
                                      picks_bin=args["picks_bin"], threshold=args.get("threshold"),
-                                     bg_radius=args.get("bg_radius"), normalize=not args["no_norm"], invert=args["invert"])
+                                     bg_radius=args.get("bg_radius"), normalize=not args["no_norm"], invert=args["invert"],
+                                     scale=args.get("scale"))
     print(json.dumps({"particles": sum(c["written"] for c in counts.values()), "micrographs": counts}))
     return counts
 

@@ -237,7 +237,334 @@ int launch_extract(const void *raw, int ny, int nx, const int *xy, int P, int B,
     return sprk::check_launch("extract_boxes");
 }
 
+// ---- Fourier-cropped boxes: sprk_extract_scale ---------------------------------------------------------------------------
+// Y = M D M^T per particle, M [S, B] the Dirichlet-kernel resampler of extract.crop_matrix (IDFT_S . crop . DFT_B), D the
+// B x B box (integer modes: minus its first sample, exact in fp32), as two fp32 GEMMs on v_mfma_f32_16x16x4_f32:
+//   U[r, j] = fmaf chain over c = 0 .. B-1 ascending of D[r, c] * M[j, c], from 0.0f;
+//   Y[i, j] = fmaf chain over r = 0 .. B-1 ascending of M[i, r] * U[r, j], from 0.0f;
+// one accumulator per output element and stage, K never split: the MFMA adds its four k in ascending order into the
+// accumulator it is given, one rounding per product, so the bytes are those of the two chains (tests/extract_scale_model.py).
+// Operands past the box (K padded to a multiple of 4, rows to a multiple of 16) are zeros formed in registers, never
+// memory outside the box, and fma(0, d, acc) = acc.
+//
+// One workgroup per particle.  The output columns are cut into strips of 16*TN; per strip, stage 1 leaves U[:, strip] in
+// LDS and stage 2 multiplies it by M.  Both stages walk blocks of kRows output rows, one 16-row tile per wave with its TN
+// accumulators in registers over the whole K loop, and take their operands in chunks of kKC columns through LDS: the A
+// operand (stage 1: samples by element loads of their own type, converted once; stage 2: rows of M) and, in stage 1, the
+// strip's rows of M.  The next two chunks are fetched into registers before the current one is multiplied.  A staged row is
+// kKC + 2 floats long: lane (row, k) of a fragment read then sits on bank 2*row + k, 32 different banks per half wave.
+// U rows are 16*TN floats; when that is a multiple of 32, odd rows swap their 16-column halves, so that the two k rows a
+// half wave reads land on different banks.
+// Not normalised: the epilogue of stage 2 adds the anchor and stores.  Normalised: it stores Y, and after a workgroup
+// barrier the workgroup reads its own Y back (L2) for the two double sums (block_sum: a fixed order) and the final store.
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+constexpr int kKC = 64;                          // columns of K staged per chunk
+constexpr int kLd = kKC + 2;                     // floats per staged row
+constexpr int kRows = 16 * kWaves;               // output rows per row block
+constexpr int kMaxTN = 4;                        // 16-column tiles per strip and wave: at most four accumulators
+constexpr int kStripBytes = 64 * 1024;           // U[:, strip] in LDS: the strip narrows until roundup(B, 16) * 16*TN * 4 fits
+constexpr int kDPerThread = kRows * kKC / kThreads;        // 16 samples of a chunk per thread
+constexpr int kMPerThread = kRows * kKC / 4 / kThreads;    // 4 float4 of 64 rows of M per thread
+
+__host__ __device__ constexpr size_t scale_lds_bytes(int B, int TN) {
+    return kScratchBytes + sizeof(float) * ((size_t)kRows * kLd + (size_t)16 * TN * kLd + (size_t)((B + 15) & ~15) * 16 * TN);
+}
+
+template <typename T, int TN>
+__global__ __launch_bounds__(kThreads) void extract_scale_kernel(const T *__restrict__ raw, int ny, int nx,
+                                                                 const int *__restrict__ xy, int B, int S,
+                                                                 const float *__restrict__ m, int ldm, float inv_s, long R2,
+                                                                 int flags, float *__restrict__ out, int *__restrict__ status) {
+    constexpr bool kFloat = std::is_same<T, float>::value;
+    constexpr int W = 16 * TN;
+    constexpr int kSwizzle = (W % 32 == 0) ? 16 : 0;
+    extern __shared__ __align__(16) unsigned char lds[];
+    float *As = reinterpret_cast<float *>(lds + kScratchBytes);        // [kRows][kLd]
+    float *Ms = As + kRows * kLd;                                      // [W][kLd]
+    float *U = Ms + W * kLd;                                           // [roundup(B, 16)][W]
+    const int p = blockIdx.x, npix = S * S, c = S / 2;
+    const bool invert = flags & SPRK_EXTRACT_INVERT, normalize = flags & SPRK_EXTRACT_NORMALIZE;
+    float *o = out + (long)p * npix;
+    const long x0 = (long)xy[2 * p] - B / 2, y0 = (long)xy[2 * p + 1] - B / 2;
+    if (x0 < 0 || y0 < 0 || x0 + B > nx || y0 + B > ny) {      // before any sample is addressed
+        zero_box(o, npix, status + p, 1);
+        return;
+    }
+    const T *origin = raw + y0 * nx + x0;                      // samples read: origin[r*nx + q], 0 <= r, q < B
+    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
+    const int Bp4 = (B + 3) & ~3, Bp16 = (B + 15) & ~15, Sp16 = (S + 15) & ~15;
+    const T first = origin[0];                                 // every lane the same address: a broadcast
+    const float anchor = kFloat ? 0.0f : (float)first;
+
+    // the chunk of D at rows r0 .., columns c0 ..: thread t holds elements t, t + kThreads, ... of the [kRows][kKC] chunk
+    // (a wave reads 64 adjacent samples of one row); positions past the box hold the anchor, whose D is 0
+    auto fetch_d = [&](T (&v)[kDPerThread], int r0, int c0) {
+#pragma unroll
+        for (int u = 0; u < kDPerThread; ++u) {
+            const int e = tid + u * kThreads, r = r0 + (e >> 6), q = c0 + (e & 63);
+            v[u] = (r < B && q < B) ? origin[(long)r * nx + q] : (kFloat ? (T)0 : first);
+        }
+    };
+    auto stage_d = [&](const T (&v)[kDPerThread]) {
+#pragma unroll
+        for (int u = 0; u < kDPerThread; ++u) {
+            const int e = tid + u * kThreads;
+            float d;
+            if constexpr (kFloat) d = v[u];
+            else d = (float)((int)v[u] - (int)first);          // |difference| < 2^17: exact
+            As[(e >> 6) * kLd + (e & 63)] = d;
+        }
+    };
+    // rows j0 .. j0+rows-1 of M, columns c0 .. c0+kKC-1, as float4 (m and ldm are 16-byte aligned); rows past S and
+    // columns past roundup(B, 4) are zeros and are not read
+    auto fetch_m = [&](float4 *v, int n4, int rows, int j0, int c0) {
+#pragma unroll
+        for (int u = 0; u < n4; ++u) {
+            const int e = tid + u * kThreads, j = j0 + (e >> 4), q = c0 + (e & 15) * 4;
+            v[u] = (e < rows * 16 && j < S && q < Bp4) ? *reinterpret_cast<const float4 *>(m + (long)j * ldm + q)
+                                                      : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    };
+    auto stage_m = [&](const float4 *v, int n4, int rows, float *dst) {
+#pragma unroll
+        for (int u = 0; u < n4; ++u) {
+            const int e = tid + u * kThreads;
+            if (e < rows * 16) {
+                float *d = dst + (e >> 4) * kLd + (e & 15) * 4;            // 8-byte aligned: kLd is even
+                *reinterpret_cast<float2 *>(d) = make_float2(v[u].x, v[u].y);
+                *reinterpret_cast<float2 *>(d + 2) = make_float2(v[u].z, v[u].w);
+            }
+        }
+    };
+    auto u_at = [&](int r, int j) -> float & { return U[r * W + (j ^ ((r & 1) ? kSwizzle : 0))]; };
+
+    for (int j0 = 0; j0 < Sp16; j0 += W) {
+        // stage 1: U[:, j0 .. j0+W-1]
+        for (int r0 = 0; r0 < Bp16; r0 += kRows) {
+            const bool active = r0 + wave * 16 < Bp16;         // wave-uniform
+            f32x4 acc[TN];
+#pragma unroll
+            for (int t = 0; t < TN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            // two chunks are in flight: the samples come from HBM (every chunk is 64 rows of one cache line each), and
+            // one chunk's MFMAs are shorter than that round trip
+            T dv[2][kDPerThread];
+            float4 mv[2][TN];
+            fetch_d(dv[0], r0, 0);
+            fetch_m(mv[0], TN, W, j0, 0);
+            if (kKC < Bp4) {
+                fetch_d(dv[1], r0, kKC);
+                fetch_m(mv[1], TN, W, j0, kKC);
+            }
+            auto chunk = [&](T (&d)[kDPerThread], float4 (&mm)[TN], int c0) {
+                __syncthreads();                               // the chunk before this one has been multiplied
+                stage_d(d);
+                stage_m(mm, TN, W, Ms);
+                __syncthreads();
+                if (c0 + 2 * kKC < Bp4) {
+                    fetch_d(d, r0, c0 + 2 * kKC);
+                    fetch_m(mm, TN, W, j0, c0 + 2 * kKC);
+                }
+                if (active) {
+                    const int ks = min(kKC, Bp4 - c0);
+                    const float *ap = As + (wave * 16 + lr) * kLd + lk, *bp = Ms + lr * kLd + lk;
+                    auto step = [&](int k) {
+                        const float a = ap[k];
+#pragma unroll
+                        for (int t = 0; t < TN; ++t)
+                            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[t * 16 * kLd + k], acc[t], 0, 0, 0);
+                    };
+                    if (ks == kKC) {                           // a whole chunk: unrolled, its LDS reads run ahead
+#pragma unroll
+                        for (int k = 0; k < kKC; k += 4) step(k);
+                    } else {
+                        for (int k = 0; k < ks; k += 4) step(k);
+                    }
+                }
+            };
+            for (int c0 = 0; c0 < Bp4; c0 += 2 * kKC) {
+                chunk(dv[0], mv[0], c0);
+                if (c0 + kKC < Bp4) chunk(dv[1], mv[1], c0 + kKC);
+            }
+            if (active) {
+#pragma unroll
+                for (int t = 0; t < TN; ++t)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) u_at(r0 + wave * 16 + lk * 4 + g, t * 16 + lr) = acc[t][g];
+            }
+        }
+        // stage 2: Y[:, j0 .. j0+W-1] = M . U
+        for (int i0 = 0; i0 < Sp16; i0 += kRows) {
+            const bool active = i0 + wave * 16 < Sp16;
+            f32x4 acc[TN];
+#pragma unroll
+            for (int t = 0; t < TN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            float4 av[2][kMPerThread];
+            fetch_m(av[0], kMPerThread, kRows, i0, 0);
+            if (kKC < Bp4) fetch_m(av[1], kMPerThread, kRows, i0, kKC);
+            auto chunk = [&](float4 (&a4)[kMPerThread], int c0) {
+                __syncthreads();                               // and, the first time, every wave's rows of U are written
+                stage_m(a4, kMPerThread, kRows, As);
+                __syncthreads();
+                if (c0 + 2 * kKC < Bp4) fetch_m(a4, kMPerThread, kRows, i0, c0 + 2 * kKC);
+                if (active) {
+                    const int ks = min(kKC, Bp4 - c0);
+                    const float *ap = As + (wave * 16 + lr) * kLd + lk;
+                    auto step = [&](int k) {
+                        const float a = ap[k];
+                        const int r = c0 + k + lk;             // < roundup(B, 4): a row of U that stage 1 wrote
+#pragma unroll
+                        for (int t = 0; t < TN; ++t)
+                            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, u_at(r, t * 16 + lr), acc[t], 0, 0, 0);
+                    };
+                    if (ks == kKC) {
+#pragma unroll
+                        for (int k = 0; k < kKC; k += 4) step(k);
+                    } else {
+                        for (int k = 0; k < ks; k += 4) step(k);
+                    }
+                }
+            };
+            for (int c0 = 0; c0 < Bp4; c0 += 2 * kKC) {
+                chunk(av[0], c0);
+                if (c0 + kKC < Bp4) chunk(av[1], c0 + kKC);
+            }
+            if (active) {
+#pragma unroll
+                for (int t = 0; t < TN; ++t)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const int i = i0 + wave * 16 + lk * 4 + g, j = j0 + t * 16 + lr;
+                        if (i < S && j < S) {
+                            float y = acc[t][g];
+                            if (!normalize) {
+                                if constexpr (!kFloat) y = __fadd_rn(y, anchor);
+                                if (invert) y = -y;
+                            }
+                            o[i * S + j] = y;
+                        }
+                    }
+            }
+        }
+    }
+    if (!normalize) {
+        if (tid == 0) status[p] = 0;
+        return;
+    }
+
+    __threadfence_block();
+    __syncthreads();                                           // Y of every wave is in memory: each thread reads its pixels
+    auto is_bg = [&](int e) {
+        const int i = fast_div(e, inv_s), j = e - i * S;       // exact: e < 2^20 (common.h)
+        return (long)((i - c) * (i - c) + (j - c) * (j - c)) > R2;
+    };
+    int n = 0;
+    double s = 0.0;
+    // f(e, Y[e]) for this thread's pixels e = tid, tid + kThreads, ... in ascending order, kUnroll loads in flight (one at
+    // a time, a pass is S*S / kThreads dependent round trips to L2: 48 of them at S = 64 cost more than stage 2)
+    auto for_each_y = [&](auto f) {
+        for (int e0 = tid; e0 < npix; e0 += kUnroll * kThreads) {
+            float v[kUnroll];
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) v[u] = e0 + u * kThreads < npix ? o[e0 + u * kThreads] : 0.0f;
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u)
+                if (e0 + u * kThreads < npix) f(e0 + u * kThreads, v[u]);
+        }
+    };
+    for_each_y([&](int e, float y) {
+        if (is_bg(e)) {
+            s += (double)y;
+            ++n;
+        }
+    });
+    n = block_sum(n, reinterpret_cast<int *>(lds));
+    if (n == 0) {
+        zero_box(o, npix, status + p, 2);
+        return;
+    }
+    const double mean = block_sum(s, reinterpret_cast<double *>(lds)) / (double)n;
+    double q = 0.0;
+    for_each_y([&](int e, float y) {
+        if (is_bg(e)) {
+            const double t = (double)y - mean;
+            q += t * t;
+        }
+    });
+    const double var = block_sum(q, reinterpret_cast<double *>(lds)) / (double)n;
+    if (!(var > 0.0)) {                                        // the same bits in every lane: a uniform branch
+        zero_box(o, npix, status + p, 2);
+        return;
+    }
+    const double sd = sqrt(var);
+    for_each_y([&](int e, float y) {
+        const float r = (float)(((double)y - mean) / sd);
+        o[e] = invert ? -r : r;
+    });
+    if (tid == 0) status[p] = 0;
+}
+
+// the strip width in 16-column tiles: the widest that keeps U[:, strip] within kStripBytes, then evened out over the strips
+inline int scale_strip_tiles(int B, int S) {
+    const int tiles = (S + 15) / 16, Bp16 = (B + 15) & ~15;
+    static const size_t budget = (size_t)sprk::knob_env("SPRK_SCALE_STRIP_KB", kStripBytes / 1024) * 1024;   // DIAG builds: 16..128
+    int tn = tiles < kMaxTN ? tiles : kMaxTN;
+    while (tn > 1 && (size_t)Bp16 * 16 * tn * sizeof(float) > budget) --tn;
+    const int strips = (tiles + tn - 1) / tn;
+    return (tiles + strips - 1) / strips;
+}
+
+template <typename T, int TN>
+int launch_scale_tn(const void *raw, int ny, int nx, const int *xy, int P, int B, int S, const float *m, int ldm, int R,
+                    int flags, float *out, int *status, hipStream_t s) {
+    const size_t lds = scale_lds_bytes(B, TN);
+    if (int rc = sprk::lds_optin(extract_scale_kernel<T, TN>, lds, "extract_scale")) return rc;
+    hipLaunchKernelGGL((extract_scale_kernel<T, TN>), dim3(P), dim3(kThreads), lds, s, (const T *)raw, ny, nx, xy, B, S, m,
+                       ldm, 1.0f / (float)S, (long)R * R, flags, out, status);
+    return sprk::check_launch("extract_scale");
+}
+
+template <typename T>
+int launch_scale(const void *raw, int ny, int nx, const int *xy, int P, int B, int S, const float *m, int ldm, int R,
+                 int flags, float *out, int *status, hipStream_t s) {
+    switch (scale_strip_tiles(B, S)) {
+        case 1: return launch_scale_tn<T, 1>(raw, ny, nx, xy, P, B, S, m, ldm, R, flags, out, status, s);
+        case 2: return launch_scale_tn<T, 2>(raw, ny, nx, xy, P, B, S, m, ldm, R, flags, out, status, s);
+        case 3: return launch_scale_tn<T, 3>(raw, ny, nx, xy, P, B, S, m, ldm, R, flags, out, status, s);
+        default: return launch_scale_tn<T, 4>(raw, ny, nx, xy, P, B, S, m, ldm, R, flags, out, status, s);
+    }
+}
+
 }  // namespace
+
+extern "C" int sprk_extract_scale(const void *raw, int mode, int ny, int nx, const int *xy, int P, int box, int side,
+                                  const float *m, int ldm, int bg_radius, int flags, float *out, int *status, void *stream) {
+    SPRK_REQUIRE(mode == SPRK_MRC_INT8 || mode == SPRK_MRC_INT16 || mode == SPRK_MRC_FLOAT32 || mode == SPRK_MRC_UINT16,
+                 "extract_scale: unsupported MRC mode %d (0, 1, 2 and 6 are)", mode);
+    SPRK_REQUIRE(box >= 2 && box <= kMaxBox && side >= 2 && side <= box,
+                 "extract_scale: box %d with output side %d (2 <= side <= box <= %d)", box, side, kMaxBox);
+    SPRK_REQUIRE(ldm >= ((box + 3) & ~3) && ldm % 4 == 0,
+                 "extract_scale: row stride ldm %d of the matrix (a multiple of 4, at least roundup(box, 4) = %d)", ldm,
+                 (box + 3) & ~3);
+    SPRK_REQUIRE(bg_radius >= 0, "extract_scale: background radius %d (>= 0)", bg_radius);
+    SPRK_REQUIRE((flags & ~(SPRK_EXTRACT_NORMALIZE | SPRK_EXTRACT_INVERT)) == 0, "extract_scale: unknown flags 0x%x", flags);
+    SPRK_REQUIRE(ny > 0 && nx > 0 && (long)ny * nx < (1L << 31), "extract_scale: bad image size %dx%d", ny, nx);
+    SPRK_REQUIRE(P >= 0, "extract_scale: %d particles", P);
+    if (P == 0) return SPRK_OK;
+    SPRK_REQUIRE(raw && xy && m && out && status, "extract_scale: null pointer");
+    SPRK_REQUIRE(((uintptr_t)raw & 15) == 0, "extract_scale: the sample buffer must start 16-byte aligned");
+    SPRK_REQUIRE(((uintptr_t)m & 15) == 0, "extract_scale: the matrix must start 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    switch (mode) {
+        case SPRK_MRC_INT8:
+            return launch_scale<int8_t>(raw, ny, nx, xy, P, box, side, m, ldm, bg_radius, flags, out, status, s);
+        case SPRK_MRC_INT16:
+            return launch_scale<int16_t>(raw, ny, nx, xy, P, box, side, m, ldm, bg_radius, flags, out, status, s);
+        case SPRK_MRC_FLOAT32:
+            return launch_scale<float>(raw, ny, nx, xy, P, box, side, m, ldm, bg_radius, flags, out, status, s);
+        default:
+            return launch_scale<uint16_t>(raw, ny, nx, xy, P, box, side, m, ldm, bg_radius, flags, out, status, s);
+    }
+}
 
 extern "C" int sprk_extract_boxes(const void *raw, int mode, int ny, int nx, const int *xy, int P, int box, int bin,
                                   int bg_radius, int flags, float *out, int *status, void *stream) {

@@ -3,7 +3,8 @@ stacks plus one ``particles.star`` out — the step between ``joint eval`` and 2
 ``relion_preprocess`` and without decoding a micrograph on the host a second time.
 
 A file's sample block is uploaded once by ``ingest.read_raw``; csrc/extract.hip (``torch.ops.sprk.extract_boxes``) cuts
-every box of that micrograph in one launch: box x box raw samples around each centre, binned N x N, normalised to zero
+every box of that micrograph in one launch: box x box raw samples around each centre, binned N x N — or, with ``scale``,
+Fourier-cropped to any S x S (``torch.ops.sprk.extract_scale``: M D M^T with the matrix of ``crop_matrix``) — normalised to zero
 mean and unit variance of the background outside ``bg_radius`` (in output pixels), optionally contrast-inverted.  Boxes
 that are not entirely inside the image (status 1) and boxes with no or a flat background (status 2) come back as zeros
 and are not written.
@@ -41,11 +42,68 @@ def check_box(box, bin=1, bg_radius=None):
         raise ValueError(str(e)) from None
 
 
-def extract_particles(path_or_raw, xy, box, bin=1, bg_radius=None, normalize=True, invert=False, device="cuda"):
+def check_scale(box, scale, bg_radius=None):
+    """-> (S, bg_radius) or ValueError: 2 <= scale <= box <= 1024, bg_radius >= 0 (default 3/8 of the output side)."""
+    if not isinstance(box, (int, np.integer)) or not isinstance(scale, (int, np.integer)):
+        raise ValueError("box and scale must be integers, got %r and %r" % (box, scale))
+    if bg_radius is None:
+        bg_radius = default_bg_radius(scale)
+    try:
+        return torch_ops.extract_scale_side(int(box), int(scale), int(bg_radius)), int(bg_radius)
+    except _lib.SprkError as e:
+        raise ValueError(str(e)) from None
+
+
+def crop_matrix64(B, S):
+    """The Fourier crop of B samples to S as a real [S, B] matrix in float64: IDFT_S . crop . DFT_B scaled by S / B,
+    M[s, b] = (1/B) sum_{k=-h..h} w_k cos(2 pi k (s/S - b/B)), h = S // 2, w_k = 1 except that for even S the two ends
+    k = +-S/2 weigh 1/2 each (the Nyquist row of the output is shared by both signs).  Every row sums to 1.  The phase
+    k (sB - bS) is reduced mod SB in integers before the cosine, and the sum over k runs in one [S, B] array (the two
+    signs of k together: the cosine is even).  S == B is the identity and is returned as such."""
+    B, S = int(B), int(S)
+    if not 2 <= S <= B:
+        raise ValueError("crop_matrix: 2 <= S <= B, got B = %d, S = %d" % (B, S))
+    if S == B:
+        return np.eye(B)
+    h, period = S // 2, S * B
+    base = np.arange(S, dtype=np.int64)[:, None] * B - np.arange(B, dtype=np.int64)[None, :] * S
+    acc = np.ones((S, B), dtype=np.float64)                      # k = 0
+    for k in range(1, h + 1):
+        w = 1.0 if (S % 2 or k < h) else 0.5                     # both signs: 2 w cos
+        acc += (2.0 * w) * np.cos((2.0 * np.pi / period) * ((k * base) % period))
+    return acc / B
+
+
+_matrices = {}
+
+
+def crop_matrix(B, S, device=None):
+    """``crop_matrix64`` rounded to float32.  Without a device: the [S, B] array.  With one: the operand of
+    ``torch.ops.sprk.extract_scale``, a contiguous tensor [roundup(S, 16), roundup(B, 4)] on that device whose added
+    rows and columns are exact zeros, built once per (B, S, device)."""
+    B, S = int(B), int(S)
+    key = (B, S, None if device is None else str(torch.device(device)))
+    if key not in _matrices:
+        if device is None:
+            _matrices[key] = crop_matrix64(B, S).astype(np.float32)
+        else:
+            padded = np.zeros((-(-S // 16) * 16, -(-B // 4) * 4), dtype=np.float32)
+            padded[:S, :B] = crop_matrix(B, S)
+            _matrices[key] = torch.from_numpy(padded).to(device)
+    return _matrices[key]
+
+
+def extract_particles(path_or_raw, xy, box, bin=1, bg_radius=None, normalize=True, invert=False, device="cuda", scale=None):
     """path_or_raw: an MRC file, or the ``(raw, header)`` pair ``ingest.read_raw`` returns for one.  xy: [P, 2] integer
-    (x, y) centres in raw samples, array or int32 CUDA tensor.
+    (x, y) centres in raw samples, array or int32 CUDA tensor.  scale = S: boxes Fourier-cropped to S x S instead of
+    binned (``bin`` must be 1), b = S.
     -> (particles float32 CUDA [P, b, b], status int32 CUDA [P]); nothing is synchronised."""
-    b, bg_radius = check_box(box, bin, bg_radius)
+    if scale is not None:
+        if bin != 1:
+            raise ValueError("scale and bin > 1 exclude one another")
+        b, bg_radius = check_scale(box, scale, bg_radius)
+    else:
+        b, bg_radius = check_box(box, bin, bg_radius)
     if isinstance(path_or_raw, (str, os.PathLike)):
         raw, header = ingest.read_raw(os.fspath(path_or_raw), device)
     else:
@@ -59,6 +117,9 @@ def extract_particles(path_or_raw, xy, box, bin=1, bg_radius=None, normalize=Tru
         info = np.iinfo(np.int32)                                # far outside either way: status 1
         xy = torch.from_numpy(np.clip(xy, info.min, info.max).astype(np.int32))
     xy = xy.to(raw.device)
+    if scale is not None:
+        return torch.ops.sprk.extract_scale(raw, header.mode, header.ny, header.nx, xy, int(box), b,
+                                            crop_matrix(box, b, raw.device), bg_radius, bool(normalize), bool(invert))
     return torch.ops.sprk.extract_boxes(raw, header.mode, header.ny, header.nx, xy, int(box), int(bin), bg_radius,
                                         bool(normalize), bool(invert))
 
@@ -80,7 +141,16 @@ def _extract_file(path, xy, box, bin, bg_radius, normalize, invert, device):
     """The device half of ``extract_dataset`` for one micrograph: one read, one upload, one launch.
     -> (float32 array [K, b, b] of the status-0 particles in pick order, through pinned memory — a view of a buffer
     the next call overwrites; status array [P])."""
-    out, status = extract_particles(path, xy, box, bin, bg_radius, normalize, invert, device)
+    return _to_host(*extract_particles(path, xy, box, bin, bg_radius, normalize, invert, device))
+
+
+def _extract_file_scaled(path, xy, box, scale, bg_radius, normalize, invert, device):
+    """``_extract_file`` with the boxes Fourier-cropped to scale x scale."""
+    return _to_host(*extract_particles(path, xy, box, 1, bg_radius, normalize, invert, device, scale=scale))
+
+
+def _to_host(out, status):
+    """-> (the status-0 particles as a float32 array through pinned memory, status array)"""
     status = status.cpu().numpy()                                # waits for the launch
     keep = np.flatnonzero(status == OK)
     if len(keep) < len(status):
@@ -123,14 +193,20 @@ def read_pick_tables(picks, names, picks_bin=1):
 
 
 def extract_dataset(dataset, picks, out_dir, box, bin=1, picks_bin=1, threshold=None, bg_radius=None, normalize=True,
-                    invert=False, device="cuda"):
+                    invert=False, device="cuda", scale=None):
     """``joint extract``: for every micrograph of the table / directory ``dataset`` that has a pick table, the picks
     with score > ``threshold`` (all of them when None), mapped from the ``picks_bin`` frame to raw samples, extracted in
     one launch and written as the float32 stack ``out_dir/{name}.mrcs`` (status-0 particles only, pick order); at the
     end ``out_dir/particles.star`` with one row per written particle.  A micrograph without a surviving particle writes
-    no stack; micrographs without a pick table are skipped with a warning.
+    no stack; micrographs without a pick table are skipped with a warning.  scale = S: stacks of side S by Fourier
+    cropping (``bin`` must be 1); the coordinates of ``particles.star`` stay in raw samples either way.
     -> {name: {"written", "outside", "flat"}} for the micrographs that had a table."""
-    b, bg_radius = check_box(box, bin, bg_radius)
+    if scale is not None:
+        if bin != 1:
+            raise ValueError("scale and bin > 1 exclude one another")
+        b, bg_radius = check_scale(box, scale, bg_radius)
+    else:
+        b, bg_radius = check_box(box, bin, bg_radius)
     picks_bin = ingest.check_bin(picks_bin)
     rows = micrograph_io.read_image_table(dataset)
     if not rows:
@@ -156,7 +232,10 @@ def extract_dataset(dataset, picks, out_dir, box, bin=1, picks_bin=1, threshold=
         counts[name] = {"written": 0, "outside": 0, "flat": 0}
         if not len(xy):
             continue
-        particles, status = _extract_file(path, xy, box, bin, bg_radius, normalize, invert, device)
+        if scale is not None:
+            particles, status = _extract_file_scaled(path, xy, box, b, bg_radius, normalize, invert, device)
+        else:
+            particles, status = _extract_file(path, xy, box, bin, bg_radius, normalize, invert, device)
         ok = np.flatnonzero(status == OK)
         counts[name] = {"written": len(ok), "outside": int((status == OUTSIDE).sum()), "flat": int((status == FLAT).sum())}
         if not len(ok):

@@ -749,6 +749,59 @@ _register("extract_boxes", "(Tensor raw, int mode, int ny, int nx, Tensor xy, in
                            "bool normalize, bool invert) -> (Tensor, Tensor)", _extract_boxes, _extract_boxes_fake)
 
 
+def extract_scale_side(box, side, bg_radius=0):
+    """Argument check shared by the operator, extract.py and the command line -> side, the output side."""
+    if not (2 <= side <= box <= EXTRACT_MAX_BOX):
+        raise _lib.SprkError("extract_scale: box %d with output side %d (2 <= side <= box <= %d)"
+                             % (box, side, EXTRACT_MAX_BOX))
+    if bg_radius < 0:
+        raise _lib.SprkError("extract_scale: background radius %d (>= 0)" % bg_radius)
+    return side
+
+
+def _extract_scale_shapes(raw, mode, ny, nx, xy, box, side, m, bg_radius):
+    if mode not in MRC_ITEMSIZE:
+        raise _lib.SprkError("extract_scale: unsupported MRC mode %d" % mode)
+    extract_scale_side(box, side, bg_radius)
+    if ny < 1 or nx < 1 or ny * nx >= 1 << 31:
+        raise _lib.SprkError("extract_scale: bad image size %dx%d" % (ny, nx))
+    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
+        raise _lib.SprkError("extract_scale: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
+                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+    if xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or xy.device != raw.device:
+        raise _lib.SprkError("extract_scale: xy must be an int32 tensor [P, 2] on %s, got %s %s on %s"
+                             % (raw.device, xy.dtype, tuple(xy.shape), xy.device))
+    rows, cols = -(-side // 16) * 16, -(-box // 4) * 4
+    if m.dtype != torch.float32 or tuple(m.shape) != (rows, cols) or m.device != raw.device:
+        raise _lib.SprkError("extract_scale: m must be the float32 matrix of extract.crop_matrix(%d, %d), [%d, %d] on %s, "
+                             "got %s %s on %s" % (box, side, rows, cols, raw.device, m.dtype, tuple(m.shape), m.device))
+    return xy.shape[0]
+
+
+def _extract_scale(raw, mode, ny, nx, xy, box, side, m, bg_radius, normalize, invert):
+    """-> (out float32 [P, side, side], status int32 [P]: 0 ok, 1 outside the image, 2 no or flat background)."""
+    P = _extract_scale_shapes(raw, mode, ny, nx, xy, box, side, m, bg_radius)
+    if not raw.is_contiguous() or not m.is_contiguous():
+        raise _lib.SprkError("extract_scale: raw and m must be contiguous")
+    xy = xy.contiguous()
+    out = _f32(raw, (P, side, side))
+    status = torch.empty((P,), dtype=torch.int32, device=raw.device)
+    flags = (EXTRACT_NORMALIZE if normalize else 0) | (EXTRACT_INVERT if invert else 0)
+    check(_lib.lib().sprk_extract_scale(_p(raw), int(mode), int(ny), int(nx), _p(xy), P, int(box), int(side), _p(m),
+                                        int(m.shape[1]), int(bg_radius), flags, _p(out), _p(status), _stream(raw)),
+          "sprk_extract_scale")
+    return out, status
+
+
+def _extract_scale_fake(raw, mode, ny, nx, xy, box, side, m, bg_radius, normalize, invert):
+    P = _extract_scale_shapes(raw, mode, ny, nx, xy, box, side, m, bg_radius)
+    return raw.new_empty((P, side, side), dtype=torch.float32), raw.new_empty((P,), dtype=torch.int32)
+
+
+_register("extract_scale", "(Tensor raw, int mode, int ny, int nx, Tensor xy, int box, int side, Tensor m, int bg_radius, "
+                           "bool normalize, bool invert) -> (Tensor, Tensor)", _extract_scale, _extract_scale_fake)
+
+
 def registered():
     """Names of the operators under torch.ops.sprk (tests)."""
     return tuple(_NAMES)
