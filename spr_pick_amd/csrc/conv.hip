@@ -21,6 +21,7 @@
 #include "gemm1x1.h"
 #include "mask1x1.h"
 #include "wgrad16.h"
+#include "wgrad1x1.h"
 #include "wino.h"
 #include "wprep_dev.h"
 
@@ -1971,6 +1972,20 @@ static size_t wgrad_ws_bytes(const sprk_conv_geom &g) {
 
 size_t sprk_conv2d_bwd_weight_ws_bytes(const sprk_conv_geom *g) { return g ? wgrad_ws_bytes(*g) : 0; }
 
+// Stage 7: may the call of layer g, planned as p and routed to conv_wgrad_mfma_kernel as v, run on wgrad1x1_kernel
+// (wgrad1x1.hip) instead?  An fp32 1x1 call in the row form (MODE 1: x and gy 16-byte aligned, 32-bit offsets) on the plan
+// of the wide heads (3 k-tiles per wave, blocks of 6 output tiles), over planes whose 64-pixel tiles are 64 consecutive
+// floats of one plane.  The one predicate of wg_route, and so of the dispatcher and of sprk_conv2d_variant.
+static bool wgrad1x1_takes(const sprk_conv_geom *g, const WgPlan &p, const WgVariant &v) {
+    const int W = g->Wout, H = g->Hout;
+    const bool rows64 = W % 64 == 0 || ((W == 4 || W == 8 || W == 16 || W == 32) && H % (64 / W) == 0 && H * W >= 64);
+    return sprk::g_wgrad1x1_on.load(std::memory_order_relaxed) && (g->dtype & SPRK_DT_MASK) == SPRK_DT_F32 &&
+           !(g->dtype & (SPRK_DT_X16 | SPRK_DT_Y16)) && !naive_of(g) && g->KH == 1 && g->KW == 1 && g->stride == 1 &&
+           g->pad_top == 0 && g->pad_left == 0 && g->C2 == 0 && !g->up1 && g->Hin == g->Hout && g->Win == g->Wout &&
+           v.stage == SPRK_STAGE_MFMA && p.xrow && v.MODE == 1 && p.IT == 3 && p.NT == 6 && p.CKW <= sprk::kWgrad1x1Rows &&
+           rows64 && (long)sprk::kWgrad1x1Rows * H * W * 4 < (1L << 31);
+}
+
 // Which stage of wgrad_dispatch takes the call, by the stages' own predicates in the dispatcher's order, and for the
 // MFMA stage the plan and the kernel variant: the twin of fwd_route.
 static WgVariant wg_route(const sprk_conv_geom *g, const void *x, const void *x2, const void *gy, WgPlan *p) {
@@ -1990,6 +2005,7 @@ static WgVariant wg_route(const sprk_conv_geom *g, const void *x, const void *x2
         bool refused;
         v = wg_variant(g, *p, x, x2, gy, &refused);
         v.stage = refused ? SPRK_STAGE_REFUSED : SPRK_STAGE_MFMA;
+        if (wgrad1x1_takes(g, *p, v)) v.stage = SPRK_STAGE_WGRAD1X1;
     }
     return v;
 }
@@ -1998,7 +2014,8 @@ static WgVariant wg_route(const sprk_conv_geom *g, const void *x, const void *x2
 // the common description, and a kernel family is a predicate, a workspace size and a run function over it (DESIGN.md,
 // "The convolution dispatcher").  item == nullptr: finish the sum over the partial buffers now; otherwise describe it in
 // *item (sprk.h).  The stages, in order:
-//   direct kernel (SPRK_DT_NAIVE) -> 16-bit operands -> storage guard -> Winograd -> MFMA (-> direct: no plan fits LDS)
+//   direct kernel (SPRK_DT_NAIVE) -> 16-bit operands -> storage guard -> Winograd -> MFMA (-> direct: no plan fits LDS),
+//   whose wide 1x1 row-form calls leave for wgrad1x1_kernel on the same plan (SPRK_STAGE_WGRAD1X1)
 static int wgrad_dispatch(const float *x, const float *x2, const float *gy, float *gw, const sprk_conv_geom *g, void *ws,
                           size_t ws_bytes, sprk_reduce_item *item, void *stream) {
     const char *who = "conv2d_bwd_weight";
@@ -2032,12 +2049,22 @@ static int wgrad_dispatch(const float *x, const float *x2, const float *gy, floa
     SPRK_REQUIRE(v.stage != SPRK_STAGE_REFUSED,
                  "conv2d_bwd_weight: 1x1 row staging needs 16-byte aligned x / gy and < 2^28-element tiles");
     float *wsf = (float *)ws;
-    WgArgs a;
-    if (int rc = wgrad_args(g, p, v, x, x2, gy, wsf, a)) return rc;
-    sprk::prof_begin(1, sprk::conv_flops(*g), s);
-    if (int rc = launch_wg(a, p, v, s)) return rc;
-    sprk::prof_end(1, s);
-    if (int rc2 = sprk::check_launch("conv_wgrad_mfma")) return rc2;
+    if (v.stage == SPRK_STAGE_WGRAD1X1) {
+        // the same split, slabs and reduction item as the MFMA stage below
+        const sprk::Wgrad1x1Call c{x, gy, wsf + kZeroFloats, g->N, g->C1, g->Cout, p.CoutP, g->Hout * g->Wout,
+                                   p.nTiles, p.tilesPerGroup, p.groups, p.CKW, p.nChunks, p.nblkN};
+        sprk::prof_begin(1, sprk::conv_flops(*g), s);
+        if (int rc = sprk::wgrad1x1_run(c, s)) return rc;
+        sprk::prof_end(1, s);
+        if (int rc2 = sprk::check_launch("wgrad1x1")) return rc2;
+    } else {
+        WgArgs a;
+        if (int rc = wgrad_args(g, p, v, x, x2, gy, wsf, a)) return rc;
+        sprk::prof_begin(1, sprk::conv_flops(*g), s);
+        if (int rc = launch_wg(a, p, v, s)) return rc;
+        sprk::prof_end(1, s);
+        if (int rc2 = sprk::check_launch("conv_wgrad_mfma")) return rc2;
+    }
     const int K = (g->C1 + g->C2) * g->KH * g->KW;
     const sprk_reduce_item it{wsf + kZeroFloats, gw, SPRK_RED_WGRAD, p.groups, 0, K, g->Cout, p.CoutP};
     return sprk::finish_or_defer(it, item, s);
