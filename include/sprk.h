@@ -619,6 +619,28 @@ size_t sprk_ingest_flatten_ws_bytes(int by, int bx, int R);
 int sprk_ingest_flatten(const float *binned_in, float *binned_out, int by, int bx, int R, const float *range_in,
                         float *range_out, void *ws, size_t ws_bytes, void *stream);
 
+/* sprk_ingest_resample (instead of sprk_ingest_bin; `--ftbin F`): the whole micrograph Fourier-cropped to by x bx pixels, any
+ * 2 <= by <= ny <= 16384 and 2 <= bx <= nx <= 16384: out [by,bx] fp32 = My D Mx^T (+ the anchor), where My [by, ny] and
+ * Mx [bx, nx] are the real matrices IDFT_S . crop . DFT_B of spr_pick_amd.ingest.resample_matrix (the operator of
+ * sprk_extract_scale's m, in closed form; every row sums to 1).  Both axes keep their whole extent: output pixel s sits at
+ * input position s*B/S, and the image is taken as periodic (the wrap-around of every Fourier crop; not tapered).
+ * my, mx: fp32 on the device, 16-byte aligned, row strides ldmy / ldmx floats, multiples of 4, at least roundup(ny, 4) /
+ * roundup(nx, 4); rows 0 .. by-1 / 0 .. bx-1 and columns 0 .. roundup(ny, 4)-1 / roundup(nx, 4)-1 are read.  raw as for
+ * sprk_ingest_bin.  D: integer modes float(x - x[0,0]) (exact), float32 x; data are taken to be finite.  The sums are fp32
+ * fmaf chains in a fixed order, on v_mfma_f32_16x16x4_f32, one accumulator per element and stage, K never split (so every
+ * tiling gives the same bits):
+ *   U[r, j] = chain over c = 0 .. nx-1 ascending of D[r, c] * Mx[j, c], from 0.0f   (fp32, in the workspace);
+ *   Y[i, j] = chain over r = 0 .. ny-1 ascending of My[i, r] * U[r, j], from 0.0f.
+ * Every padded K position is a zero formed in registers on both operands: the workspace may hold anything, NaNs included.
+ * out = Y + float(x[0,0]) (one fp32 add) for the integer modes, out = Y for float32; range_out float[2] device: the exact
+ * min and max of out (per-workgroup pairs in the workspace, reduced as sprk_ingest_bin's).
+ * Refused (SPRK_EINVAL, nothing launched): another mode, other sizes, a row stride too small or not a multiple of 4, null
+ * or misaligned pointers (out and ws 16-byte aligned as well); a short workspace: SPRK_EWORKSPACE.
+ * Three launches on `stream`, no host synchronisation, no atomics. */
+size_t sprk_ingest_resample_ws_bytes(int ny, int nx, int by, int bx);
+int sprk_ingest_resample(const void *raw, int mode, int ny, int nx, int by, int bx, const float *my, int ldmy,
+                         const float *mx, int ldmx, float *out, float *range_out, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- particle extraction (`joint extract`) -----------------------------------------------
  * Boxes cut out of ONE raw micrograph (the buffer sprk_ingest_bin takes: [ny,nx] samples of mode 0 / 1 / 2 / 6, 16-byte
  * aligned start), binned, background-normalised and optionally inverted: out [P, b, b] fp32 with b = box / bin, status [P].

@@ -45,6 +45,15 @@ def _bin_factor(text):
     return n
 
 
+def _ftbin(text):
+    """--ftbin F: ingest.check_ftbin of the decimal (or p/q) text, its ValueError as the parser's usage error."""
+    from .ingest import check_ftbin
+    try:
+        return check_ftbin(str(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def _clip(text):
     """--clip LO[,HI]: ingest.parse_clip, its ValueError as the parser's usage error."""
     from .ingest import parse_clip
@@ -79,10 +88,20 @@ class _Parser(argparse.ArgumentParser):
 
 
 def _check_eval(ns):
-    if ns.clip is not None and ns.bin is None:
+    if ns.bin is not None and ns.ftbin is not None:
+        raise ValueError("--bin and --ftbin exclude one another")
+    raw = ns.bin is not None or ns.ftbin is not None
+    if ns.clip is not None and not raw:
         raise ValueError("--clip belongs to the raw-micrograph ingest: give --bin N as well (N = 1 for unbinned files)")
-    if ns.flatten is not None and ns.bin is None:
+    if ns.flatten is not None and not raw:
         raise ValueError("--flatten belongs to the raw-micrograph ingest: give --bin N as well (N = 1 for unbinned files)")
+
+
+def _check_bin(ns):
+    if ns.bin is not None and ns.ftbin is not None:
+        raise ValueError("--bin and --ftbin exclude one another")
+    if ns.bin is None and ns.ftbin is None:
+        raise ValueError("one of the arguments --bin --ftbin is required")
 
 
 def _check_extract(ns):
@@ -132,19 +151,26 @@ def build_parser():
     ev.add_argument("--bin", type=_bin_factor, metavar="N",
                     help="the dataset holds RAW micrographs (MRC mode 0/1/2/6): bin each N x N, normalise and pad it on "
                          "the GPU instead of preparing binned copies; for N > 1 also writes {name}_scores_unbinned.txt")
+    ev.add_argument("--ftbin", type=_ftbin, metavar="F",
+                    help="instead of --bin: Fourier-crop each RAW micrograph by the factor F (any decimal or p/q in 1..64, "
+                         "e.g. 9.64) to round(ny / F) x round(nx / F) pixels on the GPU: no aliasing, no margin dropped, "
+                         "periodic at the edges like newstack -ftreduce; writes {name}_scores_unbinned.txt when the size changes")
     ev.add_argument("--clip", type=_clip, metavar="LO[,HI]",
-                    help="with --bin: clamp each binned micrograph to its LO %% / (100 - HI) %% order statistics before the "
+                    help="with --bin or --ftbin: clamp each binned micrograph to its LO %% / (100 - HI) %% order statistics before the "
                          "min-max normalisation, so that hot pixels and black spots do not set the range (HI = LO when "
                          "omitted; 0 changes nothing)")
     ev.add_argument("--flatten", type=_flatten, metavar="R",
-                    help="with --bin: subtract from each binned micrograph its mean over a (2R+1) x (2R+1) window (R in "
+                    help="with --bin or --ftbin: subtract from each binned micrograph its mean over a (2R+1) x (2R+1) window (R in "
                          "binned pixels, 1..1023) before the min-max normalisation, so that a slow gradient does not take "
                          "the grey levels; with --clip: clip, flatten, clip again")
     ev.check = _check_eval
 
     bn = cmds.add_parser("bin", help="Bin raw micrographs N x N on the GPU (replaces the `newstack -bin N` preparation).")
     bn.add_argument("--dataset", "-d", required=True, help="Table (image_name, path) or directory of raw MRC micrographs.")
-    bn.add_argument("--bin", type=_bin_factor, required=True, metavar="N", help="bin factor (at most 16, SPRK_INGEST_MAX_BIN)")
+    bn.add_argument("--bin", type=_bin_factor, metavar="N", help="bin factor (at most 16, SPRK_INGEST_MAX_BIN)")
+    bn.add_argument("--ftbin", type=_ftbin, metavar="F",
+                    help="instead of --bin: Fourier-crop by the factor F (any decimal or p/q in 1..64) to round(ny / F) x "
+                         "round(nx / F) pixels, as `joint eval --ftbin F` sees the micrographs; one of the two is required")
     bn.add_argument("--out", "-o", required=True, help="Directory for {name}.mrc (float32), images.txt and labels.txt.")
     bn.add_argument("--labels", "-l", help="Particle coordinates of the raw micrographs; written binned to labels.txt.")
     bn.add_argument("--clip", type=_clip, metavar="LO[,HI]",
@@ -153,6 +179,7 @@ def build_parser():
     bn.add_argument("--flatten", type=_flatten, metavar="R",
                     help="write the block means minus their mean over a (2R+1) x (2R+1) window (as `joint eval --bin N "
                          "--flatten R` sees them); with --clip: clip, flatten, clip again")
+    bn.check = _check_bin
 
     ex = cmds.add_parser("extract", help="Cut normalised particle stacks out of raw micrographs on the GPU "
                                          "(replaces the relion_preprocess step after picking).")
@@ -222,7 +249,8 @@ def run_train(args, parser):
 def run_eval(args):
     from .eval import DenoiserEvaluator
     evaluator = DenoiserEvaluator(args["model"], runs_dir=args["runs_dir"], contamination=args.get("contamination", False),
-                                  bin=args.get("bin"), clip=args.get("clip"), flatten=args.get("flatten"))
+                                  bin=args.get("bin"), clip=args.get("clip"), flatten=args.get("flatten"),
+                                  ftbin=args.get("ftbin"))
     for flag, key in (("batch_size", ConfigValue.TEST_MINIBATCH_SIZE), ("nms", ConfigValue.NMS),
                       ("num", ConfigValue.NUM_EVAL)):
         if args.get(flag) is not None:
@@ -235,8 +263,8 @@ def run_eval(args):
 
 def run_bin(args):
     from . import ingest
-    return ingest.bin_dataset(args["dataset"], args["bin"], args["out"], labels=args.get("labels"), clip=args.get("clip"),
-                              flatten=args.get("flatten"))
+    return ingest.bin_dataset(args["dataset"], args.get("bin"), args["out"], labels=args.get("labels"), clip=args.get("clip"),
+                              flatten=args.get("flatten"), ftbin=args.get("ftbin"))
 
 
 def run_extract(args):

@@ -20,7 +20,7 @@ class DetectionDataset:
         TARGET = auto()
         GT = auto()
         NAME = auto()
-        BIN_GEOMETRY = auto()     # ingest.RawMicrographFeed: (by, bx, oy, ox) of each binned micrograph
+        BIN_GEOMETRY = auto()     # ingest.RawMicrographFeed: (by, bx, oy, ox) of each binned micrograph; ftbin: (by, bx, ny, nx)
 
     @staticmethod
     def make_batch(inp, target, hm=None, hm_small=None, metadata=None):

@@ -9,7 +9,10 @@ laid out on the device (ingest.py); ``{name}_scores.txt`` stays i
 (``--clip LO[,HI]``, with ``bin`` only) clamps each binned micrograph to two of its order statistics before the min-max
 normalisation (``ingest.clip_ranks``): the pixels a model trained on ``joint bin --clip`` output saw.  ``flatten=R``
 (``--flatten R``, with ``bin`` only) subtracts each binned micrograph's mean over a (2R+1)^2 window first (with ``clip``:
-clip, flatten, clip), as ``joint bin --flatten R`` writes it."""
+clip, flatten, clip), as ``joint bin --flatten R`` writes it.  ``ftbin=F`` (``--ftbin F``, instead of ``bin``) Fourier-crops
+each raw micrograph by the rational factor F (``ingest.resample_geometry``, csrc/resample.hip); ``{name}_scores.txt`` stays
+in the resampled frame and ``{name}_scores_unbinned.txt`` is written whenever the size changed; ``clip`` and ``flatten``
+go with it as with ``bin``."""
 import logging
 import os
 
@@ -26,9 +29,9 @@ logger = logging.getLogger("joint.eval")
 
 class DenoiserEvaluator(DenoiserTrainer):
     def __init__(self, target_path, runs_dir=cfg_mod.DEFAULT_RUN_DIR, run_dir=None, device=None, contamination=False,
-                 bin=None, clip=None, flatten=None):
+                 bin=None, clip=None, flatten=None, ftbin=None):
         super().__init__({}, "joint", runs_dir=runs_dir, run_dir=run_dir, device=device, contamination=contamination,
-                         bin=bin, clip=clip, flatten=flatten)
+                         bin=bin, clip=clip, flatten=flatten, ftbin=ftbin)
         state_dict = checkpoint.load(target_path)
         if "denoiser" in state_dict:
             self.load_state_dict(state_dict, restore_optimizer=False)

@@ -18,11 +18,19 @@ micrograph does not take the levels of the 8-bit range.  With ``clip`` as well t
 by the same percentages: the background is estimated without the outliers, and the final range comes from the order
 statistics of the flattened image.  The closure holds with the flags on both sides; ``None`` adds no launch.
 
+``ftbin=F`` (``--ftbin F``, instead of ``bin``) resamples by a Fourier crop: any rational 1 <= F <= 64, the whole extent of
+both axes (no margin dropped), no aliasing — ``newstack -ftreduce``, MotionCor2 ``-FtBin``.  The operator is separable,
+Y = My D Mx^T with the real matrices of ``resample_matrix``, and runs as two fp32 MFMA GEMMs over the whole micrograph
+(``torch.ops.sprk.ingest_resample``, csrc/resample.hip) in place of ``ingest_bin``; ``clip`` and ``flatten`` follow as
+they are.  A Fourier crop takes the image as periodic: what leaves at one edge wraps round to the other, as in the
+tools named; it is not tapered.  Output pixel s sits at input position s * B / S (``to_raw`` / ``to_scaled``).
+
 Coordinates: x runs along nx (columns), y along ny (rows) — the frame of the label tables and of ``*_scores.txt``.
 Bin factor N keeps the centred area: binned pixel (x, y) covers samples ox + N*x .. ox + N*x + N-1 (oy likewise)."""
 import logging
 import math
 import os
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -61,6 +69,102 @@ def to_binned(x, y, N, ox, oy, bx, by):
     that binning drops (outside [0, bx) x [0, by)).  Inverse of ``to_unbinned``."""
     xb, yb = (np.asarray(x) - ox) // N, (np.asarray(y) - oy) // N
     return xb, yb, (xb >= 0) & (xb < bx) & (yb >= 0) & (yb < by)
+
+
+MAX_FTBIN = 64
+MAX_SIDE = torch_ops.INGEST_MAX_SIDE
+
+
+def check_ftbin(F):
+    """The factor of ``--ftbin F`` -> Fraction: an int, a Fraction, decimal or ``p/q`` text, or a float (through its
+    ``str``: 9.64 is 241/25, not the binary neighbour), 1 <= F <= MAX_FTBIN."""
+    try:
+        if isinstance(F, bool):
+            raise ValueError
+        if isinstance(F, (float, np.floating)):
+            F = str(float(F))
+        elif isinstance(F, np.integer):
+            F = int(F)
+        F = Fraction(F)
+    except (TypeError, ValueError, ZeroDivisionError):
+        raise ValueError("ftbin factor must be a rational number in 1..%d, got %r" % (MAX_FTBIN, F)) from None
+    if not 1 <= F <= MAX_FTBIN:
+        raise ValueError("ftbin factor must be a rational number in 1..%d, got %s" % (MAX_FTBIN, F))
+    return F
+
+
+def resample_geometry(ny, nx, F):
+    """-> (by, bx): the size of the Fourier-cropped image, floor(n / F + 1/2) per axis in exact rational arithmetic.  Both
+    axes keep their whole extent; the factor per axis is ny / by and nx / bx.  F = 1: (ny, nx)."""
+    F = check_ftbin(F)
+    ny, nx = int(ny), int(nx)
+    if ny > MAX_SIDE or nx > MAX_SIDE:
+        raise ValueError("a %dx%d image is larger than --ftbin takes (%d a side)" % (ny, nx, MAX_SIDE))
+    by, bx = (math.floor(Fraction(n) / F + Fraction(1, 2)) for n in (ny, nx))
+    if by < 2 or bx < 2:
+        raise ValueError("a %dx%d image resampled by %s leaves %dx%d pixels (at least 2 a side)" % (ny, nx, F, by, bx))
+    return by, bx
+
+
+def resample_matrix64(B, S):
+    """The Fourier crop of B samples to S as a real [S, B] matrix in float64, IDFT_S . crop . DFT_B scaled by S / B: the
+    operator of ``extract.crop_matrix64`` with its sum over k in closed form (a Dirichlet kernel).  With the phase
+    t = (s B - b S) mod (S B) in integers and theta / 2 = pi t / (S B):
+        M[s, b] = (1/B) sin(pi (t mod 2B) / B) / sin(theta / 2)              for odd S,
+        the same times cos(theta / 2)                                        for even S (the Nyquist term is shared),
+        S / B where t == 0;
+    t is taken in (-S B / 2, S B / 2] and then t mod 2B in (-B, B]: M keeps its value, and the sines of small arguments
+    their relative accuracy.  Every row sums to 1.  S == B is the identity and is returned as such.
+    Not the bits of ``crop_matrix64`` (they differ by a few 1e-13): that one stays the contract of ``joint extract --scale``."""
+    B, S = int(B), int(S)
+    if not 2 <= S <= B:
+        raise ValueError("resample_matrix: 2 <= S <= B, got B = %d, S = %d" % (B, S))
+    if S == B:
+        return np.eye(B)
+    period = S * B
+    t = (np.arange(S, dtype=np.int64)[:, None] * B - np.arange(B, dtype=np.int64)[None, :] * S) % period
+    zero = t == 0
+    t = np.where(2 * t > period, t - period, t)                  # numerator and denominator change sign together
+    tn = t % (2 * B)
+    tn = np.where(tn > B, tn - 2 * B, tn)
+    half = (np.pi / period) * t
+    m = np.sin((np.pi / B) * tn) / np.sin(np.where(zero, 1.0, half)) / B
+    if S % 2 == 0:
+        m = m * np.cos(half)
+    return np.where(zero, S / B, m)
+
+
+_resample_matrices = {}
+
+
+def resample_matrix(B, S, device=None):
+    """``resample_matrix64`` rounded to float32.  Without a device: the [S, B] array.  With one: an operand of
+    ``torch.ops.sprk.ingest_resample``, a contiguous tensor [roundup(S, 16), roundup(B, 4)] on that device whose added
+    rows and columns are exact zeros, built once per (B, S, device)."""
+    B, S = int(B), int(S)
+    key = (B, S, None if device is None else str(torch.device(device)))
+    if key not in _resample_matrices:
+        if device is None:
+            _resample_matrices[key] = resample_matrix64(B, S).astype(np.float32)
+        else:
+            padded = np.zeros((-(-S // 16) * 16, -(-B // 4) * 4), dtype=np.float32)
+            padded[:S, :B] = resample_matrix(B, S)
+            _resample_matrices[key] = torch.from_numpy(padded).to(device)
+    return _resample_matrices[key]
+
+
+def to_raw(x, y, ny, nx, by, bx):
+    """Pixel of the [by, bx] Fourier-cropped image -> the sample nearest to its position x * nx / bx (halves go up)."""
+    return (2 * x * nx + bx) // (2 * bx), (2 * y * ny + by) // (2 * by)
+
+
+def to_scaled(x, y, ny, nx, by, bx):
+    """Sample -> (x, y of the nearest pixel of the [by, bx] image, inside); ``inside`` is False for points outside the
+    micrograph.  ``to_scaled(to_raw(x))`` is x for every pixel."""
+    x, y = np.asarray(x), np.asarray(y)
+    xs = np.minimum((2 * x * bx + nx) // (2 * nx), bx - 1)
+    ys = np.minimum((2 * y * by + ny) // (2 * ny), by - 1)
+    return xs, ys, (x >= 0) & (x < nx) & (y >= 0) & (y < ny)
 
 
 def require_mrc(path):
@@ -187,15 +291,32 @@ def check_flatten(R):
     return int(R)
 
 
-def _bin(path, N, device, clip=None, flatten=None):
-    N = check_bin(N)
+def _exclusive(bin, ftbin):
+    """``ftbin`` takes the place of ``bin``: with it, ``bin`` is None or 1."""
+    if ftbin is not None and bin not in (None, 1):
+        raise ValueError("bin %r and ftbin %r exclude one another" % (bin, ftbin))
+
+
+def _bin(path, N, device, clip=None, flatten=None, ftbin=None):
+    _exclusive(N, ftbin)
+    if ftbin is None:
+        N = check_bin(N)
+    else:
+        ftbin = check_ftbin(ftbin)
     if clip is not None:
         clip = check_clip(clip)
     if flatten is not None:
         flatten = check_flatten(flatten)
     raw, header = read_raw(path, device)
-    geometry = binned_geometry(header.ny, header.nx, N)
-    binned, rng = torch.ops.sprk.ingest_bin(raw, header.mode, header.ny, header.nx, N)
+    if ftbin is None:
+        geometry = binned_geometry(header.ny, header.nx, N)
+        binned, rng = torch.ops.sprk.ingest_bin(raw, header.mode, header.ny, header.nx, N)
+    else:                     # the Fourier crop of the whole micrograph: two fp32 MFMA GEMMs (csrc/resample.hip)
+        ny, nx = header.ny, header.nx
+        by, bx = resample_geometry(ny, nx, ftbin)
+        geometry = (by, bx, ny, nx)
+        binned, rng = torch.ops.sprk.ingest_resample(raw, header.mode, ny, nx, by, bx, resample_matrix(ny, by, raw.device),
+                                                     resample_matrix(nx, bx, raw.device))
     if clip is not None:      # the image clamped to two of its order statistics, which become the range (csrc/ingest.hip)
         binned, rng = torch.ops.sprk.ingest_clip(binned, rng, *clip_ranks(binned.numel(), clip))
     if flatten is not None:   # minus the local mean; the background of the clamped image, then the clip of the flat one
@@ -205,27 +326,29 @@ def _bin(path, N, device, clip=None, flatten=None):
     return binned, rng, geometry
 
 
-def binned(path, bin, device="cuda", clip=None, flatten=None):
+def binned(path, bin, device="cuda", clip=None, flatten=None, ftbin=None):
     """-> (float32 CUDA tensor [by, bx]: the N x N block means, geometry) — what ``joint bin`` writes.  ``clip``
     (lo_pct, hi_pct): clamped to the order statistics of ``clip_ranks``; ``flatten`` R: minus the mean over the
-    (2R+1)^2 window (with ``clip``: clip, flatten, clip); None: as they are."""
-    b, _, geometry = _bin(path, bin, device, clip, flatten)
+    (2R+1)^2 window (with ``clip``: clip, flatten, clip); None: as they are.  ``ftbin`` F (``bin`` None or 1): the
+    Fourier crop to ``resample_geometry`` instead of block means, geometry (by, bx, ny, nx)."""
+    b, _, geometry = _bin(path, bin, device, clip, flatten, ftbin)
     return b, geometry
 
 
-def binned_uint8(path, bin, device="cuda", clip=None, flatten=None):
+def binned_uint8(path, bin, device="cuda", clip=None, flatten=None, ftbin=None):
     """-> uint8 array [by, bx]: ``micrograph_io.load_image`` of the binned (and, with ``clip`` / ``flatten``, clamped /
-    flattened) micrograph."""
-    b, rng, _ = _bin(path, bin, device, clip, flatten)
+    flattened) micrograph; with ``ftbin``: of the Fourier-cropped one."""
+    b, rng, _ = _bin(path, bin, device, clip, flatten, ftbin)
     u8, _ = torch.ops.sprk.ingest_finish(b, rng, True, False)
     return u8.cpu().numpy()
 
 
-def ingest(path, bin, device="cuda", clip=None, flatten=None):
+def ingest(path, bin, device="cuda", clip=None, flatten=None, ftbin=None):
     """-> (network input float32 CUDA [1, 1, S, S], (by, bx), (by, bx, oy, ox)): the binned micrograph (with ``clip``:
     clamped to its two order statistics first; with ``flatten``: its local mean subtracted) min-max quantised, /255,
-    transposed and reflect-padded, as ``MicrographFeed`` hands it to the network."""
-    b, rng, geometry = _bin(path, bin, device, clip, flatten)
+    transposed and reflect-padded, as ``MicrographFeed`` hands it to the network.  With ``ftbin`` (``bin`` None or 1): the
+    Fourier-cropped micrograph, and (by, bx, ny, nx) as the geometry."""
+    b, rng, geometry = _bin(path, bin, device, clip, flatten, ftbin)
     _, net = torch.ops.sprk.ingest_finish(b, rng, False, True)
     return net[None, None], geometry[:2], geometry
 
@@ -234,11 +357,14 @@ class RawMicrographFeed:
     """``feed.MicrographFeed`` for raw micrographs: same rows (``micrograph_io.read_image_table``), same order
     (``count`` wrapping, ``rank`` / ``world`` striding), same items — but a file is read when its turn comes (nothing
     is held in memory) and its tensor comes from ``ingest``.  IMAGE_SHAPE is [1, bx, by] (tensors are transposed), the
-    target is all zeros (evaluation has no labels to draw), BIN_GEOMETRY carries (by, bx, oy, ox)."""
+    target is all zeros (evaluation has no labels to draw), BIN_GEOMETRY carries (by, bx, oy, ox) — with ``ftbin``
+    (``bin`` None or 1) (by, bx, ny, nx)."""
 
     def __init__(self, rows, bin, count=None, device="cuda", rank=0, world=1, gt=None, clip=None,
-                 flatten=None):
-        self.bin = check_bin(bin)
+                 flatten=None, ftbin=None):
+        _exclusive(bin, ftbin)
+        self.ftbin = None if ftbin is None else check_ftbin(ftbin)
+        self.bin = check_bin(bin) if ftbin is None else None
         self.clip = None if clip is None else check_clip(clip)
         self.flatten = None if flatten is None else check_flatten(flatten)
         self.device = torch.device(device)
@@ -262,7 +388,7 @@ class RawMicrographFeed:
         M = DetectionDataset.Metadata
         for pos, k in self.order:
             path, name = self.items[k]
-            inp, (by, bx), geometry = ingest(path, self.bin, self.device, self.clip, self.flatten)
+            inp, (by, bx), geometry = ingest(path, self.bin, self.device, self.clip, self.flatten, self.ftbin)
             md = {M.INDEXES: torch.tensor([k]), M.NAME: [name], M.IMAGE_SHAPE: torch.tensor([[1, bx, by]]), M.GT: [],
                   M.BIN_GEOMETRY: [geometry]}
             if name in self.gt:
@@ -280,16 +406,30 @@ def unbinned_map(N, ox, oy):
     return to_raw
 
 
-def bin_dataset(dataset, bin, out_dir, labels=None, device="cuda", clip=None, flatten=None):
+def unscaled_map(ny, nx, by, bx):
+    """The coordinate map ``picks.write_scores`` applies for ``{name}_scores_unbinned.txt`` under ``ftbin``: plain ints
+    through ``to_raw``."""
+    def map_(x, y):
+        return to_raw(int(x), int(y), ny, nx, by, bx)
+    return map_
+
+
+def bin_dataset(dataset, bin, out_dir, labels=None, device="cuda", clip=None, flatten=None, ftbin=None):
     """``joint bin``: every micrograph of the table / directory ``dataset`` binned on the device and written as a
     float32 MRC ``out_dir/{name}.mrc``, plus ``out_dir/images.txt`` (image_name, path) and, with ``labels``,
     ``out_dir/labels.txt`` (coordinates through ``to_binned``, points outside the binned area dropped, other columns
     kept).  Label rows of images that are not in the dataset are dropped too, with a warning that names them.
     ``clip`` / ``flatten``: the image ``binned`` returns for them — what ``joint eval --bin N`` with the same flags sees.
+    ``ftbin`` F (``bin`` None or 1): Fourier-cropped instead (``joint bin --ftbin F``), labels through ``to_scaled``
+    (points outside the micrograph dropped), geometry (by, bx, ny, nx).
     -> {"images": path, "labels": path or None, "geometry": {name: (by, bx, oy, ox)},
         "label_rows": {"kept", "outside", "unknown_image"} or None}."""
     from . import coordinates
-    bin = check_bin(bin)
+    _exclusive(bin, ftbin)
+    if ftbin is None:
+        bin = check_bin(bin)
+    else:
+        ftbin = check_ftbin(ftbin)
     if clip is not None:
         clip = check_clip(clip)
     if flatten is not None:
@@ -300,7 +440,7 @@ def bin_dataset(dataset, bin, out_dir, labels=None, device="cuda", clip=None, fl
     os.makedirs(out_dir, exist_ok=True)
     geometry, lines = {}, ["image_name\tpath"]
     for _, name, path in rows:
-        b, geometry[name] = binned(path, bin, device, clip, flatten)
+        b, geometry[name] = binned(path, bin, device, clip, flatten, ftbin)
         out = os.path.join(out_dir, name + ".mrc")
         with open(out, "wb") as f:
             micrograph_io.write_mrc(f, b.cpu().numpy())
@@ -317,6 +457,10 @@ def bin_dataset(dataset, bin, out_dir, labels=None, device="cuda", clip=None, fl
         for i, name in enumerate(table["image_name"].astype(str)):
             if name not in geometry:                         # not a micrograph of this dataset (a misspelt name?)
                 unknown[name] = unknown.get(name, 0) + 1
+                continue
+            if ftbin is not None:
+                by, bx, ny, nx = geometry[name]
+                xs[i], ys[i], keep[i] = to_scaled(xs[i], ys[i], ny, nx, by, bx)
                 continue
             by, bx, oy, ox = geometry[name]
             xs[i], ys[i], keep[i] = to_binned(xs[i], ys[i], bin, ox, oy, bx, by)

@@ -693,6 +693,48 @@ def _ingest_flatten_fake(binned, rng, R):
 _register("ingest_flatten", "(Tensor binned, Tensor range, int R) -> (Tensor, Tensor)", _ingest_flatten,
           _ingest_flatten_fake)
 
+INGEST_MAX_SIDE = 16384                          # sprk_ingest_resample: the longest image side it takes
+
+
+def _resample_check(raw, mode, ny, nx, by, bx, my, mx):
+    if mode not in MRC_ITEMSIZE:
+        raise _lib.SprkError("ingest_resample: unsupported MRC mode %d" % mode)
+    if not (2 <= by <= ny <= INGEST_MAX_SIDE and 2 <= bx <= nx <= INGEST_MAX_SIDE):
+        raise _lib.SprkError("ingest_resample: a %dx%d image resampled to %dx%d (2 <= by <= ny <= %d and 2 <= bx <= nx <= %d)"
+                             % (ny, nx, by, bx, INGEST_MAX_SIDE, INGEST_MAX_SIDE))
+    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
+        raise _lib.SprkError("ingest_resample: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
+                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+    for name, m, S, B in (("my", my, by, ny), ("mx", mx, bx, nx)):
+        shape = (-(-S // 16) * 16, -(-B // 4) * 4)
+        if m.dtype != torch.float32 or tuple(m.shape) != shape or m.device != raw.device:
+            raise _lib.SprkError("ingest_resample: %s must be the float32 matrix of ingest.resample_matrix(%d, %d), [%d, %d] "
+                                 "on %s, got %s %s on %s" % (name, B, S, *shape, raw.device, m.dtype, tuple(m.shape), m.device))
+
+
+def _ingest_resample(raw, mode, ny, nx, by, bx, my, mx):
+    """raw: uint8 CUDA tensor holding the file's ny*nx samples; my, mx: ingest.resample_matrix(ny, by) / (nx, bx) ->
+    (the Fourier-cropped image float32 [by, bx], range float32 [2])."""
+    _resample_check(raw, mode, ny, nx, by, bx, my, mx)
+    if not raw.is_contiguous() or not my.is_contiguous() or not mx.is_contiguous():
+        raise _lib.SprkError("ingest_resample: raw, my and mx must be contiguous")
+    L = _lib.lib()
+    out, rng = _f32(raw, (by, bx)), _f32(raw, (2,))
+    ws = _ws(L.sprk_ingest_resample_ws_bytes(int(ny), int(nx), int(by), int(bx)), raw)
+    check(L.sprk_ingest_resample(_p(raw), int(mode), int(ny), int(nx), int(by), int(bx), _p(my), int(my.shape[1]), _p(mx),
+                                 int(mx.shape[1]), _p(out), _p(rng), _p(ws), ws.numel(), _stream(raw)),
+          "sprk_ingest_resample")
+    return out, rng
+
+
+def _ingest_resample_fake(raw, mode, ny, nx, by, bx, my, mx):
+    _resample_check(raw, mode, ny, nx, by, bx, my, mx)
+    return raw.new_empty((by, bx), dtype=torch.float32), raw.new_empty((2,), dtype=torch.float32)
+
+
+_register("ingest_resample", "(Tensor raw, int mode, int ny, int nx, int by, int bx, Tensor my, Tensor mx) -> (Tensor, Tensor)",
+          _ingest_resample, _ingest_resample_fake)
+
 
 # ---- particle extraction (extract.py: raw MRC samples + pick coordinates -> normalised particle stack) ------------------------
 EXTRACT_MAX_BOX = 1024                           # sprk_extract_boxes: the int64 sum of squares stays below 2^63 up to here

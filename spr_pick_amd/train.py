@@ -62,7 +62,7 @@ tensor_to_png = outputs_mod.tensor_to_png      # save_tensor_image (utils/data.p
 class DenoiserTrainer:
     def __init__(self, cfg, mode, state=None, runs_dir=cfg_mod.DEFAULT_RUN_DIR, run_dir=None, alpha=0.5, tau=0.01,
                  bb=32, device=None, seed=0, graph=True, loss_scale=None, contamination=False, bin=None, clip=None,
-                 flatten=None):
+                 flatten=None, ftbin=None):
         self.runs_dir = os.path.abspath(runs_dir)
         self._run_dir = run_dir
         self.cfg = cfg
@@ -91,12 +91,17 @@ class DenoiserTrainer:
         # raw-micrograph evaluation (joint eval --bin N): the test set is read, binned N x N and laid out on the device
         # (ingest.py); a run option as well.  None = the host loader, as ever.
         self.bin = None if bin is None else ingest_mod.check_bin(bin)
+        # ... or Fourier-cropped by a rational factor instead (joint eval --ftbin F; csrc/resample.hip)
+        if ftbin is not None and bin not in (None, 1):
+            raise ValueError("bin and ftbin exclude one another")
+        self.ftbin = None if ftbin is None else ingest_mod.check_ftbin(ftbin)
+        raw = self.bin is not None or self.ftbin is not None
         # ... each clamped to two of its order statistics before the min-max step (joint eval --bin N --clip LO[,HI])
-        if clip is not None and bin is None:
+        if clip is not None and not raw:
             raise ValueError("clip belongs to the raw-micrograph ingest: give bin as well")
         self.clip = None if clip is None else ingest_mod.check_clip(clip)
         # ... and / or with its local mean over a (2R+1)^2 window subtracted (joint eval --bin N --flatten R)
-        if flatten is not None and bin is None:
+        if flatten is not None and not raw:
             raise ValueError("flatten belongs to the raw-micrograph ingest: give bin as well")
         self.flatten = None if flatten is None else ingest_mod.check_flatten(flatten)
         self._metrics_file = None
@@ -473,6 +478,11 @@ class DenoiserTrainer:
                 _, _, oy, ox = metadata[DetectionDataset.Metadata.BIN_GEOMETRY][batch_index]
                 self.writer.call(picks.write_scores, path(scoreformat, "scores_unbinned"), name, scores, coords,
                                  tuple(score_map.shape), picks.BORDER, ingest_mod.unbinned_map(self.bin, ox, oy))
+            if self.ftbin is not None:
+                by, bx, ny, nx = metadata[DetectionDataset.Metadata.BIN_GEOMETRY][batch_index]
+                if (by, bx) != (ny, nx):
+                    self.writer.call(picks.write_scores, path(scoreformat, "scores_unbinned"), name, scores, coords,
+                                     tuple(score_map.shape), picks.BORDER, ingest_mod.unscaled_map(ny, nx, by, bx))
             if contam is not None:
                 st = dict(zip(CONTAM_STATS, contam.tolist()))
                 logger.info("%s: contamination mask excludes %.3f%% of the score map (%d seeds)", name,
@@ -668,11 +678,11 @@ class DenoiserTrainer:
         c = self.cfg
         self._require_txt(ConfigValue.TEST_DATASET_TYPE)
         gt = feed_mod.load_reference_images(c[ConfigValue.TEST_GT_PATH]) if c.get(ConfigValue.TEST_GT_PATH) else None
-        if self.bin is not None:
+        if self.bin is not None or self.ftbin is not None:
             return ingest_mod.RawMicrographFeed(micrograph_io.read_image_table(c[ConfigValue.TEST_DATA_PATH]), self.bin,
                                                 count=cfg_mod.test_length(c), device=self.device, rank=self.rank,
                                                 world=self.world, gt=gt, clip=self.clip,
-                                                flatten=self.flatten)
+                                                flatten=self.flatten, ftbin=self.ftbin)
         groups, names = feed_mod.load_micrographs(c[ConfigValue.TEST_DATA_PATH], c.get(ConfigValue.TEST_LABEL_PATH),
                                                   radius=3, bb=c[ConfigValue.BB])
         return feed_mod.MicrographFeed(groups, names, count=cfg_mod.test_length(c), device=self.device,
