@@ -641,6 +641,33 @@ size_t sprk_ingest_resample_ws_bytes(int ny, int nx, int by, int bx);
 int sprk_ingest_resample(const void *raw, int mode, int ny, int nx, int by, int bx, const float *my, int ldmy,
                          const float *mx, int ldmx, float *out, float *range_out, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- tiled power spectra (`joint ctf`) -----------------------------------------------------
+ * sprk_psd_tiles: the summed half-plane power spectrum of T x T tiles of ONE raw micrograph (raw as for sprk_ingest_bin:
+ * [ny,nx] samples of mode 0 / 1 / 2 / 6, 16-byte aligned start; rows may be only itemsize-aligned).  T a multiple of 16 in
+ * 16..1024, T <= ny, nx <= 16384, H = T/2 + 1.  Tiles at a step of T/2: ty = (ny - T) / (T/2) + 1 rows of tx = (nx - T) /
+ * (T/2) + 1 tiles, tile t = i*tx + j with its origin at (i*T/2, j*T/2); the trailing margin of fewer than T/2 samples on
+ * either axis is not covered.  D: integer modes float(x - x[0,0]) with x[0,0] of the micrograph (exact), float32 x, taken
+ * to be finite; no taper, no per-tile mean (the DC bin is of no use).
+ * w1 [2H, T] fp32: row v cos(2 pi ((v c) mod T) / T), row H+v the sine of the same angle; w2 [2T, 2T] fp32 = [[C, -S], [S,
+ * C]], C[u,r] = cos(2 pi ((u r) mod T) / T), S likewise (spr_pick_amd.ctf.dft_matrices: built in float64, the integer
+ * product reduced mod T first).  On the device, 16-byte aligned, row strides ldw1 >= T and ldw2 >= 2T floats, multiples
+ * of 4; rows 0 .. 2H-1 / 0 .. 2T-1 and columns 0 .. T-1 / 0 .. 2T-1 are read.  The sums are fp32 fmaf chains in a fixed
+ * order on v_mfma_f32_16x16x4_f32, one accumulator per element and stage, K never split:
+ *   U[r, q]  = chain over c = 0 .. T-1 ascending of D_t[r, c] * w1[q, c], from 0.0f, q < 2H;
+ *   V        = [U[:, :H] ; U[:, H:]], [2T, H] (in the workspace);
+ *   Re[u, v] = chain over k = 0 .. 2T-1 ascending of w2[u, k] * V[k, v], from 0.0f; Im[u, v] the same with row T+u;
+ *   Q_t      = fmaf(Im, Im, Re * Re), the product rounded first;
+ *   p_out[u, v] = ((0 + Q_0) + Q_1) + ... in ascending tile order, plain fp32 adds: fp32 [T, H], the un-normalised sum.
+ * Nothing uninitialised is read into a stored value: the workspace may hold anything, NaNs included.
+ * max_batch: tiles whose V and Q the workspace holds at a time (0 = the library's choice, about 256 MiB); p_out does not
+ * depend on it.  Refused (SPRK_EINVAL, nothing launched): another mode, T not a multiple of 16 or out of range, ny or nx
+ * below T or above 16384, a negative max_batch, a row stride too small or not a multiple of 4, null or misaligned
+ * pointers (p_out and ws 16-byte aligned as well); a short workspace: SPRK_EWORKSPACE.
+ * Three launches per batch on `stream`, no host synchronisation, no atomics. */
+size_t sprk_psd_tiles_ws_bytes(int ny, int nx, int T, int max_batch);
+int sprk_psd_tiles(const void *raw, int mode, int ny, int nx, int T, const float *w1, int ldw1, const float *w2, int ldw2,
+                   int max_batch, float *p_out, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- particle extraction (`joint extract`) -----------------------------------------------
  * Boxes cut out of ONE raw micrograph (the buffer sprk_ingest_bin takes: [ny,nx] samples of mode 0 / 1 / 2 / 6, 16-byte
  * aligned start), binned, background-normalised and optionally inverted: out [P, b, b] fp32 with b = box / bin, status [P].

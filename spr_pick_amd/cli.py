@@ -1,7 +1,8 @@
 """``joint`` command line (cli/cli.py, cli/cmds/train.py:24-300, cli/cmds/eval.py:15-71 of the
 reference): ``joint train start|resume`` and ``joint eval`` with the same flags and the same
-flag -> configuration mapping, plus ``joint bin`` (the README's ``newstack -bin`` preparation, on the GPU) and ``joint extract``
-(particle stacks from the pick tables and the raw micrographs, on the GPU).  Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
+flag -> configuration mapping, plus ``joint bin`` (the README's ``newstack -bin`` preparation, on the GPU), ``joint extract``
+(particle stacks from the pick tables and the raw micrographs, on the GPU) and ``joint ctf`` (tiled power spectra of the raw
+micrographs on the GPU, one fitted defocus each, ``micrographs_ctf.star`` for ``joint extract --ctf``).  Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
 under ``python -m torch.distributed.run --nproc-per-node N -m spr_pick_amd -- ...`` (keep the ``--``)."""
 import argparse
 
@@ -114,6 +115,12 @@ def _check_extract(ns):
     check_scale(ns.box, ns.scale, ns.bg_radius)
 
 
+def _check_ctf(ns):
+    from .ctf import check_fit_args, check_tile
+    check_tile(ns.tile)
+    check_fit_args(ns.apix, ns.kv, ns.cs, ns.ac, ns.min_res, ns.max_res, ns.min_defocus, ns.max_defocus)
+
+
 def build_parser():
     parser = _Parser(prog="joint", description="Joint denoising + particle picking on MI355X "
                                      "(train / evaluate), drop-in for spr_pick's `joint` command.")
@@ -200,7 +207,30 @@ def build_parser():
     ex.add_argument("--threshold", type=float, metavar="S", help="keep picks with score > S (default: all)")
     ex.add_argument("--invert", action="store_true", help="invert the contrast")
     ex.add_argument("--no_norm", action="store_true", help="block means only, no background normalisation")
+    ex.add_argument("--ctf", metavar="STAR",
+                    help="micrographs_ctf.star of `joint ctf`: append each micrograph's CTF columns to its rows of "
+                         "particles.star, _rlnDetectorPixelSize multiplied by N (--bin) or B / S (--scale); a micrograph "
+                         "with picks and no row there is an error")
     ex.check = _check_extract
+
+    cf = cmds.add_parser("ctf", help="Power spectra of raw micrographs on the GPU and one defocus value each "
+                                     "(replaces a CTFFIND / Gctf run before 2-D classification; astigmatism is NOT fitted: "
+                                     "DefocusU = DefocusV, angle 0).")
+    cf.add_argument("--dataset", "-d", required=True, help="Table (image_name, path) or directory of raw MRC micrographs.")
+    cf.add_argument("--out", "-o", required=True,
+                    help="Directory for {name}_psd.mrc, {name}_profile.txt and micrographs_ctf.star.")
+    cf.add_argument("--apix", type=float, metavar="A", help="Angstrom per pixel (default: the MRC header's xlen / mx)")
+    cf.add_argument("--kv", type=float, default=300, metavar="V", help="acceleration voltage in kV (default 300)")
+    cf.add_argument("--cs", type=float, default=2.7, metavar="C", help="spherical aberration in mm (default 2.7)")
+    cf.add_argument("--ac", type=float, default=0.07, metavar="Q", help="amplitude contrast in [0, 1) (default 0.07)")
+    cf.add_argument("--tile", type=int, default=512, metavar="T",
+                    help="tile side: a multiple of 16 in 16..1024 (default 512); tiles overlap by half, and a trailing "
+                         "margin of fewer than T / 2 samples is not covered")
+    cf.add_argument("--min_res", type=float, default=30, metavar="R", help="coarsest resolution fitted, Angstrom (default 30)")
+    cf.add_argument("--max_res", type=float, metavar="R", help="finest resolution fitted, Angstrom (default max(4, 2.2 A))")
+    cf.add_argument("--min_defocus", type=float, default=3000, metavar="D", help="lowest defocus searched, Angstrom (default 3000)")
+    cf.add_argument("--max_defocus", type=float, default=50000, metavar="D", help="highest defocus searched, Angstrom (default 50000)")
+    cf.check = _check_ctf
     return parser
 
 
@@ -273,9 +303,19 @@ def run_extract(args):
     counts = extract.extract_dataset(args["dataset"], args["picks"], args["out"], args["box"], bin=args["bin"],
                                      picks_bin=args["picks_bin"], threshold=args.get("threshold"),
                                      bg_radius=args.get("bg_radius"), normalize=not args["no_norm"], invert=args["invert"],
-                                     scale=args.get("scale"))
+                                     scale=args.get("scale"), ctf=args.get("ctf"))
     print(json.dumps({"particles": sum(c["written"] for c in counts.values()), "micrographs": counts}))
     return counts
+
+
+def run_ctf(args):
+    import json
+    from . import ctf
+    res = ctf.ctf_dataset(args["dataset"], args["out"], apix=args.get("apix"), kv=args["kv"], cs=args["cs"], ac=args["ac"],
+                          tile=args["tile"], min_res=args["min_res"], max_res=args.get("max_res"),
+                          min_defocus=args["min_defocus"], max_defocus=args["max_defocus"])
+    print(json.dumps({"micrographs": res}))
+    return res
 
 
 def start(argv=None):
@@ -291,4 +331,6 @@ def start(argv=None):
         return run_bin(args)
     if args["command"] == "extract":
         return run_extract(args)
+    if args["command"] == "ctf":
+        return run_ctf(args)
     return run_eval(args)

@@ -16,7 +16,7 @@
 // of 64 through LDS: the samples by element loads of their own type (rows are not 16-byte aligned when nx is odd),
 // converted once; the 64 rows of Mx as float4.  The next two chunks are in registers before the current one is
 // multiplied: fetches are unconditional loads from clamped addresses that nothing touches until they are staged, and the
-// zeros of the padding are formed at staging (fetch4 / zero4 below).  A staged row is 66 floats: lane (row, k) of a
+// zeros of the padding are formed at staging (fetch4 / zero4, mfma_stage.h).  A staged row is 66 floats: lane (row, k) of a
 // fragment read sits on bank 2*row + k.  A chunk's fragment reads run a group of four MFMA steps ahead (mfma_chunk).
 // Stage 2, resample_cols_kernel<WM, TN>: one workgroup of WM waves per 16*WM rows x 16*TN columns of Y; rows of My as
 // float4, U [64 rows of K, 16*TN columns] as float4 into rows of 16*TN + 16 floats (the two k rows a half wave reads land
@@ -29,12 +29,10 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma_stage.h"
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-constexpr int kKC = 64;                          // columns of K staged per chunk
-constexpr int kLd = kKC + 2;                     // floats per staged row of an A operand (and of Mx in stage 1)
 constexpr int kMaxSide = 16384;                  // a side of the image at most: U is ny * roundup(bx, 4) <= 2^28 floats, indexed in long
 constexpr int kRowsThreads = 256;                // stage 1: four waves
 constexpr int kRowsTile = 64;                    // ... on 64 rows x 64 columns of U
@@ -99,21 +97,6 @@ __global__ __launch_bounds__(kRangeThreads) void resample_range_kernel(const Par
     }
 }
 
-// Fetching and zeroing are apart.  A fetch is an unconditional load from an address clamped into the part of its array
-// that may be read, and nothing touches the value until the chunk is staged, two chunks later: only so are a chunk's loads
-// in flight together and behind the MFMAs of the chunks before.  (With the load under a branch, or a select on its value
-// next to it, the compiler waited for every load right behind its issue: one round trip to memory after the other.)
-// Staging then turns every element outside the operand into a zero formed in registers.
-// fetch4: the float4 at row min(row, rows-1), columns min(q, cols4-4) .. +3 (cols4 a multiple of 4, at least 4)
-__device__ __forceinline__ float4 fetch4(const float *__restrict__ m, int ld, int rows, int cols4, int row, int q) {
-    return *reinterpret_cast<const float4 *>(m + (long)min(row, rows - 1) * ld + min(q, cols4 - 4));
-}
-// zero4: the elements at K positions q .. q+3 that lie at or past `end`, or all four unless `in`, become zeros
-__device__ __forceinline__ float4 zero4(float4 v, bool in, int q, int end) {
-    return make_float4(in && q < end ? v.x : 0.0f, in && q + 1 < end ? v.y : 0.0f, in && q + 2 < end ? v.z : 0.0f,
-                       in && q + 3 < end ? v.w : 0.0f);
-}
-
 // One whole chunk of K for a wave's TN accumulators: kKC / 4 MFMA steps per accumulator, k ascending.  The fragment reads
 // of kGroup steps (ap[k]: A at this lane's row; bp[t * b_tile + k * b_step]: B of tile t) are issued a group ahead of
 // the MFMAs that consume them, so that the LDS latency hides behind a group's MFMAs instead of standing before each step.
@@ -143,12 +126,6 @@ __device__ __forceinline__ void mfma_chunk(f32x4 (&acc)[TN], const float *ap, co
             for (int t = 0; t < TN; ++t)
                 acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g & 1][q], b[g & 1][t][q], acc[t], 0, 0, 0);
     }
-}
-
-// a float4 into a staged row of kLd floats (8-byte aligned: kLd is even)
-__device__ __forceinline__ void stage4(float *d, float4 v) {
-    *reinterpret_cast<float2 *>(d) = make_float2(v.x, v.y);
-    *reinterpret_cast<float2 *>(d + 2) = make_float2(v.z, v.w);
 }
 
 // ---- stage 1: U[r0 .. r0+63, j0 .. j0+63] = D Mx^T --------------------------------------------------------------------

@@ -17,7 +17,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, export, ingest, micrograph_io, picks as picks_mod, torch_ops
+from . import _lib, ctf as ctf_mod, export, ingest, micrograph_io, picks as picks_mod, torch_ops
 
 logger = logging.getLogger("joint.extract")
 OK, OUTSIDE, FLAT = 0, 1, 2                     # status codes of sprk_extract_boxes
@@ -192,14 +192,34 @@ def read_pick_tables(picks, names, picks_bin=1):
     return tables
 
 
+def _ctf_columns(star, named_paths, pixel_factor):
+    """The text appended to every ``particles.star`` row of a micrograph, {name: "\\t..."}: the columns of its row in the
+    ``micrographs_ctf.star`` table ``star`` (matched by the file name, as ``_rlnMicrographName`` is written), verbatim
+    except ``_rlnDetectorPixelSize``, which is multiplied by ``pixel_factor``.  ValueError naming the micrographs of
+    ``named_paths`` that have no row."""
+    table = ctf_mod.read_ctf_star(star)
+    absent = [name for name, path in named_paths if os.path.basename(path) not in table]
+    if absent:
+        raise ValueError("%s has no row for %d micrographs that have picks: %s" % (star, len(absent), ", ".join(absent)))
+    cols = {}
+    for name, path in named_paths:
+        row = dict(table[os.path.basename(path)])
+        row["DetectorPixelSize"] = "%.5f" % (float(row["DetectorPixelSize"]) * pixel_factor)
+        cols[name] = "".join("\t" + row[c] for c in ctf_mod.CTF_STAR_COLUMNS[1:])
+    return cols
+
+
 def extract_dataset(dataset, picks, out_dir, box, bin=1, picks_bin=1, threshold=None, bg_radius=None, normalize=True,
-                    invert=False, device="cuda", scale=None):
+                    invert=False, device="cuda", scale=None, ctf=None):
     """``joint extract``: for every micrograph of the table / directory ``dataset`` that has a pick table, the picks
     with score > ``threshold`` (all of them when None), mapped from the ``picks_bin`` frame to raw samples, extracted in
     one launch and written as the float32 stack ``out_dir/{name}.mrcs`` (status-0 particles only, pick order); at the
     end ``out_dir/particles.star`` with one row per written particle.  A micrograph without a surviving particle writes
     no stack; micrographs without a pick table are skipped with a warning.  scale = S: stacks of side S by Fourier
-    cropping (``bin`` must be 1); the coordinates of ``particles.star`` stay in raw samples either way.
+    cropping (``bin`` must be 1); the coordinates of ``particles.star`` stay in raw samples either way.  ctf = the
+    ``micrographs_ctf.star`` of ``joint ctf``: every row gains its micrograph's CTF columns, ``_rlnDetectorPixelSize``
+    multiplied by ``bin`` (or box / S) so that it states the pixel size of the stacks; a micrograph with picks and without a
+    row there is a ValueError before anything is extracted.
     -> {name: {"written", "outside", "flat"}} for the micrographs that had a table."""
     if scale is not None:
         if bin != 1:
@@ -212,6 +232,10 @@ def extract_dataset(dataset, picks, out_dir, box, bin=1, picks_bin=1, threshold=
     if not rows:
         raise ValueError("no micrographs found in %s" % dataset)
     tables = read_pick_tables(picks, [name for _, name, _ in rows], picks_bin)
+    ctf_cols = None
+    if ctf is not None:
+        ctf_cols = _ctf_columns(ctf, [(name, path) for _, name, path in rows if name in tables and len(tables[name][0])],
+                                float(box) / b)
     os.makedirs(out_dir, exist_ok=True)
     counts, star, missing = {}, [], []
     for _, name, path in rows:
@@ -244,13 +268,15 @@ def extract_dataset(dataset, picks, out_dir, box, bin=1, picks_bin=1, threshold=
         with open(os.path.join(out_dir, stack), "wb") as f:
             micrograph_io.write_mrc(f, particles)
         for k, i in enumerate(ok):
-            star.append("%d\t%d\t%06d@%s\t%s\t%s\n" % (xy[i, 0], xy[i, 1], k + 1, stack, os.path.basename(path),
-                                                      str(scores[i])))
+            star.append("%d\t%d\t%06d@%s\t%s\t%s%s\n" % (xy[i, 0], xy[i, 1], k + 1, stack, os.path.basename(path),
+                                                        str(scores[i]), ctf_cols[name] if ctf_cols else ""))
     if missing:
         logger.warning("%s: %d micrographs skipped because %s has no pick table for them: %s", dataset, len(missing), picks,
                        ", ".join(missing[:10]) + (" ..." if len(missing) > 10 else ""))
     with open(os.path.join(out_dir, "particles.star"), "w") as f:
         f.write(export.PARTICLES_STAR_HEADER)
+        if ctf_cols is not None:
+            f.write("".join("_rln%s #%d\n" % (c, 6 + k) for k, c in enumerate(ctf_mod.CTF_STAR_COLUMNS[1:])))
         f.writelines(star)
     logger.info("%s: %d particles of %d micrographs written to %s", dataset, len(star), len(counts), out_dir)
     return counts

@@ -844,6 +844,63 @@ _register("extract_scale", "(Tensor raw, int mode, int ny, int nx, Tensor xy, in
                            "bool normalize, bool invert) -> (Tensor, Tensor)", _extract_scale, _extract_scale_fake)
 
 
+# ---- tiled power spectra (ctf.py: raw MRC samples -> the summed power spectrum of overlapping tiles) --------------------------
+PSD_MIN_TILE, PSD_MAX_TILE = 16, 1024            # sprk_psd_tiles: T a multiple of 16 in this range
+
+
+def psd_tile(T):
+    """Argument check shared by the operator, ctf.py and the command line -> T."""
+    if not PSD_MIN_TILE <= T <= PSD_MAX_TILE or T % 16:
+        raise _lib.SprkError("psd_tiles: tile side %d (a multiple of 16 in %d..%d)" % (T, PSD_MIN_TILE, PSD_MAX_TILE))
+    return T
+
+
+def psd_matrix_shapes(T):
+    """-> the shapes of the operands w1 and w2: [roundup(2H, 16), T] and [2T, 2T]"""
+    return (-(-(T + 2) // 16) * 16, T), (2 * T, 2 * T)
+
+
+def _psd_check(raw, mode, ny, nx, T, w1, w2, max_batch):
+    if mode not in MRC_ITEMSIZE:
+        raise _lib.SprkError("psd_tiles: unsupported MRC mode %d" % mode)
+    psd_tile(T)
+    if not (T <= ny <= INGEST_MAX_SIDE and T <= nx <= INGEST_MAX_SIDE):
+        raise _lib.SprkError("psd_tiles: a %dx%d image with tiles of %d (tile <= ny <= %d and tile <= nx <= %d)"
+                             % (ny, nx, T, INGEST_MAX_SIDE, INGEST_MAX_SIDE))
+    if max_batch < 0:
+        raise _lib.SprkError("psd_tiles: max_batch %d (0 = the library's choice, or a positive number of tiles)" % max_batch)
+    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
+        raise _lib.SprkError("psd_tiles: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
+                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+    for name, m, shape in zip(("w1", "w2"), (w1, w2), psd_matrix_shapes(T)):
+        if m.dtype != torch.float32 or tuple(m.shape) != shape or m.device != raw.device:
+            raise _lib.SprkError("psd_tiles: %s must be the float32 matrix of ctf.dft_matrices(%d), [%d, %d] on %s, got %s %s "
+                                 "on %s" % (name, T, *shape, raw.device, m.dtype, tuple(m.shape), m.device))
+
+
+def _psd_tiles(raw, mode, ny, nx, T, w1, w2, max_batch):
+    """raw: uint8 CUDA tensor holding the file's ny*nx samples; w1, w2: ctf.dft_matrices(T, device) -> P float32
+    [T, T/2 + 1], the un-normalised sum of the tiles' power spectra."""
+    _psd_check(raw, mode, ny, nx, T, w1, w2, max_batch)
+    if not raw.is_contiguous() or not w1.is_contiguous() or not w2.is_contiguous():
+        raise _lib.SprkError("psd_tiles: raw, w1 and w2 must be contiguous")
+    L = _lib.lib()
+    out = _f32(raw, (T, T // 2 + 1))
+    ws = _ws(L.sprk_psd_tiles_ws_bytes(int(ny), int(nx), int(T), int(max_batch)), raw)
+    check(L.sprk_psd_tiles(_p(raw), int(mode), int(ny), int(nx), int(T), _p(w1), int(w1.shape[1]), _p(w2), int(w2.shape[1]),
+                           int(max_batch), _p(out), _p(ws), ws.numel(), _stream(raw)), "sprk_psd_tiles")
+    return out
+
+
+def _psd_tiles_fake(raw, mode, ny, nx, T, w1, w2, max_batch):
+    _psd_check(raw, mode, ny, nx, T, w1, w2, max_batch)
+    return raw.new_empty((T, T // 2 + 1), dtype=torch.float32)
+
+
+_register("psd_tiles", "(Tensor raw, int mode, int ny, int nx, int T, Tensor w1, Tensor w2, int max_batch) -> Tensor",
+          _psd_tiles, _psd_tiles_fake)
+
+
 def registered():
     """Names of the operators under torch.ops.sprk (tests)."""
     return tuple(_NAMES)
