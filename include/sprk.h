@@ -668,6 +668,26 @@ size_t sprk_psd_tiles_ws_bytes(int ny, int nx, int T, int max_batch);
 int sprk_psd_tiles(const void *raw, int mode, int ny, int nx, int T, const float *w1, int ldw1, const float *w2, int ldw2,
                    int max_batch, float *p_out, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- 2-D Thon-ring fit (`joint ctf --astigmatism`) -------------------------------------------
+ * sprk_ctf_score: for every candidate (d0, e1, e2) the three sums over n bins of the spectrum from which the host forms a
+ * Pearson correlation (spr_pick_amd.ctf.score).  bins fp32 [5, ldb] on the device: rows b, p, q, r, Y of
+ * spr_pick_amd.ctf.fit_bins, columns 0 .. n-1 read (what lies past them may be anything, NaNs included); cand fp32
+ * [ncand, 3] contiguous.  1 <= n <= 2^20, 1 <= ncand <= 2^24, ldb >= n a multiple of 4.  Per bin i and candidate c:
+ *   t = fmaf(r[i], e2, fmaf(q[i], e1, fmaf(p[i], d0, b[i])))   in fp32 (the phase of cos 2 chi in turns);
+ *   x = cospif(2 t)                                            in fp32: |x - cos(2 pi t)| <= 2^-22;
+ *   S1 += x, S2 += x * x, S3 += Y[i] * x                       in fp64, the products of two converted floats exact.
+ * out fp64 [ncand, 3] = (S1, S2, S3).  The bins are cut into slices of consecutive bins, their number a function of n and
+ * ncand alone; a slice is summed in ascending bin order from 0.0 (straight into out when there is only one), the slices'
+ * sums, held in the workspace, are added in ascending slice order from 0.0.  No atomics: the bits do not depend on
+ * scheduling.  Nothing uninitialised is read into a stored value: the workspace may hold anything.
+ * Refused (SPRK_EINVAL, nothing launched): sizes outside the limits, ldb below n or not a multiple of 4, null or
+ * misaligned pointers (bins, cand, out and ws 16-byte aligned); a short workspace: SPRK_EWORKSPACE (sprk_ctf_score_ws_bytes
+ * is 0 where one slice does, and for sizes that are refused).
+ * One or two launches on `stream`, no host synchronisation. */
+size_t sprk_ctf_score_ws_bytes(int n, int ncand);
+int sprk_ctf_score(const float *bins, int ldb, int n, const float *cand, int ncand, double *out, void *ws, size_t ws_bytes,
+                   void *stream);
+
 /* ---- particle extraction (`joint extract`) -----------------------------------------------
  * Boxes cut out of ONE raw micrograph (the buffer sprk_ingest_bin takes: [ny,nx] samples of mode 0 / 1 / 2 / 6, 16-byte
  * aligned start), binned, background-normalised and optionally inverted: out [P, b, b] fp32 with b = box / bin, status [P].

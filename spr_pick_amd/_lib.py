@@ -137,6 +137,8 @@ _SIGS = {
     "sprk_ingest_resample": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_f, c_f, c_vp, c_sz, c_vp]),
     "sprk_psd_tiles_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "sprk_psd_tiles": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i, c_f, c_vp, c_sz, c_vp]),
+    "sprk_ctf_score_ws_bytes": (c_sz, [c_i, c_i]),
+    "sprk_ctf_score": (c_i, [c_f, c_i, c_i, c_f, c_i, c_vp, c_vp, c_sz, c_vp]),
     "sprk_extract_boxes": (c_i, [c_vp, c_i, c_i, c_i, c_vp, c_i, c_i, c_i, c_i, c_i, c_f, c_vp, c_vp]),
     "sprk_extract_scale": (c_i, [c_vp, c_i, c_i, c_i, c_vp, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_f, c_vp, c_vp]),
     "sprk_gather_patches": (c_i, [c_vp, c_i, c_vp, c_vp, c_vp, c_f, c_i, c_i, c_i, c_vp]),

@@ -2,7 +2,8 @@
 reference): ``joint train start|resume`` and ``joint eval`` with the same flags and the same
 flag -> configuration mapping, plus ``joint bin`` (the README's ``newstack -bin`` preparation, on the GPU), ``joint extract``
 (particle stacks from the pick tables and the raw micrographs, on the GPU) and ``joint ctf`` (tiled power spectra of the raw
-micrographs on the GPU, one fitted defocus each, ``micrographs_ctf.star`` for ``joint extract --ctf``).  Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
+micrographs on the GPU, one fitted defocus each, or with ``--astigmatism`` two and an angle, ``micrographs_ctf.star`` for
+``joint extract --ctf``).  Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
 under ``python -m torch.distributed.run --nproc-per-node N -m spr_pick_amd -- ...`` (keep the ``--``)."""
 import argparse
 
@@ -119,6 +120,11 @@ def _check_ctf(ns):
     from .ctf import check_fit_args, check_tile
     check_tile(ns.tile)
     check_fit_args(ns.apix, ns.kv, ns.cs, ns.ac, ns.min_res, ns.max_res, ns.min_defocus, ns.max_defocus)
+    if ns.max_astigmatism is not None and not ns.astigmatism:
+        raise ValueError("--max_astigmatism belongs to the 2-D fit: give --astigmatism as well")
+    if ns.astigmatism:
+        from .ctf import MAX_ASTIGMATISM, check_astigmatism
+        check_astigmatism(MAX_ASTIGMATISM if ns.max_astigmatism is None else ns.max_astigmatism, ns.min_defocus)
 
 
 def build_parser():
@@ -214,8 +220,9 @@ def build_parser():
     ex.check = _check_extract
 
     cf = cmds.add_parser("ctf", help="Power spectra of raw micrographs on the GPU and one defocus value each "
-                                     "(replaces a CTFFIND / Gctf run before 2-D classification; astigmatism is NOT fitted: "
-                                     "DefocusU = DefocusV, angle 0).")
+                                     "(replaces a CTFFIND / Gctf run before 2-D classification); with --astigmatism a 2-D fit "
+                                     "of DefocusU, DefocusV and the angle, scored on the GPU (without it DefocusU = "
+                                     "DefocusV, angle 0).")
     cf.add_argument("--dataset", "-d", required=True, help="Table (image_name, path) or directory of raw MRC micrographs.")
     cf.add_argument("--out", "-o", required=True,
                     help="Directory for {name}_psd.mrc, {name}_profile.txt and micrographs_ctf.star.")
@@ -230,6 +237,12 @@ def build_parser():
     cf.add_argument("--max_res", type=float, metavar="R", help="finest resolution fitted, Angstrom (default max(4, 2.2 A))")
     cf.add_argument("--min_defocus", type=float, default=3000, metavar="D", help="lowest defocus searched, Angstrom (default 3000)")
     cf.add_argument("--max_defocus", type=float, default=50000, metavar="D", help="highest defocus searched, Angstrom (default 50000)")
+    cf.add_argument("--astigmatism", action="store_true",
+                    help="fit DefocusU, DefocusV and DefocusAngle to the 2-D spectrum (candidates around the 1-D fit scored on "
+                         "the GPU); _rlnCtfFigureOfMerit is then the 2-D score")
+    cf.add_argument("--max_astigmatism", type=float, metavar="A",
+                    help="largest (DefocusU - DefocusV) / 2 searched, Angstrom (default 1000; needs --astigmatism, and "
+                         "A + 550 < --min_defocus)")
     cf.check = _check_ctf
     return parser
 
@@ -313,7 +326,9 @@ def run_ctf(args):
     from . import ctf
     res = ctf.ctf_dataset(args["dataset"], args["out"], apix=args.get("apix"), kv=args["kv"], cs=args["cs"], ac=args["ac"],
                           tile=args["tile"], min_res=args["min_res"], max_res=args.get("max_res"),
-                          min_defocus=args["min_defocus"], max_defocus=args["max_defocus"])
+                          min_defocus=args["min_defocus"], max_defocus=args["max_defocus"],
+                          **({"astigmatism": True, "max_astigmatism": args["max_astigmatism"] or ctf.MAX_ASTIGMATISM}
+                             if args.get("astigmatism") else {}))
     print(json.dumps({"micrographs": res}))
     return res
 

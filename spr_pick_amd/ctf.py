@@ -10,8 +10,12 @@ than T/2 samples on either axis is not covered; nothing is tapered and no mean i
 nearest neighbours carry the image's offset and are not used.  Everything after that is NumPy float64 on the T x (T/2+1)
 numbers of the spectrum and needs no GPU.
 
-Astigmatism is NOT fitted: the table carries DefocusU = DefocusV and an angle of 0.  Phase plates, per-particle defocus
-and CTF correction are out of scope."""
+By default astigmatism is not fitted: the table carries DefocusU = DefocusV and an angle of 0.  With ``astigmatism=True``
+(``joint ctf --astigmatism``) ``fit_astigmatism`` fits DefocusU, DefocusV and the angle to the 2-D spectrum
+around the 1-D fit: the host prepares five numbers per bin (``fit_bins``) and the candidates, ``torch.ops.sprk.ctf_score``
+(csrc/ctffit.hip) evaluates cos 2 chi of every bin for every candidate and returns three float64 sums each, and the host
+turns them into a Pearson correlation (``score``).  Phase plates, per-particle defocus and CTF correction are out of
+scope."""
 import logging
 import math
 import os
@@ -29,6 +33,8 @@ CTF_STAR_HEADER = "# version 30001\n\ndata_\n\nloop_\n" + "".join("_rln%s #%d\n"
                                                                    for k, c in enumerate(CTF_STAR_COLUMNS))
 MAGNIFICATION = 10000.0                          # with it _rlnDetectorPixelSize (micrometres) is the pixel size in Angstrom
 COARSE_STEP, FINE_STEP = 100.0, 5.0              # Angstrom: the two grids of fit_defocus
+MAX_ASTIGMATISM = 1000.0                         # Angstrom: the default radius of fit_astigmatism's search in (e1, e2)
+ASTIG_STEP, ASTIG_RANGE = 50.0, 500.0            # fit_astigmatism's coarse grid: the step of all three, the range of d0 - D_ref
 
 
 # ---- the device part ---------------------------------------------------------------------------------------------------
@@ -228,6 +234,125 @@ def fit_defocus(profile, T, apix, kv=300.0, cs=2.7, ac=0.07, min_res=30.0, max_r
     return float(fine[i]), float(scores[i])
 
 
+# ---- the 2-D fit: astigmatism ---------------------------------------------------------------------------
+# RELION's convention: dz(phi) = d0 + d1 cos(2 (phi - theta)), d0 = (U + V) / 2, d1 = (U - V) / 2 >= 0, phi = atan2(u', v)
+# with u' the signed row frequency and v the column frequency of the stored half plane.  With e1 = d1 cos 2 theta and e2 =
+# d1 sin 2 theta the phase of cos 2 chi, in turns, is linear in the candidate: t = b + p (d0 - D_ref) + q e1 + r e2.
+def check_astigmatism(max_astigmatism, min_defocus):
+    """ValueError unless 0 < max_astigmatism < inf and DefocusV stays positive over the whole search"""
+    if not (np.isfinite(max_astigmatism) and max_astigmatism > 0):
+        raise ValueError("max_astigmatism must be positive and finite, got %r" % (max_astigmatism,))
+    if max_astigmatism + ASTIG_RANGE + ASTIG_STEP >= min_defocus:
+        raise ValueError("max_astigmatism %r + %g reaches min_defocus %r: DefocusV could not stay positive"
+                         % (max_astigmatism, ASTIG_RANGE + ASTIG_STEP, min_defocus))
+
+
+def fit_bins(Pm, profile, T, apix, kv, cs, ac, min_res, max_res, d_ref):
+    """The operand of ``torch.ops.sprk.ctf_score``: float32 [5, n], rows b, p, q, r, Y, computed in float64 and rounded
+    once, one column per kept bin of the half plane Pm [T, T/2 + 1] in row-major order.  A bin is kept when its ring
+    ``radial_bins(T)`` lies in ``fit_range`` and neither u' nor v is 0 (the two axes carry the cross the untapered tile
+    edges leave).  p = lambda s^2, q = p cos 2 phi, r = p sin 2 phi, b = frac(-Cs lambda^3 s^4 / 2 + atan2(ac, sqrt(1 -
+    ac^2)) / pi + p d_ref): with the 1-D fit's defocus folded in here, |t| stays within a few tens of turns.  Y = log Pm
+    minus the running mean of the log radial profile at the bin's ring (the trend ``_detrend`` subtracts in the 1-D fit:
+    the same window), centred over the kept bins."""
+    Pm = np.asarray(Pm, dtype=np.float64)
+    if Pm.shape != (T, T // 2 + 1):
+        raise ValueError("a half-plane spectrum [%d, %d] is expected, got %s" % (T, T // 2 + 1, Pm.shape))
+    kf = fit_range(T, apix, min_res, max_res)
+    u = np.arange(T, dtype=np.int64)
+    u = np.where(u > T // 2, u - T, u)[:, None]
+    v = np.arange(T // 2 + 1, dtype=np.int64)[None, :]
+    k = radial_bins(T)
+    keep = (k >= kf[0]) & (k <= kf[-1]) & (u != 0) & (v != 0)
+    uu, vv = np.broadcast_to(u, k.shape)[keep].astype(np.float64), np.broadcast_to(v, k.shape)[keep].astype(np.float64)
+    power = Pm[keep]
+    if not (np.isfinite(power).all() and (power > 0).all()):
+        raise ValueError("the spectrum must be positive and finite over the fitted bins")
+    logp = np.log(np.asarray(profile, dtype=np.float64)[kf])
+    if not np.isfinite(logp).all():
+        raise ValueError("the radial profile must be positive and finite over the fitted rings")
+    w = max(1, len(kf) // 8)
+    trend = _running_mean(logp, w)
+    lam, csa = wavelength(kv), cs * 1e7
+    s2 = (uu * uu + vv * vv) / (T * float(apix)) ** 2
+    phi2 = 2.0 * np.arctan2(uu, vv)
+    p = lam * s2
+    b = -0.5 * csa * lam ** 3 * s2 * s2 + math.atan2(ac, math.sqrt(1 - ac * ac)) / math.pi + p * float(d_ref)
+    Y = np.log(power) - trend[k[keep] - kf[0]]
+    return np.stack([b - np.floor(b), p, p * np.cos(phi2), p * np.sin(phi2), Y - Y.mean()]).astype(np.float32)
+
+
+def _running_mean(y, w):
+    """the mean of y over w bins on either side, the window clamped at the ends: what ``_detrend`` subtracts"""
+    n = len(y)
+    csum = np.concatenate([[0.0], np.cumsum(y)])
+    lo, hi = np.maximum(np.arange(n) - w, 0), np.minimum(np.arange(n) + w + 1, n)
+    return (csum[hi] - csum[lo]) / (hi - lo)
+
+
+def score(S, Y):
+    """S float64 [ncand, 3] = (sum c, sum c^2, sum Y c) over the n bins, c = cos 2 pi t -> the Pearson correlation of Y with
+    -c per candidate, float64 [ncand]; 0 where a variance is not positive"""
+    S = np.asarray(S, dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    n = Y.size
+    sy, syy = Y.sum(), (Y * Y).sum()
+    var = (S[:, 1] - S[:, 0] ** 2 / n) * (syy - sy * sy / n)
+    ok = var > 0
+    return np.where(ok, -(S[:, 2] - S[:, 0] * sy / n) / np.sqrt(np.where(ok, var, 1.0)), 0.0)
+
+
+def device_sums(bins, cand, device="cuda"):
+    """``torch.ops.sprk.ctf_score`` on float32 NumPy arrays [5, n] and [ncand, 3] -> float64 [ncand, 3]"""
+    b = torch.from_numpy(np.array(bins, dtype=np.float32, order="C"))      # a copy: the caller's may be read-only
+    pad = -b.shape[1] % 4                                        # the operator wants a row stride that is a multiple of 4
+    b = torch.nn.functional.pad(b, (0, pad)).to(device)[:, :b.shape[1]]
+    c = torch.from_numpy(np.array(cand, dtype=np.float32, order="C")).to(device)
+    return torch.ops.sprk.ctf_score(b, c).cpu().numpy()
+
+
+def astigmatism_grids(max_astigmatism):
+    """-> (coarse float64 [m, 3], fine offsets float64 [9261, 3]) in (d0 - D_ref, e1, e2): d0 outermost, e2 innermost,
+    ascending.  Coarse: d0 over -500 .. 500, e1 and e2 over the multiples of 50 within max_astigmatism, kept inside the
+    circle e1^2 + e2^2 <= max_astigmatism^2; fine: steps of 5 over -50 .. 50 in all three."""
+    m = int(math.floor(max_astigmatism / ASTIG_STEP))
+    e = ASTIG_STEP * np.arange(-m, m + 1)
+    d = ASTIG_STEP * np.arange(-round(ASTIG_RANGE / ASTIG_STEP), round(ASTIG_RANGE / ASTIG_STEP) + 1)
+    g = np.stack(np.meshgrid(d, e, e, indexing="ij"), axis=-1).reshape(-1, 3)
+    coarse = g[g[:, 1] ** 2 + g[:, 2] ** 2 <= max_astigmatism ** 2]
+    f = FINE_STEP * np.arange(-round(ASTIG_STEP / FINE_STEP), round(ASTIG_STEP / FINE_STEP) + 1)
+    return coarse, np.stack(np.meshgrid(f, f, f, indexing="ij"), axis=-1).reshape(-1, 3)
+
+
+def fit_astigmatism(Pm, T, apix, kv=300.0, cs=2.7, ac=0.07, min_res=30.0, max_res=None, min_defocus=3000.0,
+                    max_defocus=50000.0, max_astigmatism=MAX_ASTIGMATISM, sums=None):
+    """DefocusU, DefocusV and the angle for a mean power spectrum Pm [T, T/2 + 1]: the 1-D fit of its radial profile gives
+    D_ref; every candidate (d0 - D_ref, e1, e2) of ``astigmatism_grids`` is scored by the correlation of the detrended log
+    spectrum with -cos 2 chi over the bins of ``fit_bins``, first the coarse grid, then the fine one around its best.  The
+    first of equal scores wins.  ``sums(bins, cand) -> float64 [ncand, 3]`` does the work: ``device_sums`` by default, a
+    NumPy model for a caller without a GPU.
+    -> (defocus_u, defocus_v, angle in degrees in [0, 180), score)."""
+    if max_res is None:
+        max_res = max(4.0, 2.2 * apix)
+    check_fit_args(apix, kv, cs, ac, min_res, max_res, min_defocus, max_defocus)
+    check_astigmatism(max_astigmatism, min_defocus)
+    profile = radial_profile(Pm)
+    d_ref, _ = fit_defocus(profile, T, apix, kv, cs, ac, min_res, max_res, min_defocus, max_defocus)
+    bins = fit_bins(Pm, profile, T, apix, kv, cs, ac, min_res, max_res, d_ref)
+    sums = device_sums if sums is None else sums
+    coarse, fine = astigmatism_grids(float(max_astigmatism))
+    best = coarse[int(np.argmax(score(sums(bins, coarse.astype(np.float32)), bins[4])))]
+    fine = best + fine
+    scores = score(sums(bins, fine.astype(np.float32)), bins[4])
+    i = int(np.argmax(scores))
+    d0, e1, e2 = d_ref + fine[i, 0], fine[i, 1], fine[i, 2]
+    d1 = math.hypot(e1, e2)
+    angle = math.degrees(0.5 * math.atan2(e2, e1)) % 180.0 if d1 > 0 else 0.0
+    if angle >= 180.0:                                           # a tiny negative angle rounds up to the modulus
+        angle = 0.0
+    return float(d0 + d1), float(d0 - d1), float(angle), float(scores[i])
+
+
 # ---- `joint ctf` ---------------------------------------------------------------------------------------------------------
 def header_apix(header):
     """the pixel size an MRC header states, xlen / mx, or None when it states none: no sampling or no cell length, or the
@@ -239,9 +364,10 @@ def header_apix(header):
     return float(header.xlen) / header.mx
 
 
-def star_row(name, defocus, score, apix, kv, cs, ac):
-    return "%s\t%.2f\t%.2f\t%.2f\t%.2f\t%.4f\t%.4f\t%.2f\t%.5f\t%.6f\n" % (name, defocus, defocus, 0.0, kv, cs, ac,
-                                                                           MAGNIFICATION, apix, score)
+def star_row(name, defocus, score, apix, kv, cs, ac, defocus_v=None, angle=0.0):
+    """one row of micrographs_ctf.star; ``defocus`` is DefocusU, and DefocusV as well unless ``defocus_v`` is given"""
+    return "%s\t%.2f\t%.2f\t%.2f\t%.2f\t%.4f\t%.4f\t%.2f\t%.5f\t%.6f\n" % (
+        name, defocus, defocus if defocus_v is None else defocus_v, angle, kv, cs, ac, MAGNIFICATION, apix, score)
 
 
 def write_profile(path, profile, T, apix, k_fit, residual, model):
@@ -256,15 +382,20 @@ def write_profile(path, profile, T, apix, k_fit, residual, model):
 
 
 def ctf_dataset(dataset, out_dir, apix=None, kv=300.0, cs=2.7, ac=0.07, tile=512, min_res=30.0, max_res=None,
-                min_defocus=3000.0, max_defocus=50000.0, device="cuda"):
+                min_defocus=3000.0, max_defocus=50000.0, device="cuda", astigmatism=False, max_astigmatism=MAX_ASTIGMATISM):
     """``joint ctf``: for every raw MRC micrograph of the table / directory ``dataset``: ``out_dir/{name}_psd.mrc`` (the
     mean power spectrum, float32 [T, T/2 + 1]), ``out_dir/{name}_profile.txt`` and one row of
     ``out_dir/micrographs_ctf.star``, written at the end.  ``apix``: Angstrom per pixel, from each file's header (xlen /
     mx) when None.  Runs in one process: the per-micrograph work is a millisecond of device time and the rest is the read
     of the file, so the table is not spread over ranks (WORLD_SIZE is ignored).
-    -> {name: {"defocus", "score", "apix", "tiles"}}."""
+    ``astigmatism``: the row carries DefocusU, DefocusV, the angle and the score of ``fit_astigmatism`` (candidates within
+    ``max_astigmatism`` Angstrom of half-difference) in place of the 1-D fit's; the other two files stay as they are.
+    -> {name: {"defocus", "score", "apix", "tiles"}}, with ``astigmatism`` also "defocus_u", "defocus_v", "angle" and
+    "score_2d"."""
     T = check_tile(tile)
     check_fit_args(apix, kv, cs, ac, min_res, max_res, min_defocus, max_defocus)
+    if astigmatism:
+        check_astigmatism(max_astigmatism, min_defocus)
     rows = micrograph_io.read_image_table(dataset)
     if not rows:
         raise ValueError("no micrographs found in %s" % dataset)
@@ -285,8 +416,14 @@ def ctf_dataset(dataset, out_dir, apix=None, kv=300.0, cs=2.7, ac=0.07, tile=512
             micrograph_io.write_mrc(f, Pm.astype(np.float32))
         k_fit, residual, model = fit_curves(profile, T, a, kv, cs, ac, min_res, res, defocus)
         write_profile(os.path.join(out_dir, name + "_profile.txt"), profile, T, a, k_fit, residual, model)
-        star.append(star_row(os.path.basename(path), defocus, score, a, kv, cs, ac))
         results[name] = {"defocus": defocus, "score": score, "apix": a, "tiles": ntiles}
+        if astigmatism:
+            du, dv, angle, score2 = fit_astigmatism(Pm, T, a, kv, cs, ac, min_res, res, min_defocus, max_defocus, max_astigmatism,
+                                                    sums=lambda b, c: device_sums(b, c, device))
+            star.append(star_row(os.path.basename(path), du, score2, a, kv, cs, ac, dv, angle))
+            results[name].update(defocus_u=du, defocus_v=dv, angle=angle, score_2d=score2)
+        else:
+            star.append(star_row(os.path.basename(path), defocus, score, a, kv, cs, ac))
     with open(os.path.join(out_dir, "micrographs_ctf.star"), "w") as f:
         f.write(CTF_STAR_HEADER)
         f.writelines(star)

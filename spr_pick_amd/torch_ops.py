@@ -901,6 +901,52 @@ _register("psd_tiles", "(Tensor raw, int mode, int ny, int nx, int T, Tensor w1,
           _psd_tiles, _psd_tiles_fake)
 
 
+# ---- scores of the 2-D Thon-ring fit (ctf.py: bins of the spectrum x candidates -> three fp64 sums each) --------------------
+CTF_MAX_BINS, CTF_MAX_CAND = 1 << 20, 1 << 24    # sprk_ctf_score
+
+
+def _ctf_check(bins, cand):
+    if bins.dtype != torch.float32 or bins.dim() != 2 or bins.shape[0] != 5:
+        raise _lib.SprkError("ctf_score: bins must be float32 [5, n] (ctf.fit_bins), got %s %s" % (bins.dtype, tuple(bins.shape)))
+    if cand.dtype != torch.float32 or cand.dim() != 2 or cand.shape[1] != 3 or cand.device != bins.device:
+        raise _lib.SprkError("ctf_score: cand must be float32 [ncand, 3] on %s, got %s %s on %s"
+                             % (bins.device, cand.dtype, tuple(cand.shape), cand.device))
+    n, ncand = bins.shape[1], cand.shape[0]
+    if not (1 <= n <= CTF_MAX_BINS and 1 <= ncand <= CTF_MAX_CAND):
+        raise _lib.SprkError("ctf_score: %d bins and %d candidates (1 <= bins <= %d, 1 <= candidates <= %d)"
+                             % (n, ncand, CTF_MAX_BINS, CTF_MAX_CAND))
+    ldb = bins.stride(0)
+    if bins.stride(1) != 1 or ldb < n or ldb % 4:
+        raise _lib.SprkError("ctf_score: the rows of bins must be dense, their stride %d a multiple of 4 and at least the "
+                             "%d bins (strides %s)" % (ldb, n, tuple(bins.stride())))
+    if not cand.is_contiguous():
+        raise _lib.SprkError("ctf_score: cand must be contiguous")
+
+
+def _ctf_score(bins, cand):
+    """bins: float32 CUDA [5, n] (rows b, p, q, r, Y; a view of a wider buffer may have a row stride above n); cand: float32
+    [ncand, 3] -> float64 [ncand, 3]: S1, S2, S3 of include/sprk.h."""
+    _ctf_check(bins, cand)
+    if bins.data_ptr() % 16 or cand.data_ptr() % 16:
+        raise _lib.SprkError("ctf_score: bins and cand must start 16-byte aligned")
+    L = _lib.lib()
+    n, ncand = int(bins.shape[1]), int(cand.shape[0])
+    out = torch.empty((ncand, 3), dtype=torch.float64, device=bins.device)
+    need = L.sprk_ctf_score_ws_bytes(n, ncand)
+    ws = _ws(need, bins)
+    check(L.sprk_ctf_score(_p(bins), int(bins.stride(0)), n, _p(cand), ncand, _p(out), _p(ws), ws.numel(), _stream(bins)),
+          "sprk_ctf_score")
+    return out
+
+
+def _ctf_score_fake(bins, cand):
+    _ctf_check(bins, cand)
+    return bins.new_empty((cand.shape[0], 3), dtype=torch.float64)
+
+
+_register("ctf_score", "(Tensor bins, Tensor cand) -> Tensor", _ctf_score, _ctf_score_fake)
+
+
 def registered():
     """Names of the operators under torch.ops.sprk (tests)."""
     return tuple(_NAMES)
