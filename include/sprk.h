@@ -133,6 +133,12 @@ long sprk_wgrad1x1_launch_count(void);
 /* process-wide host switch of that stage (default on, never read from the environment): off, those calls keep
  * conv_wgrad_mfma_kernel (SPRK_STAGE_MFMA) and compute the same bits */
 void sprk_wgrad1x1_enable(int on);
+/* number of backward-weight calls of 3x3 layers on chunks of 48 input channels that took the streaming kernel
+ * (SPRK_STAGE_WGRAD3X3; diagnostics / tests) */
+long sprk_wgrad3x3_launch_count(void);
+/* process-wide host switch of that stage (default on, never read from the environment): off, those calls keep
+ * conv_wgrad_mfma_kernel (SPRK_STAGE_MFMA) and compute the same bits */
+void sprk_wgrad3x3_enable(int on);
 /* number of convolution launches (forward, backward-data or backward-weight) that ran on the 16-bit-operand
  * kernels (diagnostics / tests) */
 long sprk_conv16_launch_count(void);
@@ -203,7 +209,7 @@ int sprk_conv2d_bwd_weight(const float *x, const float *x2, const float *gy, flo
  * SPRK_VARIANT_INTS integers.  x, x2: the layer's inputs (backward-data: x is gin, the tensor written); y_or_gy: y for
  * the forward call, gy otherwise.  The pointers are tested for 16-byte alignment only, never dereferenced.  Without a
  * device the plans are those of a 256-CU device (the MI355X).
- *   out[0] = stage, SPRK_STAGE_*; the other fields are filled by the stages that plan (MASK1X1, MFMA, GEMM1X1, WGRAD1X1: the two lists that
+ *   out[0] = stage, SPRK_STAGE_*; the other fields are filled by the stages that plan (MASK1X1, MFMA, GEMM1X1, WGRAD1X1, WGRAD3X3: the two lists that
  *   follow), by the Winograd stage (the two lists after them) and by the 16-bit stage (the last two), else 0
  *   which 0 / 1: [1] MT [2] NT [3] RB [4] XTAB [5] chunk_mma_small [6] K stages (1 | 2) [7] ragged last K-chunk
  *                [8] latency-bound re-chunking of K [9] vec1 [10] vec2 [11] vec4 [12] colOff != 0 [13] up1 [14] C2 > 0
@@ -265,6 +271,7 @@ int sprk_conv2d_bwd_weight(const float *x, const float *x2, const float *gy, flo
 #define SPRK_STAGE_MFMA 5
 #define SPRK_STAGE_GEMM1X1 6     /* gemm1x1_kernel (csrc/gemm1x1.hip) on the MFMA stage's plan and slabs: the record is that plan's */
 #define SPRK_STAGE_WGRAD1X1 7    /* backward-weight: wgrad1x1_kernel (csrc/wgrad1x1.hip) on the MFMA stage's plan: the record is that plan's */
+#define SPRK_STAGE_WGRAD3X3 8    /* backward-weight: wgrad3x3_kernel (csrc/wgrad3x3.hip) on the MFMA stage's plan: the record is that plan's */
 int sprk_conv2d_variant(int which, const sprk_conv_geom *g, const sprk_conv_epilogue *ep, const void *x, const void *x2,
                         const void *y_or_gy, int32_t *out);
 int sprk_conv2d_last_variant(int which, int32_t *out);

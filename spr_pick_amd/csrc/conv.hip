@@ -22,6 +22,7 @@
 #include "mask1x1.h"
 #include "wgrad16.h"
 #include "wgrad1x1.h"
+#include "wgrad3x3.h"
 #include "wino.h"
 #include "wprep_dev.h"
 
@@ -1986,6 +1987,19 @@ static bool wgrad1x1_takes(const sprk_conv_geom *g, const WgPlan &p, const WgVar
            rows64 && (long)sprk::kWgrad1x1Rows * H * W * 4 < (1L << 31);
 }
 
+// Stage 8: may the call of layer g, planned as p and routed to conv_wgrad_mfma_kernel as v, run on wgrad3x3_kernel
+// (wgrad3x3.hip) instead?  An fp32 3x3 stride-1 same-size call in MODE 2 (x, x2 and gy 16-byte aligned, 32-bit offsets)
+// whose plan has chunks of 48 input channels (27 k-tiles: IT = 7; none straddles the two sources) and blocks of 3 or 6
+// output tiles, over planes of 16, 32 or 64 columns and whole tiles of 4, 2 or 1 rows.
+static bool wgrad3x3_takes(const sprk_conv_geom *g, const WgPlan &p, const WgVariant &v) {
+    return sprk::g_wgrad3x3_on.load(std::memory_order_relaxed) && (g->dtype & SPRK_DT_MASK) == SPRK_DT_F32 &&
+           !(g->dtype & (SPRK_DT_X16 | SPRK_DT_Y16)) && !naive_of(g) && g->KH == 3 && g->KW == 3 && g->stride == 1 &&
+           g->dil == 1 && !g->up1 && g->Hin == g->Hout && g->Win == g->Wout && g->pad_top >= 0 && g->pad_top <= 2 &&
+           g->pad_left >= 0 && g->pad_left <= 2 && v.stage == SPRK_STAGE_MFMA && v.MODE == 2 && p.IT == 7 &&
+           (p.NT == 3 || p.NT == 6) && p.CKW == sprk::kWgrad3x3Chunk && g->C1 % p.CKW == 0 && g->C2 % p.CKW == 0 &&
+           sprk::wgrad3x3_plane(g->Hout, g->Wout) && (1 << p.lgTC) == g->Wout && (64 >> p.lgTC) == (1 << p.lgTR);
+}
+
 // Which stage of wgrad_dispatch takes the call, by the stages' own predicates in the dispatcher's order, and for the
 // MFMA stage the plan and the kernel variant: the twin of fwd_route.
 static WgVariant wg_route(const sprk_conv_geom *g, const void *x, const void *x2, const void *gy, WgPlan *p) {
@@ -2006,6 +2020,7 @@ static WgVariant wg_route(const sprk_conv_geom *g, const void *x, const void *x2
         v = wg_variant(g, *p, x, x2, gy, &refused);
         v.stage = refused ? SPRK_STAGE_REFUSED : SPRK_STAGE_MFMA;
         if (wgrad1x1_takes(g, *p, v)) v.stage = SPRK_STAGE_WGRAD1X1;
+        else if (wgrad3x3_takes(g, *p, v)) v.stage = SPRK_STAGE_WGRAD3X3;
     }
     return v;
 }
@@ -2015,7 +2030,8 @@ static WgVariant wg_route(const sprk_conv_geom *g, const void *x, const void *x2
 // "The convolution dispatcher").  item == nullptr: finish the sum over the partial buffers now; otherwise describe it in
 // *item (sprk.h).  The stages, in order:
 //   direct kernel (SPRK_DT_NAIVE) -> 16-bit operands -> storage guard -> Winograd -> MFMA (-> direct: no plan fits LDS),
-//   whose wide 1x1 row-form calls leave for wgrad1x1_kernel on the same plan (SPRK_STAGE_WGRAD1X1)
+//   whose wide 1x1 row-form calls leave for wgrad1x1_kernel on the same plan (SPRK_STAGE_WGRAD1X1), and whose 3x3 calls
+//   on chunks of 48 channels for wgrad3x3_kernel (SPRK_STAGE_WGRAD3X3)
 static int wgrad_dispatch(const float *x, const float *x2, const float *gy, float *gw, const sprk_conv_geom *g, void *ws,
                           size_t ws_bytes, sprk_reduce_item *item, void *stream) {
     const char *who = "conv2d_bwd_weight";
@@ -2057,6 +2073,14 @@ static int wgrad_dispatch(const float *x, const float *x2, const float *gy, floa
         if (int rc = sprk::wgrad1x1_run(c, s)) return rc;
         sprk::prof_end(1, s);
         if (int rc2 = sprk::check_launch("wgrad1x1")) return rc2;
+    } else if (v.stage == SPRK_STAGE_WGRAD3X3) {
+        // the same split, slabs and reduction item as the MFMA stage below
+        const sprk::Wgrad3x3Call c{x, x2, gy, wsf + kZeroFloats, g->N, g->C1, g->C2, g->Cout, p.CoutP, g->Hout, g->Wout,
+                                   g->pad_top, g->pad_left, p.NT, p.nTiles, p.tilesPerGroup, p.groups, p.nChunks, p.nblkN};
+        sprk::prof_begin(1, sprk::conv_flops(*g), s);
+        if (int rc = sprk::wgrad3x3_run(c, s)) return rc;
+        sprk::prof_end(1, s);
+        if (int rc2 = sprk::check_launch("wgrad3x3")) return rc2;
     } else {
         WgArgs a;
         if (int rc = wgrad_args(g, p, v, x, x2, gy, wsf, a)) return rc;

@@ -5,6 +5,7 @@
 #include "conv16.h"
 #include "gemm1x1.h"
 #include "wgrad1x1.h"
+#include "wgrad3x3.h"
 #include "wgrad16.h"
 
 #include <mutex>
@@ -311,6 +312,8 @@ long sprk_gemm1x1_launch_count(void) { return sprk::g_gemm1x1_launches.load(); }
 void sprk_gemm1x1_enable(int on) { sprk::g_gemm1x1_on.store(on ? 1 : 0); }
 long sprk_wgrad1x1_launch_count(void) { return sprk::g_wgrad1x1_launches.load(); }
 void sprk_wgrad1x1_enable(int on) { sprk::g_wgrad1x1_on.store(on ? 1 : 0); }
+long sprk_wgrad3x3_launch_count(void) { return sprk::g_wgrad3x3_launches.load(); }
+void sprk_wgrad3x3_enable(int on) { sprk::g_wgrad3x3_on.store(on ? 1 : 0); }
 long sprk_conv16_launch_count(void) { return sprk::conv16_launches() + sprk::wgrad16_launches(); }
 long sprk_wgrad16_launch_count(void) { return sprk::wgrad16_launches(); }
 
