@@ -139,6 +139,12 @@ long sprk_wgrad3x3_launch_count(void);
 /* process-wide host switch of that stage (default on, never read from the environment): off, those calls keep
  * conv_wgrad_mfma_kernel (SPRK_STAGE_MFMA) and compute the same bits */
 void sprk_wgrad3x3_enable(int on);
+/* number of Winograd backward-weight calls (SPRK_STAGE_WINOGRAD) whose launches ran on wino_wgrad_stream_kernel
+ * (diagnostics / tests) */
+long sprk_wino_wgrad_stream_launch_count(void);
+/* process-wide host switch of that kernel (default on, never read from the environment): off, those calls keep
+ * wino_wgrad_kernel on the same launches and compute the same bits */
+void sprk_wino_wgrad_stream_enable(int on);
 /* number of convolution launches (forward, backward-data or backward-weight) that ran on the 16-bit-operand
  * kernels (diagnostics / tests) */
 long sprk_conv16_launch_count(void);

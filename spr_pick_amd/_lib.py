@@ -63,6 +63,8 @@ _SIGS = {
     "sprk_wgrad1x1_enable": (None, [c_i]),
     "sprk_wgrad3x3_launch_count": (ctypes.c_long, []),
     "sprk_wgrad3x3_enable": (None, [c_i]),
+    "sprk_wino_wgrad_stream_launch_count": (ctypes.c_long, []),
+    "sprk_wino_wgrad_stream_enable": (None, [c_i]),
     "sprk_conv16_launch_count": (ctypes.c_long, []),
     "sprk_wgrad16_launch_count": (ctypes.c_long, []),
     "sprk_conv2d_fwd_ws_bytes": (c_sz, [ctypes.POINTER(ConvGeom)]),

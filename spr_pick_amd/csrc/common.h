@@ -13,6 +13,9 @@ namespace sprk {
 
 void set_error(const char *fmt, ...);
 extern std::atomic<long> g_launches, g_wino_launches, g_mask1x1_launches;
+// wino_wgrad_stream_kernel (wino.hip): calls it ran, and its host switch (sprk_wino_wgrad_stream_*)
+extern std::atomic<long> g_wino_wgrad_stream_launches;
+extern std::atomic<int> g_wino_wgrad_stream_on;
 
 // event bracketing of the MFMA convolution launches (sprk_prof_*)
 void prof_begin(int kclass, double flops, hipStream_t s);

@@ -15,7 +15,8 @@
 namespace sprk {
 
 static thread_local char t_error[512] = "";
-std::atomic<long> g_launches{0}, g_wino_launches{0}, g_mask1x1_launches{0};
+std::atomic<long> g_launches{0}, g_wino_launches{0}, g_mask1x1_launches{0}, g_wino_wgrad_stream_launches{0};
+std::atomic<int> g_wino_wgrad_stream_on{1};
 
 void set_error(const char *fmt, ...) {
     va_list ap;
@@ -314,6 +315,8 @@ long sprk_wgrad1x1_launch_count(void) { return sprk::g_wgrad1x1_launches.load();
 void sprk_wgrad1x1_enable(int on) { sprk::g_wgrad1x1_on.store(on ? 1 : 0); }
 long sprk_wgrad3x3_launch_count(void) { return sprk::g_wgrad3x3_launches.load(); }
 void sprk_wgrad3x3_enable(int on) { sprk::g_wgrad3x3_on.store(on ? 1 : 0); }
+long sprk_wino_wgrad_stream_launch_count(void) { return sprk::g_wino_wgrad_stream_launches.load(); }
+void sprk_wino_wgrad_stream_enable(int on) { sprk::g_wino_wgrad_stream_on.store(on ? 1 : 0); }
 long sprk_conv16_launch_count(void) { return sprk::conv16_launches() + sprk::wgrad16_launches(); }
 long sprk_wgrad16_launch_count(void) { return sprk::wgrad16_launches(); }
 

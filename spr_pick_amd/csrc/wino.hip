@@ -572,10 +572,21 @@ struct WgKArgs {
     int N, Csrc, cbase, ci0, CinTot, H, W, Cout, padT, padL, regionsX, regionsY, xcd;   // cbase: first channel of group 0
 };
 
-template <int MT>
-__global__ __launch_bounds__(kThreads, 1) void wino_wgrad_kernel(const WgKArgs a) {
+// STREAM (wino_wgrad_stream_kernel): the same regions, operands, MFMA chains and final transform with the
+// operand reads rebuilt.  The raw tile sits padL & 1 floats further into its stage (the DMA's LDS base is only 4-byte
+// aligned, which buffer_load ... lds of 16 bytes per lane takes), so every lane's operand base is 8-byte aligned for any
+// padL and both operands are read with ds_read_b64, which the LDS banks mod 64: with the pitches PA = 4 * 109 | 4 * 37 and
+// WPB = 4 * 49 floats the 16 l15 lanes of a half sit on 16 different 4-bank slots and lq picks the half of the slot — no
+// conflict, where ds_read2_b32 (banked mod 32) put lanes l15 and l15 + 8 on one bank.  The raw operands of k-step i + 1 are
+// fetched in front of the MFMAs of k-step i, and the wave DMAs that lie wholly past a tile are not issued.
+template <int MT, bool STREAM>
+__device__ __forceinline__ void wino_wgrad_body(const WgKArgs &a) {
     constexpr int PA = 6 * MT * WRP + 4, NA4 = 16 * (PA / 4), NB4 = 32 * (WPB / 4);
     static_assert(16 * PA <= WAF && 32 * WPB <= WAF, "stage holds both operands");
+    // wave DMAs (64 lanes x 16 bytes) that hold a part of the tile; the shifted raw tile ends one float later
+    constexpr int SLA = (NA4 + 63) / 64, SLB = (NB4 + 63) / 64;
+    static_assert(SLA * 256 + 1 <= WAF, "the shifted raw tile stays in front of the gradient tile");
+    const int shift = STREAM ? (a.padL & 1) : 0;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l15 = lane & 15,
               lq = lane >> 4;
@@ -648,9 +659,12 @@ __global__ __launch_bounds__(kThreads, 1) void wino_wgrad_kernel(const WgKArgs a
         const rsrc_t ra = make_rsrc(xbase + cur_n * strideA + inimg), rb = make_rsrc(a.gy + cur_n * strideB + inimg);
 #pragma unroll
         for (int rd = 0; rd < 4; ++rd) {
-            const int m = __builtin_amdgcn_sbfe(mskA[rd], bit, 1);   // -1: inside the image
-            bdma16(ra, (offA[rd] & m) | (kXZero & ~m), 0, st + rd * 2048 + wave * 256);
-            bdma16(rb, offB[rd], 0, st + WAF + rd * 2048 + wave * 256);
+            if (!STREAM || rd * 8 + 7 < SLA || (rd * 8 < SLA && wave < SLA - rd * 8)) {
+                const int m = __builtin_amdgcn_sbfe(mskA[rd], bit, 1);   // -1: inside the image
+                bdma16(ra, (offA[rd] & m) | (kXZero & ~m), 0, st + shift + rd * 2048 + wave * 256);
+            }
+            if (!STREAM || rd * 8 + 7 < SLB || (rd * 8 < SLB && wave < SLB - rd * 8))
+                bdma16(rb, offB[rd], 0, st + WAF + rd * 2048 + wave * 256);
         }
         cur_rx += d_rx;
         const int cx = cur_rx >= RX;
@@ -677,20 +691,48 @@ __global__ __launch_bounds__(kThreads, 1) void wino_wgrad_kernel(const WgKArgs a
     int baseA[2], baseB2[2], baseB[2];
 #pragma unroll
     for (int sgi = 0; sgi < 2; ++sgi) {
-        baseA[sgi] = lds_addr(smem + sgi * WSTAGE + l15 * PA + ra_ * MT * WRP + (4 - a.padL) + 2 * lq);
-        baseB2[sgi] = lds_addr(smem + sgi * WSTAGE + l15 * PA + rb_ * MT * WRP + (4 - a.padL) + 2 * lq);
+        baseA[sgi] = lds_addr(smem + sgi * WSTAGE + l15 * PA + ra_ * MT * WRP + (4 - a.padL) + shift + 2 * lq);
+        baseB2[sgi] = lds_addr(smem + sgi * WSTAGE + l15 * PA + rb_ * MT * WRP + (4 - a.padL) + shift + 2 * lq);
         baseB[sgi] = lds_addr(smem + sgi * WSTAGE + WAF + (h * 16 + l15) * WPB + zrow * 48 + 2 * lq);
     }
     asm volatile("" : "+v"(baseA[0]), "+v"(baseA[1]), "+v"(baseB2[0]), "+v"(baseB2[1]), "+v"(baseB[0]), "+v"(baseB[1]));
 
+    // the raw operands of one k-step as the lane reads them from LDS: pairs of floats, 8-byte aligned in the STREAM
+    // layout and read as such
+    struct WgRaw {
+        f32x2 pa01[MT], pa23[MT], pb01[MT], pb23[MT], z[3], zz[3];
+    };
+    auto ld2 = [](lds_cfp p, int o) -> f32x2 {
+        // volatile: the compiler otherwise pairs neighbouring reads into ds_read2_b64, which is banked mod 32 per 16 lanes
+        // (two-way conflicts at these pitches) and takes 8 LDS cycles for what two ds_read_b64 do in 4
+        if constexpr (STREAM)
+            return *(const volatile __attribute__((address_space(3))) f32x2 *)(p + o);
+        else
+            return (f32x2){p[o], p[o + 1]};
+    };
     // zm: the wave mixes two gradient rows (pg 1, 2) or takes one (pg 0, 3) — a compile-time property of each copy of
     // the region loop (a run-time branch per channel tile and k-step cost 12 taken branches per region)
-    auto kstep = [&](auto stage, auto kstp, auto zm) {
+    auto fetch = [&](auto stage, auto kstp, auto zm, WgRaw &r) {
         constexpr int S = decltype(stage)::value, ks = decltype(kstp)::value;
         constexpr bool ZMIX = decltype(zm)::value != 0;
         constexpr int trow = ks >> 1, tcol = 8 * (ks & 1);   // tiles 4 ks .. 4 ks + 3: tile row, first column
         const lds_cfp pa = lds_f(baseA[S]), pb = lds_f(baseB2[S]), pz = lds_f(baseB[S]);
-        // Both transforms in PACKED fp32 (v_pk_fma_f32 / v_pk_add_f32 on the register pairs ds_read2_b32 returns, with
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const int o = mt * WRP + 2 * trow * MT * WRP + tcol;
+            r.pa01[mt] = ld2(pa, o), r.pa23[mt] = ld2(pa, o + 2);
+            r.pb01[mt] = ld2(pb, o), r.pb23[mt] = ld2(pb, o + 2);
+        }
+#pragma unroll
+        for (int nt = 0; nt < 3; ++nt) {
+            const int o = nt * 16 + 2 * trow * 48 + tcol;
+            r.z[nt] = ld2(pz, o);
+            if constexpr (ZMIX) r.zz[nt] = ld2(pz, o + 48);
+        }
+    };
+    auto compute = [&](auto zm, const WgRaw &r) {
+        constexpr bool ZMIX = decltype(zm)::value != 0;
+        // Both transforms in PACKED fp32 (v_pk_fma_f32 / v_pk_add_f32 on the register pairs the LDS reads return, with
         // op_sel / neg modifiers doing the shuffles and signs): 30-36 VALU instructions per 36 MFMAs were a quarter of
         // this loop's issue time; now 15-18.  Position 2 is carried NEGATED on both operands (x1 - x2 and z1 - z0), so the
         // products are unchanged.
@@ -698,9 +740,7 @@ __global__ __launch_bounds__(kThreads, 1) void wino_wgrad_kernel(const WgKArgs a
         const f32x2 sgn2 = {sgn, sgn}, zs2 = {zs, zs};
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            const int o = mt * WRP + 2 * trow * MT * WRP + tcol;
-            const f32x2 pa01 = {pa[o], pa[o + 1]}, pa23 = {pa[o + 2], pa[o + 3]};
-            const f32x2 pb01 = {pb[o], pb[o + 1]}, pb23 = {pb[o + 2], pb[o + 3]};
+            const f32x2 pa01 = r.pa01[mt], pa23 = r.pa23[mt], pb01 = r.pb01[mt], pb23 = r.pb23[mt];
             const f32x2 x01 = __builtin_elementwise_fma(pb01, sgn2, pa01), x23 = __builtin_elementwise_fma(pb23, sgn2, pa23);
             f32x2 a01, a23;
             // (x0 - x2, x1 + x2)
@@ -714,9 +754,8 @@ __global__ __launch_bounds__(kThreads, 1) void wino_wgrad_kernel(const WgKArgs a
         }
 #pragma unroll
         for (int nt = 0; nt < 3; ++nt) {
-            const int o = nt * 16 + 2 * trow * 48 + tcol;
-            f32x2 z = {pz[o], pz[o + 1]};
-            if constexpr (ZMIX) z = __builtin_elementwise_fma((f32x2){pz[o + 48], pz[o + 48 + 1]}, zs2, z);
+            f32x2 z = r.z[nt];
+            if constexpr (ZMIX) z = __builtin_elementwise_fma(r.zz[nt], zs2, z);
             f32x2 b12;
             // (z0 + z1, z1 - z0): the second is -(z0 - z1)
             asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,0] neg_hi:[0,1]" : "=v"(b12) : "v"(z), "v"(z));
@@ -733,6 +772,11 @@ __global__ __launch_bounds__(kThreads, 1) void wino_wgrad_kernel(const WgKArgs a
                 for (int nt = 0; nt < 3; ++nt)
                     acc[p][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt][p], bv[nt][p], acc[p][mt][nt], 0, 0, 0);
     };
+    auto kstep = [&](auto stage, auto kstp, auto zm) {
+        WgRaw r;
+        fetch(stage, kstp, zm, r);
+        compute(zm, r);
+    };
     auto stage_body = [&](auto stage, int region, auto zm) {
         constexpr int S = decltype(stage)::value;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -742,13 +786,30 @@ __global__ __launch_bounds__(kThreads, 1) void wino_wgrad_kernel(const WgKArgs a
         // spills, and the compiler may run a k-step's LDS reads under the previous one's MFMAs: 446.5 -> 442 us)
         // fences between the k-steps: without the old per-tile branches a region is one basic block of 144 MFMAs, and the
         // scheduler hoists so many LDS reads that the kernel needs 256 registers and scratch
-        kstep(stage, IC<0>{}, zm);
-        __builtin_amdgcn_sched_barrier(0);
-        kstep(stage, IC<1>{}, zm);
-        __builtin_amdgcn_sched_barrier(0);
-        kstep(stage, IC<2>{}, zm);
-        __builtin_amdgcn_sched_barrier(0);
-        kstep(stage, IC<3>{}, zm);
+        if constexpr (STREAM) {
+            // two operand sets: the reads of k-step i + 1 are in flight under the MFMAs of k-step i, and the compiler's
+            // counted lgkmcnt in front of a transform waits for the older set only
+            WgRaw r0, r1;
+            fetch(stage, IC<0>{}, zm, r0);
+            fetch(stage, IC<1>{}, zm, r1);
+            compute(zm, r0);
+            __builtin_amdgcn_sched_barrier(0);
+            fetch(stage, IC<2>{}, zm, r0);
+            compute(zm, r1);
+            __builtin_amdgcn_sched_barrier(0);
+            fetch(stage, IC<3>{}, zm, r1);
+            compute(zm, r0);
+            __builtin_amdgcn_sched_barrier(0);
+            compute(zm, r1);
+        } else {
+            kstep(stage, IC<0>{}, zm);
+            __builtin_amdgcn_sched_barrier(0);
+            kstep(stage, IC<1>{}, zm);
+            __builtin_amdgcn_sched_barrier(0);
+            kstep(stage, IC<2>{}, zm);
+            __builtin_amdgcn_sched_barrier(0);
+            kstep(stage, IC<3>{}, zm);
+        }
     };
 
     int region = xcd_slot(blockIdx.x, gridDim.x, a.xcd);
@@ -807,6 +868,15 @@ __global__ __launch_bounds__(kThreads, 1) void wino_wgrad_kernel(const WgKArgs a
         regions(IC<0>{});
         finish();
     }
+}
+
+template <int MT>
+__global__ __launch_bounds__(kThreads, 1) void wino_wgrad_kernel(const WgKArgs a) {
+    wino_wgrad_body<MT, false>(a);
+}
+template <int MT>
+__global__ __launch_bounds__(kThreads, 1) void wino_wgrad_stream_kernel(const WgKArgs a) {
+    wino_wgrad_body<MT, true>(a);
 }
 
 // gw[co][ci][tap] = sum over the parts that wrote column ci (launches differ in their K split): up to 4 column
@@ -1101,23 +1171,27 @@ int wino_wgrad(const sprk_conv_geom &g, const WinoWgVariant &v, const float *x, 
     const int CinTot = g.C1 + g.C2;
     WgRanges rg{};
     int nr = 0;
+    // the same launches on either kernel (sprk_wino_wgrad_stream_enable); one answer per call
+    const bool stream = g_wino_wgrad_stream_on.load(std::memory_order_relaxed) != 0;
+    const auto k3 = stream ? wino_wgrad_stream_kernel<3> : wino_wgrad_kernel<3>;
+    const auto k1 = stream ? wino_wgrad_stream_kernel<1> : wino_wgrad_kernel<1>;
     for (int i = 0; i < v.launches; ++i) {
         const WinoWgVariant::Launch &l = v.l[i];
         const int Csrc = l.src ? g.C2 : g.C1, ci0 = l.src ? g.C1 : 0;
         WgKArgs a{l.src ? x2 : x, gy, partial, g.N, Csrc, 0, ci0, CinTot, g.Hin, g.Win, g.Cout, v.padT, v.padL, v.regionsX,
                   v.regionsY, xcd_on()};
         if (l.MT == 3) {
-            if (int rc = lds_optin(wino_wgrad_kernel<3>, kWgLdsBytes, "wino_wgrad")) return rc;
+            if (int rc = lds_optin(k3, kWgLdsBytes, "wino_wgrad")) return rc;
             prof_begin(kClassWinoW, flops * (48.0 * l.ch) / CinTot, s);
-            hipLaunchKernelGGL(wino_wgrad_kernel<3>, dim3(l.parts, l.ch), dim3(kThreads), kWgLdsBytes, s, a);
+            hipLaunchKernelGGL(k3, dim3(l.parts, l.ch), dim3(kThreads), kWgLdsBytes, s, a);
             prof_end(kClassWinoW, s);
             if (int rc = check_launch("wino_wgrad<3>")) return rc;
             rg.end[nr] = ci0 + 48 * l.ch;
         } else {
-            if (int rc = lds_optin(wino_wgrad_kernel<1>, kWgLdsBytes, "wino_wgrad")) return rc;
+            if (int rc = lds_optin(k1, kWgLdsBytes, "wino_wgrad")) return rc;
             a.cbase = Csrc - l.ch;   // the tail group sits after the 48-channel groups
             prof_begin(kClassWinoW, flops * (double)l.ch / CinTot, s);
-            hipLaunchKernelGGL(wino_wgrad_kernel<1>, dim3(l.parts, 1), dim3(kThreads), kWgLdsBytes, s, a);
+            hipLaunchKernelGGL(k1, dim3(l.parts, 1), dim3(kThreads), kWgLdsBytes, s, a);
             prof_end(kClassWinoW, s);
             if (int rc = check_launch("wino_wgrad<1>")) return rc;
             rg.end[nr] = ci0 + Csrc;
@@ -1129,6 +1203,7 @@ int wino_wgrad(const sprk_conv_geom &g, const WinoWgVariant &v, const float *x, 
     hipLaunchKernelGGL(wino_wgrad_reduce_kernel, dim3(cdiv(n, 32)), dim3(256), 0, s, partial, gw, n, CinTot, rg);
     if (int rc = check_launch("wino_wgrad_reduce")) return rc;
     g_wino_launches.fetch_add(1, std::memory_order_relaxed);
+    if (stream) g_wino_wgrad_stream_launches.fetch_add(1, std::memory_order_relaxed);
     return SPRK_OK;
 }
 
