@@ -743,6 +743,39 @@ int sprk_extract_boxes(const void *raw, int mode, int ny, int nx, const int *xy,
 int sprk_extract_scale(const void *raw, int mode, int ny, int nx, const int *xy, int P, int box, int side, const float *m,
                        int ldm, int bg_radius, int flags, float *out, int *status, void *stream);
 
+/* sprk_extract_filter: the same boxes CTF-corrected and Fourier-cropped (`joint extract --ctf_correct`): out [P, side,
+ * side] = IDFT2(phi . crop(DFT2(D))), box and side even, 16 <= side <= box <= 1024.  h = side/2, Hs = h + 1, Ku = side + 1.
+ * Kept frequencies: columns v = 0 .. h, rows k = -h .. h (index kk = k + h), also for side == box, where k = +-h are one
+ * frequency of the box and share it half and half.  phi: fp32 [Ku, Hs] contiguous on the device, the real and even filter
+ * of the micrograph (spr_pick_amd.ctf.correction_filter); with phi = 1 the result is sprk_extract_scale's M D M^T.
+ * Box placement, the inside test (64-bit, status 1, zeros, no sample read), raw and D are those of sprk_extract_scale.
+ * The matrices (spr_pick_amd.extract.filter_matrices: float64 with the integer phase reduced mod box or side before the
+ * division, rounded once) are fp32 on the device, 16-byte aligned, dense rows whose length is the column count rounded up
+ * to a multiple of 4; the added columns are never used:
+ *   w1 [2Hs, box]:   row v cos(2 pi v c / box), row Hs+v the sine;
+ *   w2 [2Ku, 2 box]: row kk [cos t | -sin t], row Ku+kk [-sin t | -cos t], t = 2 pi k r / box;
+ *   w3 [2 side, 2Ku]: row i [a cos f | -a sin f], row side+i [a sin f | a cos f], f = 2 pi k i / side, a = 1/2 at k = +-h, else 1;
+ *   w4 [side, 2Hs]:  row j [w cos(2 pi v j / side) | -w sin(2 pi v j / side)] / box^2, w = 1 at v = 0 and v = h, else 2.
+ * The sums are fp32 fmaf chains on v_mfma_f32_16x16x4_f32, each over its K ascending from 0.0f, one accumulator per
+ * element and stage, K never split; K positions padded to a multiple of 4 are zeros in registers on both operands:
+ *   U[r, q]   = chain over c = 0 .. box-1 of D[r, c] * w1[q, c];            V = [U[:, :Hs] ; U[:, Hs:]]    [2 box, Hs]
+ *   Re[kk, v] = chain over t = 0 .. 2 box-1 of w2[kk, t] * V[t, v], Im with row Ku+kk;
+ *   F = [Re * phi ; Im * phi], one fp32 multiply each                                                       [2Ku, Hs]
+ *   Zr[i, v]  = chain over t = 0 .. 2Ku-1 of w3[i, t] * F[t, v], Zi with row side+i;   Z = [Zr, Zi]        [side, 2Hs]
+ *   Y[i, j]   = chain over t = 0 .. 2Hs-1 of Z[i, t] * w4[j, t].
+ * flags = 0: out = fmaf(phi[h, 0], float(x[0,0]), Y) for the integer modes (phi at k = 0, v = 0), out = Y for float32.
+ * SPRK_EXTRACT_NORMALIZE and SPRK_EXTRACT_INVERT: as for sprk_extract_scale, on this Y.
+ * V, F and Z live in the workspace, max_batch particles at a time (0 = the library's choice, about 256 MiB); out does not
+ * depend on it.  Nothing uninitialised is read into a stored value: the workspace may hold anything, NaNs included.
+ * Refused (SPRK_EINVAL, nothing launched): another mode, odd or out-of-range sizes, unknown flags, a negative max_batch or
+ * bg_radius, null or misaligned pointers (out and ws 16-byte aligned as well); a short workspace: SPRK_EWORKSPACE.
+ * P == 0 returns SPRK_OK without a launch.  Four launches per batch on `stream`, five with SPRK_EXTRACT_NORMALIZE; no host
+ * synchronisation, no atomics. */
+size_t sprk_extract_filter_ws_bytes(int P, int box, int side, int max_batch);
+int sprk_extract_filter(const void *raw, int mode, int ny, int nx, const int *xy, int P, int box, int side, const float *w1,
+                        const float *w2, const float *w3, const float *w4, const float *phi, int bg_radius, int flags,
+                        int max_batch, float *out, int *status, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- in-library kernel timing (bench.py's roofline leg) --------------------------------
  * sprk_prof_enable(mask): bit k set = every launch of kernel class k is bracketed by HIP events
  * on its own stream (an event pair costs the GPU front end a few microseconds, so the timed

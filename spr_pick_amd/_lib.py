@@ -145,6 +145,9 @@ _SIGS = {
     "sprk_ctf_score": (c_i, [c_f, c_i, c_i, c_f, c_i, c_vp, c_vp, c_sz, c_vp]),
     "sprk_extract_boxes": (c_i, [c_vp, c_i, c_i, c_i, c_vp, c_i, c_i, c_i, c_i, c_i, c_f, c_vp, c_vp]),
     "sprk_extract_scale": (c_i, [c_vp, c_i, c_i, c_i, c_vp, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_f, c_vp, c_vp]),
+    "sprk_extract_filter_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "sprk_extract_filter": (c_i, [c_vp, c_i, c_i, c_i, c_vp, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_vp,
+                                  c_vp, c_sz, c_vp]),
     "sprk_gather_patches": (c_i, [c_vp, c_i, c_vp, c_vp, c_vp, c_f, c_i, c_i, c_i, c_vp]),
     "sprk_prof_enable": (None, [c_i]),
     "sprk_prof_collect": (c_i, [c_i, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),

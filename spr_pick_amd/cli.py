@@ -3,7 +3,7 @@ reference): ``joint train start|resume`` and ``joint eval`` with the same flags 
 flag -> configuration mapping, plus ``joint bin`` (the README's ``newstack -bin`` preparation, on the GPU), ``joint extract``
 (particle stacks from the pick tables and the raw micrographs, on the GPU) and ``joint ctf`` (tiled power spectra of the raw
 micrographs on the GPU, one fitted defocus each, or with ``--astigmatism`` two and an angle, ``micrographs_ctf.star`` for
-``joint extract --ctf``).  Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
+``joint extract --ctf``, which with ``--ctf_correct`` also phase-flips the stacks).  Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
 under ``python -m torch.distributed.run --nproc-per-node N -m spr_pick_amd -- ...`` (keep the ``--``)."""
 import argparse
 
@@ -107,7 +107,14 @@ def _check_bin(ns):
 
 
 def _check_extract(ns):
-    from .extract import check_box, check_scale
+    from .extract import check_box, check_filter, check_scale
+    if ns.ctf_correct is not None:
+        if ns.ctf is None:
+            raise ValueError("--ctf_correct needs --ctf STAR (the micrographs_ctf.star of `joint ctf`)")
+        if ns.bin > 1:
+            raise ValueError("--ctf_correct and --bin %d exclude one another: use --scale S for smaller stacks" % ns.bin)
+        check_filter(ns.box, ns.scale, ns.bg_radius)
+        return
     if ns.scale is None:
         check_box(ns.box, ns.bin, ns.bg_radius)
         return
@@ -217,6 +224,12 @@ def build_parser():
                     help="micrographs_ctf.star of `joint ctf`: append each micrograph's CTF columns to its rows of "
                          "particles.star, _rlnDetectorPixelSize multiplied by N (--bin) or B / S (--scale); a micrograph "
                          "with picks and no row there is an error")
+    ex.add_argument("--ctf_correct", choices=("flip", "multiply"), metavar="{flip,multiply}",
+                    help="multiply every particle in Fourier space by its micrograph's CTF sign (flip) or by the CTF itself "
+                         "(multiply), from the row of --ctf STAR, before the crop to --scale S and the normalisation; needs "
+                         "--ctf, an even --box and --scale (at least 16), excludes --bin N > 1.  The flat particles.star has "
+                         "no column that says so: tell downstream tools that the data are flipped (relion_refine "
+                         "--ctf_phase_flipped)")
     ex.check = _check_extract
 
     cf = cmds.add_parser("ctf", help="Power spectra of raw micrographs on the GPU and one defocus value each "
@@ -316,8 +329,11 @@ def run_extract(args):
     counts = extract.extract_dataset(args["dataset"], args["picks"], args["out"], args["box"], bin=args["bin"],
                                      picks_bin=args["picks_bin"], threshold=args.get("threshold"),
                                      bg_radius=args.get("bg_radius"), normalize=not args["no_norm"], invert=args["invert"],
-                                     scale=args.get("scale"), ctf=args.get("ctf"))
-    print(json.dumps({"particles": sum(c["written"] for c in counts.values()), "micrographs": counts}))
+                                     scale=args.get("scale"), ctf=args.get("ctf"), ctf_correct=args.get("ctf_correct"))
+    summary = {"particles": sum(c["written"] for c in counts.values()), "micrographs": counts}
+    if args.get("ctf_correct") is not None:
+        summary["ctf_correct"] = args["ctf_correct"]
+    print(json.dumps(summary))
     return counts
 
 

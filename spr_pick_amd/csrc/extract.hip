@@ -33,11 +33,12 @@
 #include <type_traits>
 
 #include "common.h"
+#include "box_dev.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+constexpr int kThreads = kBoxThreads;
+constexpr int kWaves = kBoxWaves;
 constexpr int kUnroll = 8;                       // output pixels a lane forms together (for_each_pixel)
 constexpr int kScratchBytes = 128;              // head of the dynamic LDS: kWaves slots of 8 bytes for the reductions
 // LDS residency of a box: 4*b*b <= 64 KiB, b <= 128.  A workgroup may take all 160 KiB of a CU (b <= 202), but it
@@ -93,23 +94,6 @@ __device__ __forceinline__ void for_each_pixel(const T *__restrict__ origin, int
             if (e < npix) f(e, row[u], e - row[u] * b, acc[u].v);
         }
     }
-}
-
-// the workgroup's sum in a fixed order, returned to every thread (all threads must call)
-template <typename S>
-__device__ __forceinline__ S block_sum(S v, S *red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    S t = red[0];
-    for (int w = 1; w < kWaves; ++w) t += red[w];
-    __syncthreads();                            // red is used again
-    return t;
-}
-
-__device__ __forceinline__ void zero_box(float *__restrict__ o, int npix, int *__restrict__ status, int code) {
-    for (int e = threadIdx.x; e < npix; e += kThreads) o[e] = 0.0f;
-    if (threadIdx.x == 0) *status = code;
 }
 
 // grid: P workgroups.  resident: the dynamic LDS holds kScratchBytes + 4*b*b bytes, else kScratchBytes.
@@ -256,7 +240,8 @@ int launch_extract(const void *raw, int ny, int nx, const int *xy, int P, int B,
 // U rows are 16*TN floats; when that is a multiple of 32, odd rows swap their 16-column halves, so that the two k rows a
 // half wave reads land on different banks.
 // Not normalised: the epilogue of stage 2 adds the anchor and stores.  Normalised: it stores Y, and after a workgroup
-// barrier the workgroup reads its own Y back (L2) for the two double sums (block_sum: a fixed order) and the final store.
+// barrier the workgroup reads its own Y back (L2) for the two double sums (block_sum: a fixed order) and the final store
+// (normalize_box, box_dev.h).
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 constexpr int kKC = 64;                          // columns of K staged per chunk
 constexpr int kLd = kKC + 2;                     // floats per staged row
@@ -282,7 +267,7 @@ __global__ __launch_bounds__(kThreads) void extract_scale_kernel(const T *__rest
     float *As = reinterpret_cast<float *>(lds + kScratchBytes);        // [kRows][kLd]
     float *Ms = As + kRows * kLd;                                      // [W][kLd]
     float *U = Ms + W * kLd;                                           // [roundup(B, 16)][W]
-    const int p = blockIdx.x, npix = S * S, c = S / 2;
+    const int p = blockIdx.x, npix = S * S;
     const bool invert = flags & SPRK_EXTRACT_INVERT, normalize = flags & SPRK_EXTRACT_NORMALIZE;
     float *o = out + (long)p * npix;
     const long x0 = (long)xy[2 * p] - B / 2, y0 = (long)xy[2 * p + 1] - B / 2;
@@ -453,54 +438,7 @@ __global__ __launch_bounds__(kThreads) void extract_scale_kernel(const T *__rest
 
     __threadfence_block();
     __syncthreads();                                           // Y of every wave is in memory: each thread reads its pixels
-    auto is_bg = [&](int e) {
-        const int i = fast_div(e, inv_s), j = e - i * S;       // exact: e < 2^20 (common.h)
-        return (long)((i - c) * (i - c) + (j - c) * (j - c)) > R2;
-    };
-    int n = 0;
-    double s = 0.0;
-    // f(e, Y[e]) for this thread's pixels e = tid, tid + kThreads, ... in ascending order, kUnroll loads in flight (one at
-    // a time, a pass is S*S / kThreads dependent round trips to L2: 48 of them at S = 64 cost more than stage 2)
-    auto for_each_y = [&](auto f) {
-        for (int e0 = tid; e0 < npix; e0 += kUnroll * kThreads) {
-            float v[kUnroll];
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) v[u] = e0 + u * kThreads < npix ? o[e0 + u * kThreads] : 0.0f;
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u)
-                if (e0 + u * kThreads < npix) f(e0 + u * kThreads, v[u]);
-        }
-    };
-    for_each_y([&](int e, float y) {
-        if (is_bg(e)) {
-            s += (double)y;
-            ++n;
-        }
-    });
-    n = block_sum(n, reinterpret_cast<int *>(lds));
-    if (n == 0) {
-        zero_box(o, npix, status + p, 2);
-        return;
-    }
-    const double mean = block_sum(s, reinterpret_cast<double *>(lds)) / (double)n;
-    double q = 0.0;
-    for_each_y([&](int e, float y) {
-        if (is_bg(e)) {
-            const double t = (double)y - mean;
-            q += t * t;
-        }
-    });
-    const double var = block_sum(q, reinterpret_cast<double *>(lds)) / (double)n;
-    if (!(var > 0.0)) {                                        // the same bits in every lane: a uniform branch
-        zero_box(o, npix, status + p, 2);
-        return;
-    }
-    const double sd = sqrt(var);
-    for_each_y([&](int e, float y) {
-        const float r = (float)(((double)y - mean) / sd);
-        o[e] = invert ? -r : r;
-    });
-    if (tid == 0) status[p] = 0;
+    normalize_box(o, S, inv_s, R2, invert, status + p, lds);
 }
 
 // the strip width in 16-column tiles: the widest that keeps U[:, strip] within kStripBytes, then evened out over the strips

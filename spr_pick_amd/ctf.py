@@ -156,6 +156,35 @@ def ctf(s, defocus, kv, cs, ac):
     return -np.sin(np.pi * lam * defocus * s2 - 0.5 * np.pi * cs * lam ** 3 * s2 * s2 + math.atan2(ac, math.sqrt(1 - ac * ac)))
 
 
+CORRECTION_MODES = ("flip", "multiply")
+
+
+def correction_filter(B, S, apix, defocus_u, defocus_v, angle, kv, cs, ac, mode):
+    """The filter of ``torch.ops.sprk.extract_filter`` for boxes of B raw samples cropped to S (both even): float32
+    [S + 1, S/2 + 1], computed in float64 and rounded once, over the kept frequencies k = -S/2 .. S/2 (rows) and v = 0 ..
+    S/2 (columns) in cycles per box.  s^2 = (k^2 + v^2) / (B apix)^2 with ``apix`` the RAW pixel size in Angstrom, phi =
+    atan2(k, v) (``fit_bins``' convention: k the row frequency), dz = d0 + d1 cos(2 (phi - angle)) with d0 = (U + V) / 2,
+    d1 = (U - V) / 2 and ``angle`` in degrees, c = ``ctf``(s, dz).  mode "flip": +1 where c <= 0, else -1; "multiply": -c.
+    Both leave the low-resolution contrast as it was (ctf(0) = -ac < 0), and both are even: Phi(-k, -v) = Phi(k, v)."""
+    if mode not in CORRECTION_MODES:
+        raise ValueError("ctf correction mode %r (one of %s)" % (mode, ", ".join(CORRECTION_MODES)))
+    B, S = int(B), int(S)
+    if B % 2 or S % 2 or not 2 <= S <= B:
+        raise ValueError("ctf correction needs an even box and an even output side, 2 <= S <= B; got B = %d, S = %d" % (B, S))
+    if not (apix > 0 and np.isfinite(apix)):
+        raise ValueError("apix must be positive, got %r" % (apix,))
+    h = S // 2
+    k = np.arange(-h, h + 1, dtype=np.float64)[:, None]
+    v = np.arange(h + 1, dtype=np.float64)[None, :]
+    s = np.sqrt(k * k + v * v) / (B * float(apix))
+    d0, d1 = 0.5 * (float(defocus_u) + float(defocus_v)), 0.5 * (float(defocus_u) - float(defocus_v))
+    dz = d0 + d1 * np.cos(2.0 * (np.arctan2(k, v) - math.radians(float(angle))))
+    c = ctf(s, dz, kv, cs, ac)
+    if mode == "flip":
+        return np.where(c <= 0, 1.0, -1.0).astype(np.float32)
+    return (-c).astype(np.float32)
+
+
 def check_fit_args(apix, kv, cs, ac, min_res, max_res, min_defocus, max_defocus):
     """ValueError for values the fit cannot work with (``apix`` and ``max_res`` may be None: taken from the file / apix)"""
     for name, v in (("apix", apix), ("kv", kv), ("min_res", min_res), ("max_res", max_res), ("min_defocus", min_defocus),

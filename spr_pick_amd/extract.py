@@ -5,7 +5,9 @@ stacks plus one ``particles.star`` out — the step between ``joint eval`` and 2
 A file's sample block is uploaded once by ``ingest.read_raw``; csrc/extract.hip (``torch.ops.sprk.extract_boxes``) cuts
 every box of that micrograph in one launch: box x box raw samples around each centre, binned N x N — or, with ``scale``,
 Fourier-cropped to any S x S (``torch.ops.sprk.extract_scale``: M D M^T with the matrix of ``crop_matrix``) — normalised to zero
-mean and unit variance of the background outside ``bg_radius`` (in output pixels), optionally contrast-inverted.  Boxes
+mean and unit variance of the background outside ``bg_radius`` (in output pixels), optionally contrast-inverted.  With
+``ctf_correct`` every box is multiplied in Fourier space by the CTF filter of its micrograph on the way
+(``torch.ops.sprk.extract_filter``, csrc/extractfilter.hip: four GEMMs with the matrices of ``filter_matrices``).  Boxes
 that are not entirely inside the image (status 1) and boxes with no or a flat background (status 2) come back as zeros
 and are not written.
 
@@ -93,12 +95,77 @@ def crop_matrix(B, S, device=None):
     return _matrices[key]
 
 
-def extract_particles(path_or_raw, xy, box, bin=1, bg_radius=None, normalize=True, invert=False, device="cuda", scale=None):
+def check_filter(box, scale=None, bg_radius=None):
+    """-> (S, bg_radius) or ValueError: box and S even, 16 <= S <= box <= 1024 (S = box without ``scale``), bg_radius >= 0
+    (default 3/8 of the output side)."""
+    scale = box if scale is None else scale
+    if not isinstance(box, (int, np.integer)) or not isinstance(scale, (int, np.integer)):
+        raise ValueError("box and scale must be integers, got %r and %r" % (box, scale))
+    if bg_radius is None:
+        bg_radius = default_bg_radius(scale)
+    try:
+        return torch_ops.extract_filter_side(int(box), int(scale), int(bg_radius)), int(bg_radius)
+    except _lib.SprkError as e:
+        raise ValueError(str(e)) from None
+
+
+def filter_matrices64(B, S):
+    """The four real matrices of ``torch.ops.sprk.extract_filter`` in float64 (include/sprk.h), h = S/2, Hs = h + 1, Ku =
+    S + 1, k = -h .. h: W1 [2Hs, B] the half-plane DFT along the rows of the box, W2 [2Ku, 2B] the DFT along its columns at
+    the kept k, W3 [2S, 2Ku] the inverse along the columns with the weights a_k (1/2 at k = +-h), W4 [S, 2Hs] the inverse
+    along the rows with w_v (1 at v = 0 and h, else 2) and 1/B^2.  Every integer phase is reduced mod B or S before the
+    division.  With a filter of ones the four stages are ``crop_matrix64(B, S)`` applied on both sides."""
+    B, S = int(B), int(S)
+    check_filter(B, S)
+    h = S // 2
+    v = np.arange(h + 1, dtype=np.int64)
+    k = np.arange(-h, h + 1, dtype=np.int64)
+    a1 = (2.0 * np.pi / B) * ((v[:, None] * np.arange(B, dtype=np.int64)[None, :]) % B)
+    a2 = (2.0 * np.pi / B) * ((k[:, None] * np.arange(B, dtype=np.int64)[None, :]) % B)
+    a3 = (2.0 * np.pi / S) * ((np.arange(S, dtype=np.int64)[:, None] * k[None, :]) % S)
+    a4 = (2.0 * np.pi / S) * ((np.arange(S, dtype=np.int64)[:, None] * v[None, :]) % S)
+    a = np.where(np.abs(k) == h, 0.5, 1.0)[None, :]
+    w = np.where((v == 0) | (v == h), 1.0, 2.0)[None, :] / (float(B) * B)
+    C2, S2, C3, S3 = np.cos(a2), np.sin(a2), a * np.cos(a3), a * np.sin(a3)
+    return (np.concatenate([np.cos(a1), np.sin(a1)]), np.block([[C2, -S2], [-S2, -C2]]), np.block([[C3, -S3], [S3, C3]]),
+            np.concatenate([w * np.cos(a4), -w * np.sin(a4)], axis=1))
+
+
+_filter_matrices = {}
+
+
+def filter_matrices(B, S, device=None):
+    """``filter_matrices64`` rounded to float32.  Without a device: the four arrays.  With one: the operands of
+    ``torch.ops.sprk.extract_filter``, contiguous tensors on that device whose columns are rounded up to a multiple of 4
+    with exact zeros (``torch_ops.extract_filter_shapes``), built once per (B, S, device)."""
+    B, S = int(B), int(S)
+    key = (B, S, None if device is None else str(torch.device(device)))
+    if key not in _filter_matrices:
+        if device is None:
+            _filter_matrices[key] = tuple(m.astype(np.float32) for m in filter_matrices64(B, S))
+        else:
+            out = []
+            for m, shape in zip(filter_matrices(B, S), torch_ops.extract_filter_shapes(B, S)):
+                padded = np.zeros(shape, dtype=np.float32)
+                padded[:m.shape[0], :m.shape[1]] = m
+                out.append(torch.from_numpy(padded).to(device))
+            _filter_matrices[key] = tuple(out)
+    return _filter_matrices[key]
+
+
+def extract_particles(path_or_raw, xy, box, bin=1, bg_radius=None, normalize=True, invert=False, device="cuda", scale=None,
+                      ctf_filter=None, max_batch=0):
     """path_or_raw: an MRC file, or the ``(raw, header)`` pair ``ingest.read_raw`` returns for one.  xy: [P, 2] integer
     (x, y) centres in raw samples, array or int32 CUDA tensor.  scale = S: boxes Fourier-cropped to S x S instead of
-    binned (``bin`` must be 1), b = S.
+    binned (``bin`` must be 1), b = S.  ctf_filter = the float32 [b + 1, b/2 + 1] array or tensor of
+    ``ctf.correction_filter``: every box is multiplied by it in Fourier space (``torch.ops.sprk.extract_filter``; box and
+    b even, b >= 16, ``bin`` must be 1; ``max_batch`` particles share the workspace at a time, 0 = the library's choice).
     -> (particles float32 CUDA [P, b, b], status int32 CUDA [P]); nothing is synchronised."""
-    if scale is not None:
+    if ctf_filter is not None:
+        if bin != 1:
+            raise ValueError("a CTF filter and bin > 1 exclude one another (use scale)")
+        b, bg_radius = check_filter(box, scale, bg_radius)
+    elif scale is not None:
         if bin != 1:
             raise ValueError("scale and bin > 1 exclude one another")
         b, bg_radius = check_scale(box, scale, bg_radius)
@@ -117,6 +184,12 @@ def extract_particles(path_or_raw, xy, box, bin=1, bg_radius=None, normalize=Tru
         info = np.iinfo(np.int32)                                # far outside either way: status 1
         xy = torch.from_numpy(np.clip(xy, info.min, info.max).astype(np.int32))
     xy = xy.to(raw.device)
+    if ctf_filter is not None:
+        if not torch.is_tensor(ctf_filter):
+            ctf_filter = torch.from_numpy(np.ascontiguousarray(ctf_filter, dtype=np.float32))
+        return torch.ops.sprk.extract_filter(raw, header.mode, header.ny, header.nx, xy, int(box), b,
+                                             *filter_matrices(box, b, raw.device), ctf_filter.to(raw.device).contiguous(),
+                                             bg_radius, bool(normalize), bool(invert), int(max_batch))
     if scale is not None:
         return torch.ops.sprk.extract_scale(raw, header.mode, header.ny, header.nx, xy, int(box), b,
                                             crop_matrix(box, b, raw.device), bg_radius, bool(normalize), bool(invert))
@@ -147,6 +220,12 @@ def _extract_file(path, xy, box, bin, bg_radius, normalize, invert, device):
 def _extract_file_scaled(path, xy, box, scale, bg_radius, normalize, invert, device):
     """``_extract_file`` with the boxes Fourier-cropped to scale x scale."""
     return _to_host(*extract_particles(path, xy, box, 1, bg_radius, normalize, invert, device, scale=scale))
+
+
+def _extract_file_filtered(path, xy, box, scale, bg_radius, normalize, invert, device, ctf_filter):
+    """``_extract_file_scaled`` with the boxes multiplied by ``ctf_filter`` in Fourier space."""
+    return _to_host(*extract_particles(path, xy, box, 1, bg_radius, normalize, invert, device, scale=scale,
+                                       ctf_filter=ctf_filter))
 
 
 def _to_host(out, status):
@@ -192,6 +271,15 @@ def read_pick_tables(picks, names, picks_bin=1):
     return tables
 
 
+def _ctf_filter(row, box, side, mode):
+    """``ctf.correction_filter`` from one row of ``micrographs_ctf.star`` (``ctf.read_ctf_star``); the raw pixel size is
+    DetectorPixelSize . 10^4 / Magnification Angstrom."""
+    apix = float(row["DetectorPixelSize"]) * 1e4 / float(row["Magnification"])
+    return ctf_mod.correction_filter(box, side, apix, float(row["DefocusU"]), float(row["DefocusV"]), float(row["DefocusAngle"]),
+                                     float(row["Voltage"]), float(row["SphericalAberration"]), float(row["AmplitudeContrast"]),
+                                     mode)
+
+
 def _ctf_columns(star, named_paths, pixel_factor):
     """The text appended to every ``particles.star`` row of a micrograph, {name: "\\t..."}: the columns of its row in the
     ``micrographs_ctf.star`` table ``star`` (matched by the file name, as ``_rlnMicrographName`` is written), verbatim
@@ -210,7 +298,7 @@ def _ctf_columns(star, named_paths, pixel_factor):
 
 
 def extract_dataset(dataset, picks, out_dir, box, bin=1, picks_bin=1, threshold=None, bg_radius=None, normalize=True,
-                    invert=False, device="cuda", scale=None, ctf=None):
+                    invert=False, device="cuda", scale=None, ctf=None, ctf_correct=None):
     """``joint extract``: for every micrograph of the table / directory ``dataset`` that has a pick table, the picks
     with score > ``threshold`` (all of them when None), mapped from the ``picks_bin`` frame to raw samples, extracted in
     one launch and written as the float32 stack ``out_dir/{name}.mrcs`` (status-0 particles only, pick order); at the
@@ -219,9 +307,20 @@ def extract_dataset(dataset, picks, out_dir, box, bin=1, picks_bin=1, threshold=
     cropping (``bin`` must be 1); the coordinates of ``particles.star`` stay in raw samples either way.  ctf = the
     ``micrographs_ctf.star`` of ``joint ctf``: every row gains its micrograph's CTF columns, ``_rlnDetectorPixelSize``
     multiplied by ``bin`` (or box / S) so that it states the pixel size of the stacks; a micrograph with picks and without a
-    row there is a ValueError before anything is extracted.
+    row there is a ValueError before anything is extracted.  ctf_correct = "flip" or "multiply" (needs ``ctf``; ``bin``
+    must be 1, box and S even, S >= 16): every particle is multiplied in Fourier space by the filter
+    ``ctf.correction_filter`` builds from its micrograph's row, before the crop to S and the normalisation; the STAR
+    format has no column that says so, downstream tools must be told (``relion_refine --ctf_phase_flipped``).
     -> {name: {"written", "outside", "flat"}} for the micrographs that had a table."""
-    if scale is not None:
+    if ctf_correct is not None:
+        if ctf_correct not in ctf_mod.CORRECTION_MODES:
+            raise ValueError("ctf_correct %r (one of %s)" % (ctf_correct, ", ".join(ctf_mod.CORRECTION_MODES)))
+        if ctf is None:
+            raise ValueError("ctf_correct needs the micrographs_ctf.star of `joint ctf` (ctf)")
+        if bin != 1:
+            raise ValueError("ctf_correct and bin > 1 exclude one another (use scale)")
+        b, bg_radius = check_filter(box, scale, bg_radius)
+    elif scale is not None:
         if bin != 1:
             raise ValueError("scale and bin > 1 exclude one another")
         b, bg_radius = check_scale(box, scale, bg_radius)
@@ -232,10 +331,12 @@ def extract_dataset(dataset, picks, out_dir, box, bin=1, picks_bin=1, threshold=
     if not rows:
         raise ValueError("no micrographs found in %s" % dataset)
     tables = read_pick_tables(picks, [name for _, name, _ in rows], picks_bin)
-    ctf_cols = None
+    ctf_cols, ctf_table = None, None
     if ctf is not None:
         ctf_cols = _ctf_columns(ctf, [(name, path) for _, name, path in rows if name in tables and len(tables[name][0])],
                                 float(box) / b)
+        if ctf_correct is not None:
+            ctf_table = ctf_mod.read_ctf_star(ctf)
     os.makedirs(out_dir, exist_ok=True)
     counts, star, missing = {}, [], []
     for _, name, path in rows:
@@ -256,7 +357,10 @@ def extract_dataset(dataset, picks, out_dir, box, bin=1, picks_bin=1, threshold=
         counts[name] = {"written": 0, "outside": 0, "flat": 0}
         if not len(xy):
             continue
-        if scale is not None:
+        if ctf_correct is not None:
+            phi = _ctf_filter(ctf_table[os.path.basename(path)], box, b, ctf_correct)
+            particles, status = _extract_file_filtered(path, xy, box, b, bg_radius, normalize, invert, device, phi)
+        elif scale is not None:
             particles, status = _extract_file_scaled(path, xy, box, b, bg_radius, normalize, invert, device)
         else:
             particles, status = _extract_file(path, xy, box, bin, bg_radius, normalize, invert, device)

@@ -844,6 +844,77 @@ _register("extract_scale", "(Tensor raw, int mode, int ny, int nx, Tensor xy, in
                            "bool normalize, bool invert) -> (Tensor, Tensor)", _extract_scale, _extract_scale_fake)
 
 
+EXTRACT_FILTER_MIN_SIDE = 16                     # sprk_extract_filter: box and side even, 16 <= side <= box <= 1024
+
+
+def extract_filter_side(box, side, bg_radius=0):
+    """Argument check shared by the operator, extract.py and the command line -> side, the output side."""
+    if not (EXTRACT_FILTER_MIN_SIDE <= side <= box <= EXTRACT_MAX_BOX) or box % 2 or side % 2:
+        raise _lib.SprkError("extract_filter: box %d with output side %d (both even, %d <= side <= box <= %d)"
+                             % (box, side, EXTRACT_FILTER_MIN_SIDE, EXTRACT_MAX_BOX))
+    if bg_radius < 0:
+        raise _lib.SprkError("extract_filter: background radius %d (>= 0)" % bg_radius)
+    return side
+
+
+def extract_filter_shapes(box, side):
+    """-> the shapes of the operands w1, w2, w3, w4 and phi: the columns of the matrices rounded up to a multiple of 4"""
+    hs, ku = side // 2 + 1, side + 1
+    up4 = lambda n: -(-n // 4) * 4
+    return (2 * hs, up4(box)), (2 * ku, 2 * box), (2 * side, up4(2 * ku)), (side, up4(2 * hs)), (ku, hs)
+
+
+def _extract_filter_shapes(raw, mode, ny, nx, xy, box, side, w1, w2, w3, w4, phi, bg_radius, max_batch):
+    if mode not in MRC_ITEMSIZE:
+        raise _lib.SprkError("extract_filter: unsupported MRC mode %d" % mode)
+    extract_filter_side(box, side, bg_radius)
+    if max_batch < 0:
+        raise _lib.SprkError("extract_filter: max_batch %d (0 = the library's choice, or a positive number of particles)"
+                             % max_batch)
+    if ny < 1 or nx < 1 or ny * nx >= 1 << 31:
+        raise _lib.SprkError("extract_filter: bad image size %dx%d" % (ny, nx))
+    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
+        raise _lib.SprkError("extract_filter: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
+                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+    if xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or xy.device != raw.device:
+        raise _lib.SprkError("extract_filter: xy must be an int32 tensor [P, 2] on %s, got %s %s on %s"
+                             % (raw.device, xy.dtype, tuple(xy.shape), xy.device))
+    for name, m, shape in zip(("w1", "w2", "w3", "w4", "phi"), (w1, w2, w3, w4, phi), extract_filter_shapes(box, side)):
+        if m.dtype != torch.float32 or tuple(m.shape) != shape or m.device != raw.device:
+            raise _lib.SprkError("extract_filter: %s must be the float32 %s, [%d, %d] on %s, got %s %s on %s"
+                                 % (name, "filter of ctf.correction_filter" if name == "phi" else
+                                    "matrix of extract.filter_matrices(%d, %d)" % (box, side), *shape, raw.device, m.dtype,
+                                    tuple(m.shape), m.device))
+    return xy.shape[0]
+
+
+def _extract_filter(raw, mode, ny, nx, xy, box, side, w1, w2, w3, w4, phi, bg_radius, normalize, invert, max_batch):
+    """-> (out float32 [P, side, side], status int32 [P]: 0 ok, 1 outside the image, 2 no or flat background)."""
+    P = _extract_filter_shapes(raw, mode, ny, nx, xy, box, side, w1, w2, w3, w4, phi, bg_radius, max_batch)
+    if not all(t.is_contiguous() for t in (raw, w1, w2, w3, w4, phi)):
+        raise _lib.SprkError("extract_filter: raw, the matrices and phi must be contiguous")
+    xy = xy.contiguous()
+    L = _lib.lib()
+    out = _f32(raw, (P, side, side))
+    status = torch.empty((P,), dtype=torch.int32, device=raw.device)
+    flags = (EXTRACT_NORMALIZE if normalize else 0) | (EXTRACT_INVERT if invert else 0)
+    ws = _ws(L.sprk_extract_filter_ws_bytes(P, int(box), int(side), int(max_batch)), raw)
+    check(L.sprk_extract_filter(_p(raw), int(mode), int(ny), int(nx), _p(xy), P, int(box), int(side), _p(w1), _p(w2), _p(w3),
+                                _p(w4), _p(phi), int(bg_radius), flags, int(max_batch), _p(out), _p(status), _p(ws),
+                                ws.numel(), _stream(raw)), "sprk_extract_filter")
+    return out, status
+
+
+def _extract_filter_fake(raw, mode, ny, nx, xy, box, side, w1, w2, w3, w4, phi, bg_radius, normalize, invert, max_batch):
+    P = _extract_filter_shapes(raw, mode, ny, nx, xy, box, side, w1, w2, w3, w4, phi, bg_radius, max_batch)
+    return raw.new_empty((P, side, side), dtype=torch.float32), raw.new_empty((P,), dtype=torch.int32)
+
+
+_register("extract_filter", "(Tensor raw, int mode, int ny, int nx, Tensor xy, int box, int side, Tensor w1, Tensor w2, "
+                            "Tensor w3, Tensor w4, Tensor phi, int bg_radius, bool normalize, bool invert, int max_batch) "
+                            "-> (Tensor, Tensor)", _extract_filter, _extract_filter_fake)
+
+
 # ---- tiled power spectra (ctf.py: raw MRC samples -> the summed power spectrum of overlapping tiles) --------------------------
 PSD_MIN_TILE, PSD_MAX_TILE = 16, 1024            # sprk_psd_tiles: T a multiple of 16 in this range
 
