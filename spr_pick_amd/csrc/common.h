@@ -62,6 +62,7 @@ inline int finish_or_defer(const sprk_reduce_item &it, sprk_reduce_item *out, hi
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 inline int roundup(int a, int b) { return (a + b - 1) / b * b; }
+inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }   // workspace parts start 16-byte aligned
 inline int pow2_ceil(int v) {
     int p = 1;
     while (p < v) p <<= 1;

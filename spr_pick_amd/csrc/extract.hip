@@ -34,6 +34,7 @@
 
 #include "common.h"
 #include "box_dev.h"
+#include "mfma_stage.h"
 
 namespace {
 
@@ -236,15 +237,13 @@ int launch_extract(const void *raw, int ny, int nx, const int *xy, int P, int B,
 // accumulators in registers over the whole K loop, and take their operands in chunks of kKC columns through LDS: the A
 // operand (stage 1: samples by element loads of their own type, converted once; stage 2: rows of M) and, in stage 1, the
 // strip's rows of M.  The next two chunks are fetched into registers before the current one is multiplied.  A staged row is
-// kKC + 2 floats long: lane (row, k) of a fragment read then sits on bank 2*row + k, 32 different banks per half wave.
+// kLd = kKC + 2 floats long (mfma_stage.h, whose chunk size and stage4 this kernel shares; its K loops stay its own: they
+// run inside the kernel's strip and row-block loops, the fetch is predicated and U lives in LDS).
 // U rows are 16*TN floats; when that is a multiple of 32, odd rows swap their 16-column halves, so that the two k rows a
 // half wave reads land on different banks.
 // Not normalised: the epilogue of stage 2 adds the anchor and stores.  Normalised: it stores Y, and after a workgroup
 // barrier the workgroup reads its own Y back (L2) for the two double sums (block_sum: a fixed order) and the final store
 // (normalize_box, box_dev.h).
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-constexpr int kKC = 64;                          // columns of K staged per chunk
-constexpr int kLd = kKC + 2;                     // floats per staged row
 constexpr int kRows = 16 * kWaves;               // output rows per row block
 constexpr int kMaxTN = 4;                        // 16-column tiles per strip and wave: at most four accumulators
 constexpr int kStripBytes = 64 * 1024;           // U[:, strip] in LDS: the strip narrows until roundup(B, 16) * 16*TN * 4 fits
@@ -314,11 +313,7 @@ __global__ __launch_bounds__(kThreads) void extract_scale_kernel(const T *__rest
 #pragma unroll
         for (int u = 0; u < n4; ++u) {
             const int e = tid + u * kThreads;
-            if (e < rows * 16) {
-                float *d = dst + (e >> 4) * kLd + (e & 15) * 4;            // 8-byte aligned: kLd is even
-                *reinterpret_cast<float2 *>(d) = make_float2(v[u].x, v[u].y);
-                *reinterpret_cast<float2 *>(d + 2) = make_float2(v[u].z, v[u].w);
-            }
+            if (e < rows * 16) stage4(dst + (e >> 4) * kLd + (e & 15) * 4, v[u]);
         }
     };
     auto u_at = [&](int r, int j) -> float & { return U[r * W + (j ^ ((r & 1) ? kSwizzle : 0))]; };

@@ -18,11 +18,12 @@
 // its own box.  Four launches per batch on the caller's stream, five with SPRK_EXTRACT_NORMALIZE; no host synchronisation,
 // no atomics.  grid.z is the particle of the batch, and a box that is not entirely inside the image leaves every stage at
 // once (stage 4 writes its zeros and its status 1): none of its samples is read.
-//   filter_rows_kernel<T> (stage 1) and filter_out_kernel (stage 4): psd_rows_kernel's shape, one workgroup of four waves per
-//     64 x 64 outputs, a wave on 16 rows with four accumulators; both operands in chunks of 64 K positions through LDS, two
-//     chunks fetched ahead from clamped addresses.
-//   filter_cols_kernel<kStage> (stages 2 and 3): psd_cols_kernel's shape, a wave holds the accumulators of rows u and M + u
-//     of its 16 rows (Re and Im, Zr and Zi), so the filter is applied in the epilogue of stage 2 without a second pass.
+//   filter_rows_kernel<T> (stage 1) and filter_out_kernel (stage 4): the pipeline of mfma_stage.h, one workgroup of four
+//     waves per 64 x 64 outputs, a wave on 16 rows with four accumulators; both operands in chunks of 64 K positions through
+//     LDS, two chunks fetched ahead from clamped addresses (stage 1: sample rows against matrix rows; stage 4: matrix rows
+//     on both sides).
+//   filter_cols_kernel<kStage> (stages 2 and 3): the paired form of that pipeline, a wave holds the accumulators of rows u
+//     and M + u of its 16 rows (Re and Im, Zr and Zi), so the filter is applied in the epilogue of stage 2 without a second pass.
 //   filter_norm_kernel: one workgroup per particle over its Y in `out`: normalize_box (box_dev.h), the background sums in
 //     double and the final store that extract_scale_kernel ends with.
 //
@@ -42,7 +43,6 @@ constexpr int kThreads = kBoxThreads;            // four waves, every kernel
 constexpr int kWaves = kBoxWaves;
 constexpr int kTile = 64;                        // 64 x 64 outputs per workgroup, every stage
 constexpr int kTN = kTile / 16;
-constexpr int kLdb = kTile + 16;                 // stages 2 and 3: floats per staged row of the K-major operand
 constexpr int kMaxBatch = 65535;                 // grid.z
 constexpr size_t kBudget = (size_t)256 << 20;    // the library's own choice of a batch keeps the workspace near this
 
@@ -66,10 +66,6 @@ template <typename T>
 __global__ __launch_bounds__(kThreads) void filter_rows_kernel(const T *__restrict__ raw, Geo g, const int *__restrict__ xy,
                                                                int p0, const float *__restrict__ w1,
                                                                float *__restrict__ v_out) {
-    constexpr bool kFloat = std::is_same<T, float>::value;
-    using R = typename std::conditional<kFloat, float, int>::type;
-    constexpr int kDPerThread = kTile * kKC / kThreads;        // 16 samples of a chunk per thread
-    constexpr int kMPerThread = kTile * kKC / 4 / kThreads;    // 4 float4 of a chunk of W1 per thread
     __shared__ __align__(16) float As[kTile * kLd];            // [64 rows of D][kLd]
     __shared__ __align__(16) float Ms[kTile * kLd];            // [64 rows of W1][kLd]
     const int B = g.B, Hs = g.Hs, N = 2 * g.Hs, Kp = g.ld1;
@@ -80,94 +76,23 @@ __global__ __launch_bounds__(kThreads) void filter_rows_kernel(const T *__restri
     const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
     const T first = origin[0];                                 // every lane the same address: a broadcast
 
-    // thread t holds elements t, t + 256, ... of the [64][kKC] chunk; rows and columns past the box are fetched from
-    // its last row / column and staged as zeros
-    auto fetch_d = [&](R (&v)[kDPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kDPerThread; ++k) {
-            const int e = tid + k * kThreads, r = r0 + (e >> 6), q = c0 + (e & 63);
-            v[k] = origin[(long)min(r, B - 1) * g.nx + min(q, B - 1)];
-        }
-    };
-    auto stage_d = [&](const R (&v)[kDPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kDPerThread; ++k) {
-            const int e = tid + k * kThreads, r = r0 + (e >> 6), q = c0 + (e & 63);
-            float d;
-            if constexpr (kFloat) d = v[k];
-            else d = (float)(v[k] - (int)first);               // |difference| < 2^17: exact
-            As[(e >> 6) * kLd + (e & 63)] = (r < B && q < B) ? d : 0.0f;
-        }
-    };
-    auto fetch_m = [&](float4 (&v)[kMPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kMPerThread; ++k) {
-            const int e = tid + k * kThreads;
-            v[k] = fetch4(w1, g.ld1, N, g.ld1, q0 + (e >> 4), c0 + (e & 15) * 4);
-        }
-    };
-    auto stage_m = [&](const float4 (&v)[kMPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kMPerThread; ++k) {
-            const int e = tid + k * kThreads;
-            stage4(Ms + (e >> 4) * kLd + (e & 15) * 4, zero4(v[k], q0 + (e >> 4) < N, c0 + (e & 15) * 4, B));
-        }
-    };
-
+    // rows and columns past the box are fetched from its last row / column; rows of W1 past 2Hs are staged as zeros
+    const SampleRows<T, kThreads> d{origin, g.nx, B, B, r0, first, lds_ptr(As)};
+    const MatrixRows<kTile, kThreads, RowsFrom> m{w1, g.ld1, N, g.ld1, B, RowsFrom{q0, N}, lds_ptr(Ms)};
     const bool active = r0 + wave * 16 < B;                    // wave-uniform
     f32x4 acc[kTN];
 #pragma unroll
     for (int t = 0; t < kTN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    R dv[2][kDPerThread];
-    float4 mv[2][kMPerThread];
-    fetch_d(dv[0], 0);
-    fetch_m(mv[0], 0);
-    if (kKC < Kp) {
-        fetch_d(dv[1], kKC);
-        fetch_m(mv[1], kKC);
-    }
-    auto chunk = [&](R (&d)[kDPerThread], float4 (&mm)[kMPerThread], int c0) {
-        __syncthreads();                                       // the chunk before this one has been multiplied
-        stage_d(d, c0);
-        stage_m(mm, c0);
-        __syncthreads();
-        if (c0 + 2 * kKC < Kp) {
-            fetch_d(d, c0 + 2 * kKC);
-            fetch_m(mm, c0 + 2 * kKC);
-        }
-        if (active) {
-            const int ks = min(kKC, Kp - c0);                  // a multiple of 4
-            const float *ap = As + (wave * 16 + lr) * kLd + lk, *bp = Ms + lr * kLd + lk;
-            auto step = [&](int k) {
-                const float a = ap[k];
-#pragma unroll
-                for (int t = 0; t < kTN; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[t * 16 * kLd + k], acc[t], 0, 0, 0);
-            };
-            if (ks == kKC) {
-#pragma unroll
-                for (int k = 0; k < kKC; k += 4) step(k);
-            } else {
-                for (int k = 0; k < ks; k += 4) step(k);
-            }
-        }
-    };
-    for (int c0 = 0; c0 < Kp; c0 += 2 * kKC) {
-        chunk(dv[0], mv[0], c0);
-        if (c0 + kKC < Kp) chunk(dv[1], mv[1], c0 + kKC);
-    }
+    k_loop(Kp, d, m, active,
+           [&](int ks) { multiply<BtRows, false>(acc, a_frag(As, wave, lr, lk), BtRows::frag(Ms, lr, lk), ks); });
     if (active) {
         float *__restrict__ vp = v_out + (long)blockIdx.z * 2 * B * g.ldv;
-#pragma unroll
-        for (int t = 0; t < kTN; ++t)
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) {
-                const int r = r0 + wave * 16 + lk * 4 + gg, q = q0 + t * 16 + lr;
-                if (r < B && q < N) {
-                    const int part = q >= Hs;                  // the sine half goes below the cosine half
-                    vp[(long)(part * B + r) * g.ldv + (q - part * Hs)] = acc[t][gg];
-                }
-            }
+        for_each_output(acc, r0, q0, wave, lk, lr, [&](int r, int q, float u) {
+            // the sine half goes below the cosine half; the address is formed outside the condition, so once per tile
+            const int part = q >= Hs;
+            float *p = vp + (long)(part * B + r) * g.ldv + (q - part * Hs);
+            if (r < B && q < N) *p = u;
+        });
     }
 }
 
@@ -179,11 +104,9 @@ template <int kStage>
 __global__ __launch_bounds__(kThreads) void filter_cols_kernel(Geo g, const int *__restrict__ xy, int p0,
                                                                const float *__restrict__ w, const float *__restrict__ b_in,
                                                                const float *__restrict__ phi, float *__restrict__ c_out) {
-    constexpr int kAPerThread = 2 * kTile * kKC / 4 / kThreads;    // 8 float4 of a chunk of W (rows u and M + u)
-    constexpr int kBPerThread = kKC * kTile / 4 / kThreads;        // 4 float4 of a chunk of the operand
-    constexpr int kBRow4 = kTile / 4;
+    using BRows = KMajorRows<kTile, kThreads, true>;
     __shared__ __align__(16) float As[2 * kTile * kLd];        // [64 rows u, then 64 rows M + u][kLd]
-    __shared__ __align__(16) float Bs[kKC * kLdb];             // [rows of the operand = K][kLdb]
+    __shared__ __align__(16) float Bs[kKC * BRows::kLdb];      // [rows of the operand = K][kLdb]
     const int Hs = g.Hs, ldv = g.ldv;
     const int M = kStage == 2 ? g.Ku : g.S, K = kStage == 2 ? 2 * g.B : 2 * g.Ku, ldw = kStage == 2 ? 2 * g.B : g.ld3;
     const int Kp = (K + 3) & ~3;
@@ -193,102 +116,31 @@ __global__ __launch_bounds__(kThreads) void filter_cols_kernel(Geo g, const int 
     const int u0 = blockIdx.y * kTile, v0 = blockIdx.x * kTile;
     const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
 
-    // staged row rr < 64 is row u0 + rr of W, staged row 64 + rr is row M + u0 + rr; rows at or past M of either half
-    // are fetched from a row that exists and staged as zeros, and so are the K positions at or past K
-    auto fetch_a = [&](float4 (&v)[kAPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kAPerThread; ++k) {
-            const int e = tid + k * kThreads, rr = e >> 4, u = u0 + (rr & (kTile - 1));
-            v[k] = fetch4(w, ldw, 2 * M, ldw, (rr >= kTile ? M : 0) + min(u, M - 1), c0 + (e & 15) * 4);
-        }
-    };
-    auto stage_a = [&](const float4 (&v)[kAPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kAPerThread; ++k) {
-            const int e = tid + k * kThreads, rr = e >> 4;
-            stage4(As + rr * kLd + (e & 15) * 4, zero4(v[k], u0 + (rr & (kTile - 1)) < M, c0 + (e & 15) * 4, K));
-        }
-    };
-    // rows c0 .. of the operand, columns v0 .. v0+63 (ldv and v0 are multiples of 4).  Columns Hs .. ldv-1 were never
-    // written: they are staged as zeros, like everything past ldv and every row at or past K
-    auto fetch_b = [&](float4 (&v)[kBPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kBPerThread; ++k) {
-            const int e = tid + k * kThreads;
-            v[k] = fetch4(bt, ldv, K, ldv, c0 + e / kBRow4, v0 + (e % kBRow4) * 4);
-        }
-    };
-    auto stage_b = [&](const float4 (&v)[kBPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kBPerThread; ++k) {
-            const int e = tid + k * kThreads, j = v0 + (e % kBRow4) * 4;
-            *reinterpret_cast<float4 *>(Bs + (e / kBRow4) * kLdb + (e % kBRow4) * 4) =
-                zero4(v[k], c0 + e / kBRow4 < K && j < ldv, j, Hs);
-        }
-    };
-
+    // A: rows u and M + u of W, the K positions at or past K staged as zeros.  B: columns Hs .. ldv-1 of the operand were
+    // never written: staged as zeros, like every row at or past K
+    const MatrixRows<2 * kTile, kThreads, RowPairs> a{w, ldw, 2 * M, ldw, K, RowPairs{u0, M}, lds_ptr(As)};
+    const BRows b{bt, ldv, K, v0, Hs, lds_ptr(Bs)};
     const bool active = u0 + wave * 16 < M;                    // wave-uniform
-    f32x4 re[kTN], im[kTN];
+    f32x4 re[kTN], im[kTN];                                    // Re and Im, Zr and Zi
 #pragma unroll
     for (int t = 0; t < kTN; ++t) re[t] = im[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    float4 av[2][kAPerThread], bv[2][kBPerThread];
-    fetch_a(av[0], 0);
-    fetch_b(bv[0], 0);
-    if (kKC < Kp) {
-        fetch_a(av[1], kKC);
-        fetch_b(bv[1], kKC);
-    }
-    auto chunk = [&](float4 (&a4)[kAPerThread], float4 (&b4)[kBPerThread], int c0) {
-        __syncthreads();                                       // the chunk before this one has been multiplied
-        stage_a(a4, c0);
-        stage_b(b4, c0);
-        __syncthreads();
-        if (c0 + 2 * kKC < Kp) {
-            fetch_a(a4, c0 + 2 * kKC);
-            fetch_b(b4, c0 + 2 * kKC);
-        }
-        if (active) {
-            const int ks = min(kKC, Kp - c0);                  // a multiple of 4
-            const float *ap = As + (wave * 16 + lr) * kLd + lk, *bp = Bs + lk * kLdb + lr;
-            auto step = [&](int k) {
-                const float a_re = ap[k], a_im = ap[kTile * kLd + k];
-#pragma unroll
-                for (int t = 0; t < kTN; ++t) {
-                    const float b = bp[k * kLdb + t * 16];
-                    re[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_re, b, re[t], 0, 0, 0);
-                    im[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_im, b, im[t], 0, 0, 0);
-                }
-            };
-            if (ks == kKC) {
-#pragma unroll
-                for (int k = 0; k < kKC; k += 4) step(k);
-            } else {
-                for (int k = 0; k < ks; k += 4) step(k);
-            }
-        }
-    };
-    for (int c0 = 0; c0 < Kp; c0 += 2 * kKC) {
-        chunk(av[0], bv[0], c0);
-        if (c0 + kKC < Kp) chunk(av[1], bv[1], c0 + kKC);
-    }
+    k_loop(Kp, a, b, active, [&](int ks) {
+        multiply_pair<KMajor<kTile>>(re, im, a_frag(As, wave, lr, lk), KMajor<kTile>::frag(Bs, lr, lk), ks);
+    });
     if (active) {
         float *__restrict__ ct = c_out + (long)blockIdx.z * (kStage == 2 ? 2 * g.Ku * ldv : g.S * g.ldz);
-#pragma unroll
-        for (int t = 0; t < kTN; ++t)
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) {
-                const int u = u0 + wave * 16 + lk * 4 + gg, v = v0 + t * 16 + lr;
-                if (u < M && v < Hs) {
-                    if constexpr (kStage == 2) {
-                        const float f = phi[u * Hs + v];
-                        ct[(long)u * ldv + v] = __fmul_rn(re[t][gg], f);
-                        ct[(long)(M + u) * ldv + v] = __fmul_rn(im[t][gg], f);
-                    } else {
-                        ct[(long)u * g.ldz + v] = re[t][gg];
-                        ct[(long)u * g.ldz + Hs + v] = im[t][gg];
-                    }
+        for_each_output(re, im, u0, v0, wave, lk, lr, [&](int u, int v, float x, float y) {
+            if (u < M && v < Hs) {
+                if constexpr (kStage == 2) {
+                    const float f = phi[u * Hs + v];
+                    ct[(long)u * ldv + v] = __fmul_rn(x, f);
+                    ct[(long)(M + u) * ldv + v] = __fmul_rn(y, f);
+                } else {
+                    ct[(long)u * g.ldz + v] = x;
+                    ct[(long)u * g.ldz + Hs + v] = y;
                 }
             }
+        });
     }
 }
 
@@ -309,7 +161,6 @@ __global__ __launch_bounds__(kThreads) void filter_out_kernel(const void *__rest
                                                               const float *__restrict__ z_in, const float *__restrict__ w4,
                                                               const float *__restrict__ phi, int flags,
                                                               float *__restrict__ out, int *__restrict__ status) {
-    constexpr int kPerThread = kTile * kKC / 4 / kThreads;     // 4 float4 of a chunk of Z, and of W4, per thread
     __shared__ __align__(16) float As[kTile * kLd];            // [64 rows of Z][kLd]
     __shared__ __align__(16) float Ms[kTile * kLd];            // [64 rows of W4][kLd]
     const int S = g.S, K = 2 * g.Hs, Kp = g.ldz;
@@ -330,77 +181,25 @@ __global__ __launch_bounds__(kThreads) void filter_out_kernel(const void *__rest
     const float *__restrict__ zt = z_in + (long)blockIdx.z * S * g.ldz;
     const float anchor = anchor_of(raw, mode, offset), phi0 = phi[(S / 2) * g.Hs];   // Phi at k = 0, v = 0
 
-    auto fetch = [&](float4 (&v)[kPerThread], const float *__restrict__ m, int row0, int c0) {
-#pragma unroll
-        for (int k = 0; k < kPerThread; ++k) {
-            const int e = tid + k * kThreads;
-            v[k] = fetch4(m, g.ldz, S, g.ldz, row0 + (e >> 4), c0 + (e & 15) * 4);
-        }
-    };
-    auto stage = [&](const float4 (&v)[kPerThread], float *dst, int row0, int c0) {
-#pragma unroll
-        for (int k = 0; k < kPerThread; ++k) {
-            const int e = tid + k * kThreads;
-            stage4(dst + (e >> 4) * kLd + (e & 15) * 4, zero4(v[k], row0 + (e >> 4) < S, c0 + (e & 15) * 4, K));
-        }
-    };
-
+    // rows of Z and of W4 at or past S and the K positions at or past 2Hs are staged as zeros
+    const MatrixRows<kTile, kThreads, RowsFrom> z{zt, g.ldz, S, g.ldz, K, RowsFrom{i0, S}, lds_ptr(As)};
+    const MatrixRows<kTile, kThreads, RowsFrom> m{w4, g.ldz, S, g.ldz, K, RowsFrom{j0, S}, lds_ptr(Ms)};
     const bool active = i0 + wave * 16 < S;                    // wave-uniform
     f32x4 acc[kTN];
 #pragma unroll
     for (int t = 0; t < kTN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    float4 zv[2][kPerThread], mv[2][kPerThread];
-    fetch(zv[0], zt, i0, 0);
-    fetch(mv[0], w4, j0, 0);
-    if (kKC < Kp) {
-        fetch(zv[1], zt, i0, kKC);
-        fetch(mv[1], w4, j0, kKC);
-    }
-    auto chunk = [&](float4 (&z4)[kPerThread], float4 (&m4)[kPerThread], int c0) {
-        __syncthreads();                                       // the chunk before this one has been multiplied
-        stage(z4, As, i0, c0);
-        stage(m4, Ms, j0, c0);
-        __syncthreads();
-        if (c0 + 2 * kKC < Kp) {
-            fetch(z4, zt, i0, c0 + 2 * kKC);
-            fetch(m4, w4, j0, c0 + 2 * kKC);
-        }
-        if (active) {
-            const int ks = min(kKC, Kp - c0);                  // a multiple of 4
-            const float *ap = As + (wave * 16 + lr) * kLd + lk, *bp = Ms + lr * kLd + lk;
-            auto step = [&](int k) {
-                const float a = ap[k];
-#pragma unroll
-                for (int t = 0; t < kTN; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[t * 16 * kLd + k], acc[t], 0, 0, 0);
-            };
-            if (ks == kKC) {
-#pragma unroll
-                for (int k = 0; k < kKC; k += 4) step(k);
-            } else {
-                for (int k = 0; k < ks; k += 4) step(k);
-            }
-        }
-    };
-    for (int c0 = 0; c0 < Kp; c0 += 2 * kKC) {
-        chunk(zv[0], mv[0], c0);
-        if (c0 + kKC < Kp) chunk(zv[1], mv[1], c0 + kKC);
-    }
+    k_loop(Kp, z, m, active,
+           [&](int ks) { multiply<BtRows, false>(acc, a_frag(As, wave, lr, lk), BtRows::frag(Ms, lr, lk), ks); });
     if (active) {
-#pragma unroll
-        for (int t = 0; t < kTN; ++t)
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) {
-                const int i = i0 + wave * 16 + lk * 4 + gg, j = j0 + t * 16 + lr;
-                if (i < S && j < S) {
-                    float y = acc[t][gg];
-                    if (!normalize) {
-                        if (mode != SPRK_MRC_FLOAT32) y = __fmaf_rn(phi0, anchor, y);
-                        if (invert) y = -y;
-                    }
-                    o[i * S + j] = y;
+        for_each_output(acc, i0, j0, wave, lk, lr, [&](int i, int j, float y) {
+            if (i < S && j < S) {
+                if (!normalize) {
+                    if (mode != SPRK_MRC_FLOAT32) y = __fmaf_rn(phi0, anchor, y);
+                    if (invert) y = -y;
                 }
+                o[i * S + j] = y;
             }
+        });
     }
     if (!normalize && tid == 0 && blockIdx.x == 0 && blockIdx.y == 0) status[p] = 0;
 }
@@ -416,15 +215,14 @@ __global__ __launch_bounds__(kThreads) void filter_norm_kernel(Geo g, const int 
     normalize_box(out + (long)p * g.S * g.S, g.S, inv_s, R2, flags & SPRK_EXTRACT_INVERT, status + p, red);
 }
 
-inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 inline bool sizes_ok(int B, int S) { return S >= kMinSide && S <= B && B <= kMaxBox && B % 2 == 0 && S % 2 == 0; }
 inline Geo geo_of(int B, int S, int ny, int nx) {
     const int Hs = S / 2 + 1, Ku = S + 1;
     return Geo{B, S, Hs, Ku, (Hs + 3) & ~3, (2 * Hs + 3) & ~3, (B + 3) & ~3, (2 * Ku + 3) & ~3, ny, nx};
 }
-inline size_t v_bytes(const Geo &g) { return align16((size_t)2 * g.B * g.ldv * sizeof(float)); }
-inline size_t f_bytes(const Geo &g) { return align16((size_t)2 * g.Ku * g.ldv * sizeof(float)); }
-inline size_t z_bytes(const Geo &g) { return align16((size_t)g.S * g.ldz * sizeof(float)); }
+inline size_t v_bytes(const Geo &g) { return sprk::align16((size_t)2 * g.B * g.ldv * sizeof(float)); }
+inline size_t f_bytes(const Geo &g) { return sprk::align16((size_t)2 * g.Ku * g.ldv * sizeof(float)); }
+inline size_t z_bytes(const Geo &g) { return sprk::align16((size_t)g.S * g.ldz * sizeof(float)); }
 // particles per batch: the caller's, or as many as keep the workspace within kBudget (one at least)
 inline int batch_of(long P, const Geo &g, int max_batch) {
     long nb = max_batch > 0 ? max_batch : (long)(kBudget / (v_bytes(g) + f_bytes(g) + z_bytes(g)));

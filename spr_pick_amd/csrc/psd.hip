@@ -17,12 +17,13 @@
 // top of what the batches before left there, so the bits do not depend on nb.  Three launches per batch on the caller's
 // stream, no host synchronisation, no atomics:
 //   psd_rows_kernel<T>: one workgroup of four waves per 64 rows x 64 columns of one tile's U (grid.z = the tile), a wave
-//     on 16 rows with four accumulators; resample_rows_kernel's pipeline (fetch two chunks of K ahead from clamped
-//     addresses, zeros formed at staging, staged rows of 66 floats).  2H = T + 2 is never a multiple of 16: the ragged
-//     last column tile is the normal case, its rows of W1 past 2H staged as zeros and its columns not stored.
-//   psd_cols_kernel: one workgroup of four waves per 64 rows u x 64 columns v of one tile's spectrum; a wave holds the
-//     Re and the Im accumulators of its 16 rows (eight of them), so that Q needs no second pass: A is rows u and T+u of
-//     W2, B the chunk of V.
+//     on 16 rows with four accumulators; the pipeline of mfma_stage.h (fetch two chunks of K ahead from clamped
+//     addresses, zeros formed at staging, staged rows of 66 floats) with plain fragment reads.  2H = T + 2 is never a
+//     multiple of 16: the ragged last column tile is the normal case, its rows of W1 past 2H staged as zeros and its
+//     columns not stored.
+//   psd_cols_kernel: one workgroup of four waves per 64 rows u x 64 columns v of one tile's spectrum; the paired form of
+//     the same pipeline: a wave holds the Re and the Im accumulators of its 16 rows (eight of them), so that Q needs no
+//     second pass: A is rows u and T+u of W2, B the chunk of V.
 //   psd_sum_kernel: one thread per element of P over the batch's tiles.
 #include <cstdint>
 #include <type_traits>
@@ -36,7 +37,6 @@ constexpr int kMaxSide = 16384, kMinTile = 16, kMaxTile = 1024;
 constexpr int kThreads = 256;                    // four waves, both stages
 constexpr int kTile = 64;                        // 64 x 64 outputs per workgroup, both stages
 constexpr int kTN = kTile / 16;
-constexpr int kLdb = kTile + 16;                 // stage 2: floats per staged row of V
 constexpr int kMaxBatch = 65535;                 // grid.z
 constexpr size_t kBudget = (size_t)256 << 20;    // the library's own choice of a batch keeps the workspace near this
 
@@ -51,10 +51,6 @@ template <typename S>
 __global__ __launch_bounds__(kThreads) void psd_rows_kernel(const S *__restrict__ raw, Tiling g, int t0,
                                                             const float *__restrict__ w1, int ldw1,
                                                             float *__restrict__ v_out) {
-    constexpr bool kFloat = std::is_same<S, float>::value;
-    using R = typename std::conditional<kFloat, float, int>::type;
-    constexpr int kDPerThread = kTile * kKC / kThreads;        // 16 samples of a chunk per thread
-    constexpr int kMPerThread = kTile * kKC / 4 / kThreads;    // 4 float4 of a chunk of W1 per thread
     __shared__ __align__(16) float As[kTile * kLd];            // [64 rows of D][kLd]
     __shared__ __align__(16) float Ms[kTile * kLd];            // [64 rows of W1][kLd]
     const int T = g.T, H = g.H, N = 2 * g.H, half = T >> 1;
@@ -64,94 +60,24 @@ __global__ __launch_bounds__(kThreads) void psd_rows_kernel(const S *__restrict_
     const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
     const S first = raw[0];                                    // of the micrograph; every lane the same address
 
-    // thread t holds elements t, t + 256, ... of the [64][kKC] chunk; rows and columns past the tile are fetched from
-    // its last row / column (inside the image) and staged as zeros
-    auto fetch_d = [&](R (&v)[kDPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kDPerThread; ++k) {
-            const int e = tid + k * kThreads, r = r0 + (e >> 6), q = c0 + (e & 63);
-            v[k] = base[(long)min(r, T - 1) * g.nx + min(q, T - 1)];
-        }
-    };
-    auto stage_d = [&](const R (&v)[kDPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kDPerThread; ++k) {
-            const int e = tid + k * kThreads, r = r0 + (e >> 6), q = c0 + (e & 63);
-            float d;
-            if constexpr (kFloat) d = v[k];
-            else d = (float)(v[k] - (int)first);               // |difference| < 2^17: exact
-            As[(e >> 6) * kLd + (e & 63)] = (r < T && q < T) ? d : 0.0f;
-        }
-    };
-    auto fetch_m = [&](float4 (&v)[kMPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kMPerThread; ++k) {
-            const int e = tid + k * kThreads;
-            v[k] = fetch4(w1, ldw1, N, T, q0 + (e >> 4), c0 + (e & 15) * 4);
-        }
-    };
-    auto stage_m = [&](const float4 (&v)[kMPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kMPerThread; ++k) {
-            const int e = tid + k * kThreads;
-            stage4(Ms + (e >> 4) * kLd + (e & 15) * 4, zero4(v[k], q0 + (e >> 4) < N, c0 + (e & 15) * 4, T));
-        }
-    };
-
+    // rows and columns past the tile are fetched from its last row / column (inside the image); rows of W1 past 2H are
+    // staged as zeros
+    const SampleRows<S, kThreads> d{base, g.nx, T, T, r0, first, lds_ptr(As)};
+    const MatrixRows<kTile, kThreads, RowsFrom> m{w1, ldw1, N, T, T, RowsFrom{q0, N}, lds_ptr(Ms)};
     const bool active = r0 + wave * 16 < T;                    // wave-uniform
     f32x4 acc[kTN];
 #pragma unroll
     for (int t = 0; t < kTN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    R dv[2][kDPerThread];
-    float4 mv[2][kMPerThread];
-    fetch_d(dv[0], 0);
-    fetch_m(mv[0], 0);
-    if (kKC < T) {
-        fetch_d(dv[1], kKC);
-        fetch_m(mv[1], kKC);
-    }
-    auto chunk = [&](R (&d)[kDPerThread], float4 (&mm)[kMPerThread], int c0) {
-        __syncthreads();                                       // the chunk before this one has been multiplied
-        stage_d(d, c0);
-        stage_m(mm, c0);
-        __syncthreads();
-        if (c0 + 2 * kKC < T) {
-            fetch_d(d, c0 + 2 * kKC);
-            fetch_m(mm, c0 + 2 * kKC);
-        }
-        if (active) {
-            const int ks = min(kKC, T - c0);                   // a multiple of 16
-            const float *ap = As + (wave * 16 + lr) * kLd + lk, *bp = Ms + lr * kLd + lk;
-            auto step = [&](int k) {
-                const float a = ap[k];
-#pragma unroll
-                for (int t = 0; t < kTN; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[t * 16 * kLd + k], acc[t], 0, 0, 0);
-            };
-            if (ks == kKC) {
-#pragma unroll
-                for (int k = 0; k < kKC; k += 4) step(k);
-            } else {
-                for (int k = 0; k < ks; k += 4) step(k);
-            }
-        }
-    };
-    for (int c0 = 0; c0 < T; c0 += 2 * kKC) {
-        chunk(dv[0], mv[0], c0);
-        if (c0 + kKC < T) chunk(dv[1], mv[1], c0 + kKC);
-    }
+    k_loop(T, d, m, active,                                    // T is a multiple of 16: no K position is padded
+           [&](int ks) { multiply<BtRows, false>(acc, a_frag(As, wave, lr, lk), BtRows::frag(Ms, lr, lk), ks); });
     if (active) {
         float *__restrict__ vt = v_out + (long)blockIdx.z * 2 * T * g.ldv;
-#pragma unroll
-        for (int t = 0; t < kTN; ++t)
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) {
-                const int r = r0 + wave * 16 + lk * 4 + gg, q = q0 + t * 16 + lr;
-                if (r < T && q < N) {
-                    const int part = q >= H;                   // the sine half goes below the cosine half
-                    vt[(long)(part * T + r) * g.ldv + (q - part * H)] = acc[t][gg];
-                }
-            }
+        for_each_output(acc, r0, q0, wave, lk, lr, [&](int r, int q, float u) {
+            // the sine half goes below the cosine half; the address is formed outside the condition, so once per tile
+            const int part = q >= H;
+            float *p = vt + (long)(part * T + r) * g.ldv + (q - part * H);
+            if (r < T && q < N) *p = u;
+        });
     }
 }
 
@@ -160,103 +86,29 @@ __global__ __launch_bounds__(kThreads) void psd_rows_kernel(const S *__restrict_
 __global__ __launch_bounds__(kThreads) void psd_cols_kernel(const float *__restrict__ w2, int ldw2,
                                                             const float *__restrict__ v_in, Tiling g,
                                                             float *__restrict__ q_out) {
-    constexpr int kAPerThread = 2 * kTile * kKC / 4 / kThreads;    // 8 float4 of a chunk of W2 (rows u and T+u)
-    constexpr int kBPerThread = kKC * kTile / 4 / kThreads;        // 4 float4 of a chunk of V
-    constexpr int kBRow4 = kTile / 4;
+    using VRows = KMajorRows<kTile, kThreads, true>;
     __shared__ __align__(16) float As[2 * kTile * kLd];        // [64 rows u, then 64 rows T+u][kLd]
-    __shared__ __align__(16) float Bs[kKC * kLdb];             // [rows of V = K][kLdb]
+    __shared__ __align__(16) float Bs[kKC * VRows::kLdb];      // [rows of V = K][kLdb]
     const int T = g.T, H = g.H, K = 2 * g.T, ldv = g.ldv;
     const float *__restrict__ vt = v_in + (long)blockIdx.z * K * ldv;
     const int u0 = blockIdx.y * kTile, v0 = blockIdx.x * kTile;
     const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
 
-    // staged row rr < 64 is row u0 + rr of W2, staged row 64 + rr is row T + u0 + rr; rows at or past T of either half
-    // are fetched from a row that exists and staged as zeros
-    auto fetch_a = [&](float4 (&v)[kAPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kAPerThread; ++k) {
-            const int e = tid + k * kThreads, rr = e >> 4, u = u0 + (rr & (kTile - 1));
-            v[k] = fetch4(w2, ldw2, K, K, (rr >= kTile ? T : 0) + min(u, T - 1), c0 + (e & 15) * 4);
-        }
-    };
-    auto stage_a = [&](const float4 (&v)[kAPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kAPerThread; ++k) {
-            const int e = tid + k * kThreads, rr = e >> 4;
-            stage4(As + rr * kLd + (e & 15) * 4, zero4(v[k], u0 + (rr & (kTile - 1)) < T, c0 + (e & 15) * 4, K));
-        }
-    };
-    // rows c0 .. of V, columns v0 .. v0+63 (ldv and v0 are multiples of 4).  Columns H .. ldv-1 were never written: they
-    // are staged as zeros, like everything past ldv; both reach only output columns that are not stored
-    auto fetch_b = [&](float4 (&v)[kBPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kBPerThread; ++k) {
-            const int e = tid + k * kThreads;
-            v[k] = fetch4(vt, ldv, K, ldv, c0 + e / kBRow4, v0 + (e % kBRow4) * 4);
-        }
-    };
-    auto stage_b = [&](const float4 (&v)[kBPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kBPerThread; ++k) {
-            const int e = tid + k * kThreads, j = v0 + (e % kBRow4) * 4;
-            *reinterpret_cast<float4 *>(Bs + (e / kBRow4) * kLdb + (e % kBRow4) * 4) =
-                zero4(v[k], c0 + e / kBRow4 < K && j < ldv, j, H);
-        }
-    };
-
+    // A: rows u and T + u of W2.  B: columns H .. ldv-1 of V were never written: staged as zeros
+    const MatrixRows<2 * kTile, kThreads, RowPairs> a{w2, ldw2, K, K, K, RowPairs{u0, T}, lds_ptr(As)};
+    const VRows b{vt, ldv, K, v0, H, lds_ptr(Bs)};
     const bool active = u0 + wave * 16 < T;                    // wave-uniform
     f32x4 re[kTN], im[kTN];
 #pragma unroll
     for (int t = 0; t < kTN; ++t) re[t] = im[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    float4 av[2][kAPerThread], bv[2][kBPerThread];
-    fetch_a(av[0], 0);
-    fetch_b(bv[0], 0);
-    if (kKC < K) {
-        fetch_a(av[1], kKC);
-        fetch_b(bv[1], kKC);
-    }
-    auto chunk = [&](float4 (&a4)[kAPerThread], float4 (&b4)[kBPerThread], int c0) {
-        __syncthreads();                                       // the chunk before this one has been multiplied
-        stage_a(a4, c0);
-        stage_b(b4, c0);
-        __syncthreads();
-        if (c0 + 2 * kKC < K) {
-            fetch_a(a4, c0 + 2 * kKC);
-            fetch_b(b4, c0 + 2 * kKC);
-        }
-        if (active) {
-            const int ks = min(kKC, K - c0);                   // a multiple of 32
-            const float *ap = As + (wave * 16 + lr) * kLd + lk, *bp = Bs + lk * kLdb + lr;
-            auto step = [&](int k) {
-                const float a_re = ap[k], a_im = ap[kTile * kLd + k];
-#pragma unroll
-                for (int t = 0; t < kTN; ++t) {
-                    const float b = bp[k * kLdb + t * 16];
-                    re[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_re, b, re[t], 0, 0, 0);
-                    im[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_im, b, im[t], 0, 0, 0);
-                }
-            };
-            if (ks == kKC) {
-#pragma unroll
-                for (int k = 0; k < kKC; k += 4) step(k);
-            } else {
-                for (int k = 0; k < ks; k += 4) step(k);
-            }
-        }
-    };
-    for (int c0 = 0; c0 < K; c0 += 2 * kKC) {
-        chunk(av[0], bv[0], c0);
-        if (c0 + kKC < K) chunk(av[1], bv[1], c0 + kKC);
-    }
+    k_loop(K, a, b, active, [&](int ks) {
+        multiply_pair<KMajor<kTile>>(re, im, a_frag(As, wave, lr, lk), KMajor<kTile>::frag(Bs, lr, lk), ks);
+    });
     if (active) {
         float *__restrict__ qt = q_out + (long)blockIdx.z * T * H;
-#pragma unroll
-        for (int t = 0; t < kTN; ++t)
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) {
-                const int u = u0 + wave * 16 + lk * 4 + gg, v = v0 + t * 16 + lr;
-                if (u < T && v < H) qt[(long)u * H + v] = __fmaf_rn(im[t][gg], im[t][gg], __fmul_rn(re[t][gg], re[t][gg]));
-            }
+        for_each_output(re, im, u0, v0, wave, lk, lr, [&](int u, int v, float x, float y) {
+            if (u < T && v < H) qt[(long)u * H + v] = __fmaf_rn(y, y, __fmul_rn(x, x));
+        });
     }
 }
 
@@ -270,13 +122,12 @@ __global__ __launch_bounds__(256) void psd_sum_kernel(const float *__restrict__ 
     p[e] = acc;
 }
 
-inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 inline bool tile_ok(int T) { return T >= kMinTile && T <= kMaxTile && T % 16 == 0; }
 inline bool sizes_ok(int ny, int nx, int T) { return T <= ny && ny <= kMaxSide && T <= nx && nx <= kMaxSide; }
 inline long tiles_of(int ny, int nx, int T) { return (long)((ny - T) / (T / 2) + 1) * ((nx - T) / (T / 2) + 1); }
 inline int ldv_of(int T) { return (T / 2 + 1 + 3) & ~3; }
-inline size_t v_bytes(int T) { return align16((size_t)2 * T * ldv_of(T) * sizeof(float)); }
-inline size_t q_bytes(int T) { return align16((size_t)T * (T / 2 + 1) * sizeof(float)); }
+inline size_t v_bytes(int T) { return sprk::align16((size_t)2 * T * ldv_of(T) * sizeof(float)); }
+inline size_t q_bytes(int T) { return sprk::align16((size_t)T * (T / 2 + 1) * sizeof(float)); }
 // tiles per batch: the caller's, or as many as keep the workspace within kBudget (one at least)
 inline int batch_of(long ntiles, int T, int max_batch) {
     long nb = max_batch > 0 ? max_batch : (long)(kBudget / (v_bytes(T) + q_bytes(T)));

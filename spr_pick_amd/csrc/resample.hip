@@ -13,11 +13,13 @@
 //
 // Stage 1, resample_rows_kernel: one workgroup of four waves per 64 rows x 64 columns of U, a wave on 16 rows with four
 // independent accumulators (a dependent 16x16x4 chain has 40 cycles of latency against 32 of issue).  K runs in chunks
-// of 64 through LDS: the samples by element loads of their own type (rows are not 16-byte aligned when nx is odd),
-// converted once; the 64 rows of Mx as float4.  The next two chunks are in registers before the current one is
-// multiplied: fetches are unconditional loads from clamped addresses that nothing touches until they are staged, and the
-// zeros of the padding are formed at staging (fetch4 / zero4, mfma_stage.h).  A staged row is 66 floats: lane (row, k) of a
-// fragment read sits on bank 2*row + k.  A chunk's fragment reads run a group of four MFMA steps ahead (mfma_chunk).
+// of 64 through LDS by the pipeline of mfma_stage.h (its loaders, K loop, multiply and accumulator walk; both kernels
+// here are their index set-up, two loader descriptions and an epilogue): the samples by element loads of their own type
+// (rows are not 16-byte aligned when nx is odd), converted once; the 64 rows of Mx as float4.  The next two chunks are
+// in registers before the current one is multiplied: fetches are unconditional loads from clamped addresses that nothing
+// touches until they are staged, and the zeros of the padding are formed at staging.  A staged row is 66 floats: lane
+// (row, k) of a fragment read sits on bank 2*row + k.  A chunk's fragment reads run a group of four MFMA steps ahead
+// (multiply<..., true>: mfma_chunk).
 // Stage 2, resample_cols_kernel<WM, TN>: one workgroup of WM waves per 16*WM rows x 16*TN columns of Y; rows of My as
 // float4, U [64 rows of K, 16*TN columns] as float4 into rows of 16*TN + 16 floats (the two k rows a half wave reads land
 // on different banks).  The output is small (512^2 is 64 tiles of 64 x 64 on 256 CUs), so the tile drops to 32 x 32 on
@@ -37,8 +39,6 @@ constexpr int kMaxSide = 16384;                  // a side of the image at most:
 constexpr int kRowsThreads = 256;                // stage 1: four waves
 constexpr int kRowsTile = 64;                    // ... on 64 rows x 64 columns of U
 constexpr int kRowsTN = kRowsTile / 16;
-constexpr int kDPerThread = kRowsTile * kKC / kRowsThreads;        // 16 samples of a chunk per thread
-constexpr int kMPerThread = kRowsTile * kKC / 4 / kRowsThreads;    // 4 float4 of a chunk of Mx per thread
 constexpr int kRangeThreads = 256;
 constexpr size_t kHeadBytes = 16;                // the workspace starts with the anchor (one float), then the pairs, then U
 
@@ -97,37 +97,6 @@ __global__ __launch_bounds__(kRangeThreads) void resample_range_kernel(const Par
     }
 }
 
-// One whole chunk of K for a wave's TN accumulators: kKC / 4 MFMA steps per accumulator, k ascending.  The fragment reads
-// of kGroup steps (ap[k]: A at this lane's row; bp[t * b_tile + k * b_step]: B of tile t) are issued a group ahead of
-// the MFMAs that consume them, so that the LDS latency hides behind a group's MFMAs instead of standing before each step.
-constexpr int kGroup = 4;
-template <int TN>
-__device__ __forceinline__ void mfma_chunk(f32x4 (&acc)[TN], const float *ap, const float *bp, int b_tile, int b_step) {
-    constexpr int kGroups = kKC / 4 / kGroup;
-    float a[2][kGroup], b[2][TN][kGroup];
-    auto load = [&](int buf, int g) {
-#pragma unroll
-        for (int q = 0; q < kGroup; ++q) {
-            const int k = (g * kGroup + q) * 4;
-            a[buf][q] = ap[k];
-#pragma unroll
-            for (int t = 0; t < TN; ++t) b[buf][t][q] = bp[t * b_tile + k * b_step];
-        }
-    };
-    load(0, 0);
-#pragma unroll
-    for (int g = 0; g < kGroups; ++g) {
-        __builtin_amdgcn_sched_barrier(0);                     // the scheduler otherwise moves every read back to its MFMA
-        if (g + 1 < kGroups) load((g + 1) & 1, g + 1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < kGroup; ++q)
-#pragma unroll
-            for (int t = 0; t < TN; ++t)
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g & 1][q], b[g & 1][t][q], acc[t], 0, 0, 0);
-    }
-}
-
 // ---- stage 1: U[r0 .. r0+63, j0 .. j0+63] = D Mx^T --------------------------------------------------------------------
 // grid (ceil(bx / 64), ceil(ny / 64)); every row r < ny of U is written in columns 0 .. ldu-1 (ldu = roundup(bx, 4) <= the
 // grid's columns; columns bx .. ldu-1 are the products with zero rows of Mx: zeros)
@@ -137,9 +106,6 @@ __global__ __launch_bounds__(kRowsThreads) void resample_rows_kernel(const T *__
                                                                      float *__restrict__ u, int ldu,
                                                                      float *__restrict__ anchor_out) {
     constexpr bool kFloat = std::is_same<T, float>::value;
-    // a fetched sample in its register: widened by the load itself (packed pairs of 16-bit samples would need an
-    // operation on the loaded value right behind the load, and with it a wait)
-    using R = typename std::conditional<kFloat, float, int>::type;
     __shared__ __align__(16) float As[kRowsTile * kLd];        // [64 rows of D][kLd]
     __shared__ __align__(16) float Ms[kRowsTile * kLd];        // [64 rows of Mx][kLd]
     const int r0 = blockIdx.y * kRowsTile, j0 = blockIdx.x * kRowsTile;
@@ -148,91 +114,20 @@ __global__ __launch_bounds__(kRowsThreads) void resample_rows_kernel(const T *__
     const T first = raw[0];                                    // every lane the same address: a broadcast
     if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *anchor_out = kFloat ? 0.0f : (float)first;
 
-    // the chunk of D at rows r0 .., columns c0 ..: thread t holds elements t, t + 256, ... of the [64][kKC] chunk (a wave
-    // reads 64 adjacent samples of one row); positions past the image are fetched from its last row / column and staged as 0
-    auto fetch_d = [&](R (&v)[kDPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kDPerThread; ++k) {
-            const int e = tid + k * kRowsThreads, r = r0 + (e >> 6), q = c0 + (e & 63);
-            v[k] = raw[(long)min(r, ny - 1) * nx + min(q, nx - 1)];
-        }
-    };
-    auto stage_d = [&](const R (&v)[kDPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kDPerThread; ++k) {
-            const int e = tid + k * kRowsThreads, r = r0 + (e >> 6), q = c0 + (e & 63);
-            float d;
-            if constexpr (kFloat) d = v[k];
-            else d = (float)(v[k] - (int)first);               // |difference| < 2^17: exact
-            As[(e >> 6) * kLd + (e & 63)] = (r < ny && q < nx) ? d : 0.0f;
-        }
-    };
-    // rows j0 .. j0+63 of Mx, columns c0 .. c0+kKC-1, as float4 (mx and ldmx are 16-byte aligned); rows past bx and
-    // columns past nx are staged as zeros
-    auto fetch_m = [&](float4 (&v)[kMPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kMPerThread; ++k) {
-            const int e = tid + k * kRowsThreads;
-            v[k] = fetch4(mx, ldmx, bx, Kp4, j0 + (e >> 4), c0 + (e & 15) * 4);
-        }
-    };
-    auto stage_m = [&](const float4 (&v)[kMPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kMPerThread; ++k) {
-            const int e = tid + k * kRowsThreads;
-            stage4(Ms + (e >> 4) * kLd + (e & 15) * 4, zero4(v[k], j0 + (e >> 4) < bx, c0 + (e & 15) * 4, nx));
-        }
-    };
-
+    // positions past the image are fetched from its last row / column and staged as 0; rows of Mx past bx and its
+    // columns past nx (mx and ldmx are 16-byte aligned) are staged as zeros
+    const SampleRows<T, kRowsThreads> d{raw, nx, ny, nx, r0, first, lds_ptr(As)};
+    const MatrixRows<kRowsTile, kRowsThreads, RowsFrom> m{mx, ldmx, bx, Kp4, nx, RowsFrom{j0, bx}, lds_ptr(Ms)};
     const bool active = r0 + wave * 16 < ny;                   // wave-uniform
     f32x4 acc[kRowsTN];
 #pragma unroll
     for (int t = 0; t < kRowsTN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    R dv[2][kDPerThread];
-    float4 mv[2][kMPerThread];
-    fetch_d(dv[0], 0);
-    fetch_m(mv[0], 0);
-    if (kKC < Kp4) {
-        fetch_d(dv[1], kKC);
-        fetch_m(mv[1], kKC);
-    }
-    auto chunk = [&](R (&d)[kDPerThread], float4 (&mm)[kMPerThread], int c0) {
-        __syncthreads();                                       // the chunk before this one has been multiplied
-        stage_d(d, c0);
-        stage_m(mm, c0);
-        __syncthreads();
-        if (c0 + 2 * kKC < Kp4) {
-            fetch_d(d, c0 + 2 * kKC);
-            fetch_m(mm, c0 + 2 * kKC);
-        }
-        if (active) {
-            const int ks = min(kKC, Kp4 - c0);
-            const float *ap = As + (wave * 16 + lr) * kLd + lk, *bp = Ms + lr * kLd + lk;
-            auto step = [&](int k) {
-                const float a = ap[k];
-#pragma unroll
-                for (int t = 0; t < kRowsTN; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[t * 16 * kLd + k], acc[t], 0, 0, 0);
-            };
-            if (ks == kKC) {
-                mfma_chunk<kRowsTN>(acc, ap, bp, 16 * kLd, 1);
-            } else {
-                for (int k = 0; k < ks; k += 4) step(k);
-            }
-        }
-    };
-    for (int c0 = 0; c0 < Kp4; c0 += 2 * kKC) {
-        chunk(dv[0], mv[0], c0);
-        if (c0 + kKC < Kp4) chunk(dv[1], mv[1], c0 + kKC);
-    }
+    k_loop(Kp4, d, m, active,
+           [&](int ks) { multiply<BtRows, true>(acc, a_frag(As, wave, lr, lk), BtRows::frag(Ms, lr, lk), ks); });
     if (active) {
-#pragma unroll
-        for (int t = 0; t < kRowsTN; ++t)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int r = r0 + wave * 16 + lk * 4 + g, j = j0 + t * 16 + lr;
-                if (r < ny && j < ldu) u[(long)r * ldu + j] = acc[t][g];
-            }
+        for_each_output(acc, r0, j0, wave, lk, lr, [&](int r, int j, float v) {
+            if (r < ny && j < ldu) u[(long)r * ldu + j] = v;
+        });
     }
 }
 
@@ -243,116 +138,42 @@ __global__ __launch_bounds__(64 * WM) void resample_cols_kernel(const float *__r
                                                                 const float *__restrict__ u, int ldu, int ny, int by,
                                                                 int bx, const float *__restrict__ anchor_in,
                                                                 float *__restrict__ out, Part *__restrict__ parts) {
-    constexpr int kThreads = 64 * WM, kRows = 16 * WM, W = 16 * TN, kLdb = W + 16;
-    constexpr int kAPerThread = kRows * kKC / 4 / kThreads;    // 4 float4 of a chunk of My per thread
-    constexpr int kBPerThread = kKC * W / 4 / kThreads;        // float4 of a chunk of U per thread
-    constexpr int kBRow4 = W / 4;                              // float4 per staged row of U
-    static_assert(kRows * kKC / 4 % kThreads == 0 && kKC * W / 4 % kThreads == 0, "whole float4 per thread");
+    constexpr int kThreads = 64 * WM, kRows = 16 * WM, W = 16 * TN;
+    using URows = KMajorRows<W, kThreads, false>;
     __shared__ __align__(16) float As[kRows * kLd];            // [rows of My][kLd]
-    __shared__ __align__(16) float Bs[kKC * kLdb];             // [rows of U = K][kLdb]
+    __shared__ __align__(16) float Bs[kKC * URows::kLdb];      // [rows of U = K][kLdb]
     const int i0 = blockIdx.y * kRows, j0 = blockIdx.x * W;
     const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
     const int Kp4 = (ny + 3) & ~3;
 
-    // rows i0 .. of My, columns c0 .. c0+kKC-1 (my and ldmy are 16-byte aligned); rows past by and columns past ny are
-    // staged as zeros
-    auto fetch_a = [&](float4 (&v)[kAPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kAPerThread; ++k) {
-            const int e = tid + k * kThreads;
-            v[k] = fetch4(my, ldmy, by, Kp4, i0 + (e >> 4), c0 + (e & 15) * 4);
-        }
-    };
-    auto stage_a = [&](const float4 (&v)[kAPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kAPerThread; ++k) {
-            const int e = tid + k * kThreads;
-            stage4(As + (e >> 4) * kLd + (e & 15) * 4, zero4(v[k], i0 + (e >> 4) < by, c0 + (e & 15) * 4, ny));
-        }
-    };
-    // rows c0 .. c0+kKC-1 of U, columns j0 .. j0+W-1 (u is 16-byte aligned, ldu and j0 multiples of 4).  Rows at or past
-    // ny were never written: fetched from row ny-1 instead and staged as zeros.  Columns at or past ldu likewise; they
-    // reach only output columns that are not stored
-    auto fetch_b = [&](float4 (&v)[kBPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kBPerThread; ++k) {
-            const int e = tid + k * kThreads;
-            v[k] = fetch4(u, ldu, ny, ldu, c0 + e / kBRow4, j0 + (e % kBRow4) * 4);
-        }
-    };
-    auto stage_b = [&](const float4 (&v)[kBPerThread], int c0) {
-#pragma unroll
-        for (int k = 0; k < kBPerThread; ++k) {
-            const int e = tid + k * kThreads, j = j0 + (e % kBRow4) * 4;
-            *reinterpret_cast<float4 *>(Bs + (e / kBRow4) * kLdb + (e % kBRow4) * 4) =
-                zero4(v[k], c0 + e / kBRow4 < ny && j < ldu, 0, 4);
-        }
-    };
-
+    // A: rows of My past by and columns past ny are staged as zeros (my and ldmy are 16-byte aligned).  B: rows of U at or
+    // past ny were never written: fetched from row ny-1 instead and staged as zeros; every column below ldu was written
+    const MatrixRows<kRows, kThreads, RowsFrom> a{my, ldmy, by, Kp4, ny, RowsFrom{i0, by}, lds_ptr(As)};
+    const URows b{u, ldu, ny, j0, ldu, lds_ptr(Bs)};
     const bool active = i0 + wave * 16 < by;                   // wave-uniform
     f32x4 acc[TN];
 #pragma unroll
     for (int t = 0; t < TN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    float4 av[2][kAPerThread], bv[2][kBPerThread];
-    fetch_a(av[0], 0);
-    fetch_b(bv[0], 0);
-    if (kKC < Kp4) {
-        fetch_a(av[1], kKC);
-        fetch_b(bv[1], kKC);
-    }
-    auto chunk = [&](float4 (&a4)[kAPerThread], float4 (&b4)[kBPerThread], int c0) {
-        __syncthreads();                                       // the chunk before this one has been multiplied
-        stage_a(a4, c0);
-        stage_b(b4, c0);
-        __syncthreads();
-        if (c0 + 2 * kKC < Kp4) {
-            fetch_a(a4, c0 + 2 * kKC);
-            fetch_b(b4, c0 + 2 * kKC);
-        }
-        if (active) {
-            const int ks = min(kKC, Kp4 - c0);
-            const float *ap = As + (wave * 16 + lr) * kLd + lk, *bp = Bs + lk * kLdb + lr;
-            auto step = [&](int k) {
-                const float a = ap[k];
-#pragma unroll
-                for (int t = 0; t < TN; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[k * kLdb + t * 16], acc[t], 0, 0, 0);
-            };
-            if (ks == kKC) {
-                mfma_chunk<TN>(acc, ap, bp, 16, kLdb);
-            } else {
-                for (int k = 0; k < ks; k += 4) step(k);
-            }
-        }
-    };
-    for (int c0 = 0; c0 < Kp4; c0 += 2 * kKC) {
-        chunk(av[0], bv[0], c0);
-        if (c0 + kKC < Kp4) chunk(av[1], bv[1], c0 + kKC);
-    }
+    k_loop(Kp4, a, b, active,
+           [&](int ks) { multiply<KMajor<W>, true>(acc, a_frag(As, wave, lr, lk), KMajor<W>::frag(Bs, lr, lk), ks); });
 
     unsigned int lo = 0xffffffffu, hi = 0u;
     if (active) {
         const float anchor = anchor_in ? *anchor_in : 0.0f;
-#pragma unroll
-        for (int t = 0; t < TN; ++t)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int i = i0 + wave * 16 + lk * 4 + g, j = j0 + t * 16 + lr;
-                if (i < by && j < bx) {
-                    float y = acc[t][g];
-                    if (anchor_in) y = __fadd_rn(y, anchor);
-                    out[(long)i * bx + j] = y;
-                    const unsigned int k = enc(y);
-                    lo = min(lo, k);
-                    hi = max(hi, k);
-                }
+        for_each_output(acc, i0, j0, wave, lk, lr, [&](int i, int j, float y) {
+            if (i < by && j < bx) {
+                if (anchor_in) y = __fadd_rn(y, anchor);
+                out[(long)i * bx + j] = y;
+                const unsigned int k = enc(y);
+                lo = min(lo, k);
+                hi = max(hi, k);
             }
+        });
     }
     // every workgroup stores its pair (each holds at least one output): nothing to initialise
     if (block_reduce<kThreads>(lo, hi)) parts[blockIdx.y * gridDim.x + blockIdx.x] = Part{lo, hi};
 }
 
-inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 inline int ldu_of(int bx) { return (bx + 3) & ~3; }
 // the most workgroups stage 2 can have (its smaller tile): the pairs' share of the workspace
 inline size_t max_parts(int by, int bx) { return (size_t)sprk::cdiv(by, 32) * sprk::cdiv(bx, 32); }
@@ -385,7 +206,7 @@ extern "C" {
 
 size_t sprk_ingest_resample_ws_bytes(int ny, int nx, int by, int bx) {
     if (!sizes_ok(ny, nx, by, bx)) return 0;
-    return kHeadBytes + align16(max_parts(by, bx) * sizeof(Part)) + (size_t)ny * ldu_of(bx) * sizeof(float);
+    return kHeadBytes + sprk::align16(max_parts(by, bx) * sizeof(Part)) + (size_t)ny * ldu_of(bx) * sizeof(float);
 }
 
 int sprk_ingest_resample(const void *raw, int mode, int ny, int nx, int by, int bx, const float *my, int ldmy,
@@ -409,7 +230,7 @@ int sprk_ingest_resample(const void *raw, int mode, int ny, int nx, int by, int 
     hipStream_t s = (hipStream_t)stream;
     float *anchor = (float *)ws;
     Part *parts = (Part *)((char *)ws + kHeadBytes);
-    float *u = (float *)((char *)parts + align16(max_parts(by, bx) * sizeof(Part)));
+    float *u = (float *)((char *)parts + sprk::align16(max_parts(by, bx) * sizeof(Part)));
     int rc;
     switch (mode) {
         case SPRK_MRC_INT8: rc = launch_rows<int8_t>(raw, ny, nx, bx, mx, ldmx, u, anchor, s); break;

@@ -12,7 +12,9 @@ from test_resample_cpu import make_image
 
 # (ny, nx, T) of the bit-exact GPU comparison (tests/test_gpu_psd.py), int16: one tile; margins on both axes; T not a power
 # of two; a wide image; K of several chunks, several output tiles and the ragged 2H = 130; 511 tiles
-SHAPES = [(32, 32, 32), (100, 70, 32), (97, 131, 48), (64, 200, 64), (130, 257, 128), (17, 4100, 16)]
+# (160, 241, 160): stage 1 with K = 160 (three chunks of 64, a tail of 32), stage 2 with K = 320 (five chunks), three row
+# blocks with the last one half inactive, 2H = 162 ragged, two tiles on an odd pitch
+SHAPES = [(32, 32, 32), (100, 70, 32), (97, 131, 48), (64, 200, 64), (130, 257, 128), (160, 241, 160), (17, 4100, 16)]
 MODES_SHAPE = (45, 61, 16)                       # odd pitch, margins on both axes, 24 tiles
 
 
