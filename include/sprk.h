@@ -654,7 +654,36 @@ size_t sprk_ingest_resample_ws_bytes(int ny, int nx, int by, int bx);
 int sprk_ingest_resample(const void *raw, int mode, int ny, int nx, int by, int bx, const float *my, int ldmy,
                          const float *mx, int ldmx, float *out, float *range_out, void *ws, size_t ws_bytes, void *stream);
 
-/* ---- tiled power spectra (`joint ctf`) -----------------------------------------------------
+/* ---- whole-frame motion correction of movies (`joint align`) --------------------------------
+ * sprk_align_corr: the periodic cross-correlation window of Z reduced frames a [Z, Sy, Sx] fp32 against their references
+ * (frame f's at r + f * r_stride floats; r_stride 0: one shared reference), for the row and column shifts -R .. R:
+ *   cc[f, i, j] = fmaf chain, from 0.0f, over y' = 0 .. Sy-1 and then x = 0 .. Sx-1 ascending of
+ *                 a[f, (y' - (i-R)) mod Sy, x] * r[f, y', (x + (j-R)) mod Sx],       cc [Z, 2R+1, 2R+1] fp32,
+ * one fp32 GEMM per frame on MFMA (M and N the shifts, K the Sy*Sx pixels, never split): the bytes do not depend on the
+ * tiling.  A frame displaced by d against its reference (a(p) = r(p - d)) has its peak at shift -d.
+ * 1 <= R <= 31, Sx a multiple of 64 (so 2R+1 <= Sx), 1 <= Sy, Sy and Sx at most 16384, 1 <= Z <= 65535 (Sy may be smaller
+ * than the window: the rows roll modulo Sy); a 16-byte aligned; r_stride 0 or at least Sy*Sx.  tile: 0 = the library's choice (the largest of 64, 32, 16 that gives every compute unit a workgroup,
+ * else 16), or one of them.  Anything else: SPRK_EINVAL, nothing launched.  One launch on `stream`, no workspace, no host
+ * synchronisation, no atomics.
+ *
+ * sprk_align_accumulate: one frame into a running sum, y (+)= My D Mx^T: sprk_ingest_resample's two GEMMs (its arguments,
+ * sizes, matrices and their padding) with
+ *   D = (float)(x - anchor) for the integer modes (anchor: a sample value, passed by value: no device read), x for float32
+ *       (anchor 0);
+ *   U[r, j] = fmaf chain over c ascending of D[r, c] * mx[j, c], from 0.0f (U [ny, roundup(bx, 4)] in the workspace);
+ *   y[i, j] = fmaf chain over r ascending of my[i, r] * U[r, j], from 0.0f if `first`, else from the y[i, j] already there
+ * (y [by, bx] fp32, 16-byte aligned, not read when `first`).  Z calls in frame order give the bits of one chain over
+ * (frame, r) ascending.  No anchor is added back and no range is formed: with matrices whose rows sum to 1 the caller adds
+ * Z * anchor once.  Refusals as sprk_ingest_resample's, and an anchor that is no sample value of the mode (SPRK_EINVAL); a
+ * short workspace: SPRK_EWORKSPACE; nothing launched.  Two launches on `stream`, no host synchronisation, no atomics. */
+int sprk_align_corr(const float *a, const float *r, long r_stride, int Z, int Sy, int Sx, int R, int tile, float *cc,
+                    void *stream);
+size_t sprk_align_accumulate_ws_bytes(int ny, int nx, int by, int bx);
+int sprk_align_accumulate(const void *raw, int mode, int ny, int nx, int by, int bx, const float *my, int ldmy,
+                          const float *mx, int ldmx, float anchor, float *y, int first, void *ws, size_t ws_bytes,
+                          void *stream);
+
+/* ---- tiled power spectra (`joint ctf`)-----------------------------------------------------
  * sprk_psd_tiles: the summed half-plane power spectrum of T x T tiles of ONE raw micrograph (raw as for sprk_ingest_bin:
  * [ny,nx] samples of mode 0 / 1 / 2 / 6, 16-byte aligned start; rows may be only itemsize-aligned).  T a multiple of 16 in
  * 16..1024, T <= ny, nx <= 16384, H = T/2 + 1.  Tiles at a step of T/2: ty = (ny - T) / (T/2) + 1 rows of tx = (nx - T) /

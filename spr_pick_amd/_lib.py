@@ -139,6 +139,10 @@ _SIGS = {
     "sprk_ingest_flatten": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_vp, c_sz, c_vp]),
     "sprk_ingest_resample_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "sprk_ingest_resample": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_f, c_f, c_vp, c_sz, c_vp]),
+    "sprk_align_corr": (c_i, [c_f, c_f, ctypes.c_long, c_i, c_i, c_i, c_i, c_i, c_f, c_vp]),
+    "sprk_align_accumulate_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "sprk_align_accumulate": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, ctypes.c_float, c_f, c_i, c_vp, c_sz,
+                                    c_vp]),
     "sprk_psd_tiles_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "sprk_psd_tiles": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i, c_f, c_vp, c_sz, c_vp]),
     "sprk_ctf_score_ws_bytes": (c_sz, [c_i, c_i]),

@@ -1,0 +1,381 @@
+"""``joint align``: whole-frame motion correction of movies on the device — the step before ``joint bin`` /
+``joint eval --bin`` / ``joint ctf`` / ``joint extract``, in place of a MotionCor2 or ``relion_motioncorr`` run.
+
+A movie is an MRC stack of Z >= 2 short-exposure frames (modes 0 / 1 / 2 / 6), gain-corrected.  Per movie:
+
+* every frame is uploaded through two pinned slots (``MovieReader``) and Fourier-cropped to about ``align_size`` pixels a
+  side (``align_geometry``; ``torch.ops.sprk.ingest_resample``), its mean taken out;
+* the shifts are estimated on the reduced frames (``estimate_shifts``): each frame, as it is, is cross-correlated
+  (``torch.ops.sprk.align_corr``, a window of +-``max_shift`` reduced pixels) with the sum of the OTHER frames shifted by
+  the current estimate (``torch.ops.sprk.align_accumulate`` with the matrices of ``shift_matrix``); the peak of every
+  window, refined by a three-point parabola per axis, is the new estimate; the mean over the frames is taken out;
+* the raw frames are shifted by the estimate, summed and (``ftbin``) Fourier-cropped in one pass, ``align_accumulate`` per
+  frame: Y = sum_f My_f D_f Mx_f^T with one fp32 accumulator chain per pixel that runs on through the frames.
+
+A sub-pixel shift with periodic edges is the same kind of operator as the Fourier crop: the real matrix
+``shift_matrix64`` = (S/B) IDFT_S . crop . diag(e^{-2 pi i k delta / B}) . DFT_B per axis.  What leaves a frame at one edge
+wraps round to the other, as in every Fourier shift; nothing is tapered.
+
+Out of scope: gain and dark references, dose weighting, patch-wise (local) motion, TIFF and EER input.
+
+Coordinates and signs: x runs along nx (columns), y along ny (rows).  ``{name}_shifts.txt`` lists, per frame, the
+displacement (dx, dy) of the frame's content in raw pixels against the movie's mean position (mean zero over the frames);
+the sum applies its negative."""
+import io
+import logging
+import os
+
+import numpy as np
+import torch
+
+from . import ingest, micrograph_io, torch_ops
+
+logger = logging.getLogger("joint.align")
+MAX_SHIFT = torch_ops.ALIGN_MAX_SHIFT
+DEFAULT_ALIGN_SIZE, DEFAULT_MAX_SHIFT, DEFAULT_ITERS = 1024, 16, 6
+TOLERANCE = 0.01                                 # reduced pixels: the loop stops when no component moves by this much
+RESIDENT_BYTES = 8 << 30                         # frames of a movie below this size stay on the device for the second pass
+
+
+# ---- arguments and geometry ----------------------------------------------------------------------------------------------
+def check_align_args(align_size, max_shift, iters):
+    for name, v, lo, hi in (("align_size", align_size, 64, ingest.MAX_SIDE), ("max_shift", max_shift, 1, MAX_SHIFT),
+                            ("iters", iters, 1, 100)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d..%d, got %r" % (name, lo, hi, v))
+    return int(align_size), int(max_shift), int(iters)
+
+
+def align_geometry(ny, nx, align_size=DEFAULT_ALIGN_SIZE):
+    """-> (Sy, Sx): the size of the reduced frames the shifts are estimated on.  Sx is the multiple of 64 nearest
+    nx * A / max(ny, nx) (halves go up), at least 64 and at most nx; Sy = round(ny * Sx / nx), at most ny.  A shift of one
+    reduced pixel is ny / Sy raw pixels along y and nx / Sx along x."""
+    ny, nx, A = int(ny), int(nx), int(align_size)
+    if not (64 <= nx <= ingest.MAX_SIDE and 2 <= ny <= ingest.MAX_SIDE):
+        raise ValueError("a %dx%d frame: 64 <= nx <= %d and 2 <= ny <= %d" % (ny, nx, ingest.MAX_SIDE, ingest.MAX_SIDE))
+    if A < 64:
+        raise ValueError("align_size must be at least 64, got %d" % A)
+    m = max(ny, nx)
+    Sx = 64 * ((2 * nx * A + 64 * m) // (128 * m))            # floor(nx A / (64 m) + 1/2) in integers
+    Sx = min(max(Sx, 64), nx // 64 * 64)
+    Sy = min(max((2 * ny * Sx + nx) // (2 * nx), 2), ny)
+    return Sy, Sx
+
+
+# ---- the shift-and-crop operator --------------------------------------------------------------------------------------------
+def _wrap_delta(B, delta):
+    delta = float(delta)
+    if not np.isfinite(delta):
+        raise ValueError("shift must be finite, got %r" % (delta,))
+    return delta - B * np.round(delta / B)                       # the operator has period B in delta
+
+
+def shift_matrix64(B, S, delta):
+    """Shift B periodic samples by ``delta`` samples (out(t) = in(t - delta)) and Fourier-crop them to S, as a real [S, B]
+    matrix in float64: (S/B) IDFT_S . crop . diag(e^{-2 pi i k delta / B}) . DFT_B with its sum over k in closed form, a
+    Dirichlet kernel at u = s B / S - b - delta.  With x = pi u / B:
+        M[s, b] = (1/B) sin(S x) / sin(x)                for odd S,
+        the same times cos(x)                            for even S (the +-S/2 term is shared at half weight each),
+        S / B where sin(x) == 0.
+    The integer part t = s B - b S of S u is reduced exactly (to (-S B / 2, S B / 2], and to (-B, B] for the numerator, whose
+    argument is folded about +-pi/2) before ``delta`` enters, so that the sines keep their relative accuracy.  Every row
+    sums to 1; ``delta`` = 0 is ``ingest.resample_matrix64`` (within 1e-12), the identity for S == B."""
+    B, S = int(B), int(S)
+    if not 2 <= S <= B:
+        raise ValueError("shift_matrix: 2 <= S <= B, got B = %d, S = %d" % (B, S))
+    delta = _wrap_delta(B, delta)
+    period = S * B
+    t = (np.arange(S, dtype=np.int64)[:, None] * B - np.arange(B, dtype=np.int64)[None, :] * S) % period
+    t = np.where(2 * t > period, t - period, t)
+    tn = t % (2 * B)
+    tn = np.where(tn > B, tn - 2 * B, tn)
+    w = (tn - S * delta) / B                                     # the numerator is sin(pi w)
+    w = w - 2.0 * np.round(w / 2.0)
+    w = np.where(w > 0.5, 1.0 - w, np.where(w < -0.5, -1.0 - w, w))
+    half = (np.pi / period) * (t - S * delta)
+    den = np.sin(half)
+    zero = den == 0
+    m = np.sin(np.pi * w) / np.where(zero, 1.0, den) / B
+    if S % 2 == 0:
+        m = m * np.cos(half)
+    return np.where(zero, S / B, m)
+
+
+def shift_matrix_device64(B, S, delta, device):
+    """``shift_matrix64`` built on ``device`` with torch, operation for operation: float64 [S, B].  (On the host, 40 frames
+    times two 4096^2 matrices of sines are tens of seconds.)  It differs from the NumPy one by what the two sines differ."""
+    B, S = int(B), int(S)
+    if not 2 <= S <= B:
+        raise ValueError("shift_matrix: 2 <= S <= B, got B = %d, S = %d" % (B, S))
+    delta = _wrap_delta(B, delta)
+    period = S * B
+    i64 = dict(dtype=torch.int64, device=device)
+    t = (torch.arange(S, **i64)[:, None] * B - torch.arange(B, **i64)[None, :] * S) % period
+    t = torch.where(2 * t > period, t - period, t)
+    tn = t % (2 * B)
+    tn = torch.where(tn > B, tn - 2 * B, tn)
+    w = (tn.double() - S * delta) / B
+    w = w - 2.0 * torch.round(w / 2.0)
+    w = torch.where(w > 0.5, 1.0 - w, torch.where(w < -0.5, -1.0 - w, w))
+    half = (np.pi / period) * (t.double() - S * delta)
+    den = torch.sin(half)
+    zero = den == 0
+    m = torch.sin(np.pi * w) / torch.where(zero, torch.ones_like(den), den) / B
+    if S % 2 == 0:
+        m = m * torch.cos(half)
+    return torch.where(zero, torch.full_like(m, S / B), m)
+
+
+def shift_matrix(B, S, delta, device=None):
+    """``shift_matrix64`` rounded to float32.  Without a device: the [S, B] array.  With one: an operand of
+    ``torch.ops.sprk.align_accumulate``, built there (``shift_matrix_device64``) and padded as
+    ``ingest.resample_matrix(B, S, device)`` pads: [roundup(S, 16), roundup(B, 4)] with exact zeros added."""
+    if device is None:
+        return shift_matrix64(B, S, delta).astype(np.float32)
+    B, S = int(B), int(S)
+    padded = torch.zeros((-(-S // 16) * 16, -(-B // 4) * 4), dtype=torch.float32, device=device)
+    padded[:S, :B] = shift_matrix_device64(B, S, delta, device).float()
+    return padded
+
+
+# ---- the estimate ----------------------------------------------------------------------------------------------------------
+def fit_peaks(cc):
+    """cc [Z, 2R+1, 2R+1] correlation windows -> (py, px, edge): the position of each window's maximum in pixels from its
+    centre, float64 [Z], refined per axis by the parabola through the maximum and its two neighbours; ``edge`` [Z] bool:
+    the maximum sits on the window's border (its index is clamped to the interior before the fit)."""
+    cc = np.asarray(cc, dtype=np.float64)
+    Z, n, n2 = cc.shape
+    if n != n2 or n < 3 or n % 2 == 0:
+        raise ValueError("fit_peaks: windows of %dx%d (odd and square, at least 3)" % (n, n2))
+    R = (n - 1) // 2
+    iy, ix = np.unravel_index(cc.reshape(Z, -1).argmax(axis=1), (n, n))
+    edge = (iy == 0) | (iy == n - 1) | (ix == 0) | (ix == n - 1)
+    iy, ix = np.clip(iy, 1, n - 2), np.clip(ix, 1, n - 2)
+    f = np.arange(Z)
+
+    def vertex(lo, c, hi):
+        curv = lo - 2.0 * c + hi
+        with np.errstate(divide="ignore", invalid="ignore"):
+            off = np.where(curv < 0, 0.5 * (lo - hi) / curv, 0.0)
+        return np.clip(off, -0.5, 0.5)
+
+    c = cc[f, iy, ix]
+    py = iy - R + vertex(cc[f, iy - 1, ix], c, cc[f, iy + 1, ix])
+    px = ix - R + vertex(cc[f, iy, ix - 1], c, cc[f, iy, ix + 1])
+    return py, px, edge
+
+
+def _flat_bytes(t):
+    return t.view(torch.uint8).reshape(-1)
+
+
+def estimate_shifts(reduced, max_shift=DEFAULT_MAX_SHIFT, iters=DEFAULT_ITERS, name=""):
+    """reduced: float32 CUDA [Z, Sy, Sx], every frame's mean taken out -> (sy, sx, info): the shift of every frame, in
+    reduced pixels, that lays it on the others (mean zero over the frames; float64 [Z]), and {"iterations", "edge_frames",
+    "moved"}.  Each iteration correlates the frames as they are with the sum of the other frames shifted by the current
+    estimate; a frame is left out of its own reference (its noise correlates with itself at shift zero and pulls the
+    estimate there)."""
+    Z, Sy, Sx = reduced.shape
+    R = int(max_shift)
+    dev = reduced.device
+    sy, sx = np.zeros(Z), np.zeros(Z)
+    shifted = torch.empty_like(reduced)
+    info = {"iterations": 0, "edge_frames": [], "moved": None}
+    for it in range(int(iters)):
+        for f in range(Z):
+            torch.ops.sprk.align_accumulate(_flat_bytes(reduced[f]), 2, Sy, Sx, Sy, Sx, shift_matrix(Sy, Sy, sy[f], dev),
+                                            shift_matrix(Sx, Sx, sx[f], dev), 0.0, shifted[f], True)
+        refs = shifted.sum(dim=0, keepdim=True) - shifted
+        cc = torch.ops.sprk.align_corr(reduced, refs, R, 0).cpu().numpy()
+        py, px, edge = fit_peaks(cc)
+        py, px = py - py.mean(), px - px.mean()
+        moved = float(max(np.abs(py - sy).max(), np.abs(px - sx).max()))
+        sy, sx = py, px
+        info = {"iterations": it + 1, "edge_frames": [int(f) for f in np.nonzero(edge)[0]], "moved": moved}
+        if edge.any():
+            logger.warning("%s: iteration %d: the correlation peak of frame(s) %s sits on the edge of the +-%d pixel window; "
+                           "the clamped position is used (a larger --max_shift or a smaller --align_size reaches further)",
+                           name, it + 1, ", ".join(str(f) for f in info["edge_frames"]), R)
+        if moved < TOLERANCE:
+            break
+    return sy, sx, info
+
+
+# ---- movies ----------------------------------------------------------------------------------------------------------------
+def read_movie_header(path, f):
+    """The 1024-byte MRC header of an open movie -> (MRCHeader, byte offset of frame 0).  ``ingest.read_header``'s refusals,
+    with the one about stacks turned round: a single image is refused."""
+    head = f.read(ingest._HEADER_BYTES)
+    if len(head) < ingest._HEADER_BYTES:
+        raise ValueError("MRC file shorter than its 1024-byte header")
+    header = micrograph_io.MRCHeader._make(micrograph_io._HEADER.unpack(head))
+    if header.mode not in micrograph_io._MODES:
+        raise ValueError("Unsupported MRC mode: %d" % header.mode)
+    if header.nz < 2:
+        raise ValueError("%s: expected a movie, a stack of at least 2 frames, got shape %s"
+                         % (path, (header.nz, header.ny, header.nx)))
+    if header.ny < 1 or header.nx < 1 or header.next < 0:
+        raise ValueError("%s: bad MRC header (nx %d, ny %d, next %d)" % (path, header.nx, header.ny, header.next))
+    if header.ny > ingest.MAX_SIDE or header.nx > ingest.MAX_SIDE:
+        raise ValueError("%s: frames of %dx%d are larger than joint align takes (%d a side)"
+                         % (path, header.ny, header.nx, ingest.MAX_SIDE))
+    return header, ingest._HEADER_BYTES + header.next
+
+
+class MovieReader(ingest.RawReader):
+    """``ingest.RawReader`` for the frames of a stack: frame k of an open file through the two pinned slots, so that the
+    read of frame k+1 overlaps the upload and the GEMMs of frame k."""
+
+    def read_frame(self, f, path, start, nbytes, k):
+        """-> (uint8 CUDA tensor with frame k's ny*nx samples, the first ``nbytes`` of the pinned slot as a NumPy view,
+        valid until the slot is used again: two reads later)"""
+        slot = self._slot(nbytes)
+        f.seek(start + k * nbytes)
+        host = self._bufs[slot].numpy()[:nbytes]
+        got = f.readinto(memoryview(host))
+        if got != nbytes:
+            raise ValueError("%s: frame %d has %d bytes of samples, the header promises %d" % (path, k, got, nbytes))
+        raw = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        raw.copy_(self._bufs[slot][:nbytes], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._events[slot] = ev
+        return raw, host
+
+
+class Movie:
+    """An open movie: ``frame(k)`` -> the uint8 CUDA tensor of frame k's samples.  The frames stay on the device after
+    their first read when the whole movie is at most ``resident_bytes``; they are read again from the file otherwise.
+    ``anchor``: the first sample of frame 0 (0.0 for float32), known on the host without a device read."""
+
+    def __init__(self, path, device="cuda", resident_bytes=RESIDENT_BYTES):
+        ingest.require_mrc(path)
+        self.path = path
+        self._reader = MovieReader(device)
+        self._f = open(path, "rb")
+        try:
+            self.header, self._start = read_movie_header(path, self._f)
+        except Exception:
+            self._f.close()
+            raise
+        h = self.header
+        self.dtype = np.dtype(micrograph_io._MODES[h.mode])
+        self.frame_bytes = h.ny * h.nx * self.dtype.itemsize
+        self.resident = h.nz * self.frame_bytes <= resident_bytes
+        self._frames = [None] * h.nz
+        self.anchor = None
+
+    def frame(self, k):
+        if self._frames[k] is not None:
+            return self._frames[k]
+        raw, host = self._reader.read_frame(self._f, self.path, self._start, self.frame_bytes, k)
+        if k == 0 and self.anchor is None:
+            self.anchor = 0.0 if self.header.mode == 2 else float(host[:self.dtype.itemsize].view(self.dtype)[0])
+        if self.resident:
+            self._frames[k] = raw
+        return raw
+
+    def close(self):
+        self._frames = []
+        self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def sum_frames(movie, by, bx, shifts_y, shifts_x):
+    """-> float32 CUDA [by, bx]: sum over the frames of (frame f shifted by (shifts_y[f], shifts_x[f]) raw pixels and
+    Fourier-cropped to by x bx), ``align_accumulate`` per frame and the anchor term at the end (one fp32 add: the rows of
+    every matrix sum to 1)."""
+    h = movie.header
+    dev = movie._reader.device
+    y = torch.empty((by, bx), dtype=torch.float32, device=dev)
+    for k in range(h.nz):
+        raw = movie.frame(k)
+        torch.ops.sprk.align_accumulate(raw, h.mode, h.ny, h.nx, by, bx, shift_matrix(h.ny, by, shifts_y[k], dev),
+                                        shift_matrix(h.nx, bx, shifts_x[k], dev), movie.anchor, y, k == 0)
+    if h.mode != 2:
+        y += float(np.float32(h.nz * movie.anchor))
+    return y
+
+
+def align_movie(path, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_shift=DEFAULT_MAX_SHIFT, iters=DEFAULT_ITERS,
+                no_align=False, device="cuda", resident_bytes=RESIDENT_BYTES):
+    """One movie -> (sum float32 CUDA [by, bx], drift float64 [Z, 2] (dx, dy) in raw pixels, header, info)."""
+    align_size, max_shift, iters = check_align_args(align_size, max_shift, iters)
+    with Movie(path, device, resident_bytes) as movie:
+        h = movie.header
+        ny, nx, Z = h.ny, h.nx, h.nz
+        by, bx = ingest.resample_geometry(ny, nx, ftbin)
+        sy, sx = np.zeros(Z), np.zeros(Z)
+        info = {"iterations": 0, "edge_frames": [], "moved": None}
+        if not no_align:
+            Sy, Sx = align_geometry(ny, nx, align_size)
+            if 2 * max_shift + 1 > min(Sy, Sx):
+                raise ValueError("%s: a window of +-%d pixels does not fit the %dx%d reduced frames" % (path, max_shift, Sy, Sx))
+            dev = movie._reader.device
+            my, mx = ingest.resample_matrix(ny, Sy, dev), ingest.resample_matrix(nx, Sx, dev)
+            reduced = torch.empty((Z, Sy, Sx), dtype=torch.float32, device=dev)
+            for k in range(Z):
+                red, _ = torch.ops.sprk.ingest_resample(movie.frame(k), h.mode, ny, nx, Sy, Sx, my, mx)
+                reduced[k] = red - red.mean()
+            ry, rx, info = estimate_shifts(reduced, max_shift, iters, os.path.basename(path))
+            sy, sx = ry * (ny / Sy), rx * (nx / Sx)
+            info = dict(info, reduced=(Sy, Sx))
+        total = sum_frames(movie, by, bx, sy, sx)
+    return total, np.stack([0.0 - sx, 0.0 - sy], axis=1), h, info             # 0.0 - x: no "-0.0000" in the table
+
+
+def write_sum(path, image, header, by, bx):
+    """The aligned sum as a float32 MRC: ``micrograph_io.write_mrc``'s file with the movie's pixel size times ny / by (the
+    cell of the movie's frames on the new sampling), when the movie's header states one."""
+    buf = io.BytesIO()
+    micrograph_io.write_mrc(buf, image)
+    out = bytearray(buf.getvalue())
+    from .ctf import header_apix
+    if header_apix(header) is not None:
+        fields = list(micrograph_io.MRCHeader._make(micrograph_io._HEADER.unpack(bytes(out[:1024]))))
+        names = micrograph_io.MRCHeader._fields
+        my_in = header.my if header.my > 0 else header.ny
+        cell = {"mx": bx, "my": by, "mz": 1, "xlen": header.xlen / header.mx * header.nx,
+                "ylen": (header.ylen / my_in if header.ylen > 0 else header.xlen / header.mx) * header.ny, "zlen": 1.0}
+        for key, v in cell.items():
+            fields[names.index(key)] = v
+        out[:1024] = micrograph_io._HEADER.pack(*fields)
+    with open(path, "wb") as f:
+        f.write(bytes(out))
+
+
+def align_dataset(movies, out_dir, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_shift=DEFAULT_MAX_SHIFT, iters=DEFAULT_ITERS,
+                  no_align=False, device="cuda", resident_bytes=RESIDENT_BYTES):
+    """``joint align``: for every movie of the table / directory ``movies``: ``out_dir/{name}.mrc`` (the aligned sum, float32
+    [by, bx] with (by, bx) = ``ingest.resample_geometry(ny, nx, ftbin)``) and ``out_dir/{name}_shifts.txt`` (frame, dx, dy in
+    raw pixels, mean zero), plus ``out_dir/images.txt`` (image_name, path) for the commands that follow.
+    -> {name: {"frames", "shape", "shifts": [[dx, dy], ...], "iterations", "edge_frames"}}."""
+    ftbin = ingest.check_ftbin(ftbin)
+    check_align_args(align_size, max_shift, iters)
+    rows = micrograph_io.read_image_table(movies)
+    if not rows:
+        raise ValueError("no movies found in %s" % movies)
+    for _, _, path in rows:
+        ingest.require_mrc(path)
+    os.makedirs(out_dir, exist_ok=True)
+    results, lines = {}, ["image_name\tpath"]
+    for _, name, path in rows:
+        total, drift, header, info = align_movie(path, ftbin, align_size, max_shift, iters, no_align, device, resident_bytes)
+        by, bx = total.shape
+        out = os.path.join(out_dir, name + ".mrc")
+        write_sum(out, total.cpu().numpy(), header, by, bx)
+        with open(os.path.join(out_dir, name + "_shifts.txt"), "w") as f:
+            f.write("frame\tdx\tdy\n" + "".join("%d\t%.4f\t%.4f\n" % (k, dx, dy) for k, (dx, dy) in enumerate(drift)))
+        lines.append("%s\t%s" % (name, out))
+        results[name] = {"frames": int(header.nz), "shape": [int(by), int(bx)], "shifts": [[float(dx), float(dy)] for dx, dy in drift],
+                         "iterations": info["iterations"], "edge_frames": info["edge_frames"]}
+        logger.info("%s: %d frames of %dx%d -> %dx%d, %d iteration(s), largest displacement %.2f raw pixels", name, header.nz,
+                    header.ny, header.nx, by, bx, info["iterations"], float(np.abs(drift).max()))
+    with open(os.path.join(out_dir, "images.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return results

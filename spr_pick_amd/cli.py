@@ -3,7 +3,8 @@ reference): ``joint train start|resume`` and ``joint eval`` with the same flags 
 flag -> configuration mapping, plus ``joint bin`` (the README's ``newstack -bin`` preparation, on the GPU), ``joint extract``
 (particle stacks from the pick tables and the raw micrographs, on the GPU) and ``joint ctf`` (tiled power spectra of the raw
 micrographs on the GPU, one fitted defocus each, or with ``--astigmatism`` two and an angle, ``micrographs_ctf.star`` for
-``joint extract --ctf``, which with ``--ctf_correct`` also phase-flips the stacks).  Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
+``joint extract --ctf``, which with ``--ctf_correct`` also phase-flips the stacks) and ``joint align`` (whole-frame motion
+correction of movies on the GPU, the sums the other commands start from).  Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
 under ``python -m torch.distributed.run --nproc-per-node N -m spr_pick_amd -- ...`` (keep the ``--``)."""
 import argparse
 
@@ -134,6 +135,11 @@ def _check_ctf(ns):
         check_astigmatism(MAX_ASTIGMATISM if ns.max_astigmatism is None else ns.max_astigmatism, ns.min_defocus)
 
 
+def _check_align(ns):
+    from .align import check_align_args
+    check_align_args(ns.align_size, ns.max_shift, ns.iters)
+
+
 def build_parser():
     parser = _Parser(prog="joint", description="Joint denoising + particle picking on MI355X "
                                      "(train / evaluate), drop-in for spr_pick's `joint` command.")
@@ -257,6 +263,29 @@ def build_parser():
                     help="largest (DefocusU - DefocusV) / 2 searched, Angstrom (default 1000; needs --astigmatism, and "
                          "A + 550 < --min_defocus)")
     cf.check = _check_ctf
+
+    al_help = ("Whole-frame motion correction of gain-corrected movies (MRC stacks) on the GPU: shifts estimated by iterated "
+               "cross-correlation, frames shifted, summed and (--ftbin) Fourier-cropped (replaces a MotionCor2 / "
+               "relion_motioncorr run before everything else).  Not covered: gain and dark references, dose weighting, "
+               "patch-wise (local) motion, TIFF and EER input.")
+    al = cmds.add_parser("align", help=al_help, description=al_help)
+    al.add_argument("--movies", "-d", required=True, metavar="T",
+                    help="Table (image_name, path) or directory of MRC movie stacks (modes 0 / 1 / 2 / 6, at least 2 frames, "
+                         "at most 16384 pixels a side, gain-corrected).")
+    al.add_argument("--out", "-o", required=True,
+                    help="Directory for {name}.mrc (the aligned sum, float32), {name}_shifts.txt (frame, dx, dy in raw pixels, "
+                         "mean zero) and images.txt.")
+    al.add_argument("--ftbin", type=_ftbin, default=1, metavar="F",
+                    help="Fourier-crop the sum by the factor F (any decimal or p/q in 1..64) in the same pass; default 1")
+    al.add_argument("--align_size", type=int, default=1024, metavar="A",
+                    help="the shifts are estimated on frames Fourier-cropped to about A pixels on their longer side "
+                         "(64..16384, default 1024)")
+    al.add_argument("--max_shift", type=int, default=16, metavar="R",
+                    help="half width of the correlation window in pixels of the reduced frames (1..31, default 16)")
+    al.add_argument("--iters", type=int, default=6, metavar="I",
+                    help="iterations of the estimate at most (default 6; it stops when no shift moves by 0.01 reduced pixel)")
+    al.add_argument("--no_align", action="store_true", help="sum (and crop) the frames as they are: all shifts zero")
+    al.check = _check_align
     return parser
 
 
@@ -349,6 +378,15 @@ def run_ctf(args):
     return res
 
 
+def run_align(args):
+    import json
+    from . import align
+    res = align.align_dataset(args["movies"], args["out"], ftbin=args["ftbin"], align_size=args["align_size"],
+                              max_shift=args["max_shift"], iters=args["iters"], no_align=args["no_align"])
+    print(json.dumps({"movies": res}))
+    return res
+
+
 def start(argv=None):
     import sys
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -364,4 +402,6 @@ def start(argv=None):
         return run_extract(args)
     if args["command"] == "ctf":
         return run_ctf(args)
+    if args["command"] == "align":
+        return run_align(args)
     return run_eval(args)

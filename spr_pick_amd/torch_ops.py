@@ -736,6 +736,76 @@ _register("ingest_resample", "(Tensor raw, int mode, int ny, int nx, int by, int
           _ingest_resample, _ingest_resample_fake)
 
 
+# ---- whole-frame motion correction of movies (align.py: csrc/align.hip) --------------------------------------------------------
+ALIGN_MAX_SHIFT = 31                             # sprk_align_corr: the largest window radius R
+ALIGN_TILES = (0, 16, 32, 64)                    # ... and its tilings (0: the library's choice); the bytes are the same
+
+
+def _align_corr_check(a, r, R, tile):
+    if a.dtype != torch.float32 or a.dim() != 3 or r.dtype != torch.float32 or r.device != a.device:
+        raise _lib.SprkError("align_corr: a must be float32 [Z, Sy, Sx] and r float32 on the same device, got %s %s and %s %s"
+                             % (a.dtype, tuple(a.shape), r.dtype, tuple(r.shape)))
+    Z, Sy, Sx = a.shape
+    if tuple(r.shape) not in ((Z, Sy, Sx), (Sy, Sx)):
+        raise _lib.SprkError("align_corr: r must be [%d, %d, %d] (one reference per frame) or [%d, %d] (one shared), got %s"
+                             % (Z, Sy, Sx, Sy, Sx, tuple(r.shape)))
+    if not (1 <= R <= ALIGN_MAX_SHIFT and Z >= 1 and Sx >= 64 and Sx % 64 == 0 and 1 <= Sy and max(Sy, Sx) <= INGEST_MAX_SIDE):
+        raise _lib.SprkError("align_corr: %d frames of %dx%d with R %d (1 <= R <= %d, Sx a multiple of 64, both sides at most %d)"
+                             % (Z, Sy, Sx, R, ALIGN_MAX_SHIFT, INGEST_MAX_SIDE))
+    if tile not in ALIGN_TILES:
+        raise _lib.SprkError("align_corr: tile %r (one of %s)" % (tile, ALIGN_TILES))
+    return Z, Sy, Sx
+
+
+def _align_corr(a, r, R, tile=0):
+    """a: reduced frames float32 [Z, Sy, Sx]; r: their references [Z, Sy, Sx], or one shared [Sy, Sx] -> the correlation
+    windows float32 [Z, 2R+1, 2R+1] (sprk_align_corr)."""
+    Z, Sy, Sx = _align_corr_check(a, r, R, tile)
+    if not a.is_contiguous() or not r.is_contiguous():
+        raise _lib.SprkError("align_corr: a and r must be contiguous")
+    cc = _f32(a, (Z, 2 * R + 1, 2 * R + 1))
+    check(_lib.lib().sprk_align_corr(_p(a), _p(r), Sy * Sx if r.dim() == 3 else 0, Z, Sy, Sx, int(R), int(tile), _p(cc),
+                                     _stream(a)), "sprk_align_corr")
+    return cc
+
+
+def _align_corr_fake(a, r, R, tile=0):
+    Z, _, _ = _align_corr_check(a, r, R, tile)
+    return a.new_empty((Z, 2 * R + 1, 2 * R + 1))
+
+
+_register("align_corr", "(Tensor a, Tensor r, int R, int tile=0) -> Tensor", _align_corr, _align_corr_fake)
+
+
+def _align_accumulate_check(raw, mode, ny, nx, by, bx, my, mx, y):
+    _resample_check(raw, mode, ny, nx, by, bx, my, mx)
+    if y.dtype != torch.float32 or tuple(y.shape) != (by, bx) or y.device != raw.device:
+        raise _lib.SprkError("align_accumulate: y must be float32 [%d, %d] on %s, got %s %s on %s"
+                             % (by, bx, raw.device, y.dtype, tuple(y.shape), y.device))
+
+
+def _align_accumulate(raw, mode, ny, nx, by, bx, my, mx, anchor, y, first):
+    """raw, mode, sizes and matrices as ``ingest_resample``'s; anchor: what the integer modes subtract from every sample (a
+    sample value; 0 for float32); y float32 [by, bx]: the running sum, updated in place (overwritten when ``first``)
+    (sprk_align_accumulate)."""
+    _align_accumulate_check(raw, mode, ny, nx, by, bx, my, mx, y)
+    if not raw.is_contiguous() or not my.is_contiguous() or not mx.is_contiguous() or not y.is_contiguous():
+        raise _lib.SprkError("align_accumulate: raw, my, mx and y must be contiguous")
+    L = _lib.lib()
+    ws = _ws(L.sprk_align_accumulate_ws_bytes(int(ny), int(nx), int(by), int(bx)), raw)
+    check(L.sprk_align_accumulate(_p(raw), int(mode), int(ny), int(nx), int(by), int(bx), _p(my), int(my.shape[1]), _p(mx),
+                                  int(mx.shape[1]), float(anchor), _p(y), 1 if first else 0, _p(ws), ws.numel(),
+                                  _stream(raw)), "sprk_align_accumulate")
+
+
+def _align_accumulate_fake(raw, mode, ny, nx, by, bx, my, mx, anchor, y, first):
+    _align_accumulate_check(raw, mode, ny, nx, by, bx, my, mx, y)
+
+
+_register("align_accumulate", "(Tensor raw, int mode, int ny, int nx, int by, int bx, Tensor my, Tensor mx, float anchor, "
+          "Tensor(a!) y, bool first) -> ()", _align_accumulate, _align_accumulate_fake)
+
+
 # ---- particle extraction (extract.py: raw MRC samples + pick coordinates -> normalised particle stack) ------------------------
 EXTRACT_MAX_BOX = 1024                           # sprk_extract_boxes: the int64 sum of squares stays below 2^63 up to here
 EXTRACT_NORMALIZE, EXTRACT_INVERT = 1, 2         # SPRK_EXTRACT_*
