@@ -683,6 +683,40 @@ int sprk_align_accumulate(const void *raw, int mode, int ny, int nx, int by, int
                           const float *mx, int ldmx, float anchor, float *y, int first, void *ws, size_t ws_bytes,
                           void *stream);
 
+/* Dose-weighted sums (`joint align --dose`): Y = IDFT2[by,bx]( sum over the frames f of G_f . crop(DFT2[ny,nx](D_f)) ), the
+ * movie accumulated in Fourier space.  The four real fp32 GEMMs of sprk_extract_filter (its matrix layouts) over a whole
+ * rectangular frame, on v_mfma_f32_16x16x4_f32; every sum an fmaf chain over its K ascending from 0.0f, one accumulator per
+ * element and stage, K never split (so every tiling gives the same bits).  Ku kept rows and Hs kept columns of the
+ * spectrum; which frequencies they are, every weight and every phase is the caller's (spr_pick_amd.dose): the kernels know
+ * no trigonometry.  ldv = roundup(Hs, 4).  All matrices fp32 on the device, 16-byte aligned, dense rows whose length is
+ * the column count rounded up to a multiple of 4, the padding columns exact zeros.
+ *
+ * sprk_align_spectrum: one frame into the running spectrum F (stages 1 and 2).  2 <= ny, nx <= 16384, 1 <= Hs <= nx/2 + 1,
+ * 1 <= Ku <= ny + 1; raw, mode, D and anchor as sprk_align_accumulate's.  w1 [2Hs, roundup(nx, 4)], w2 [2Ku, roundup(2ny, 4)].
+ *   U[r, q]  = chain over c = 0 .. nx-1 of D[r, c] * w1[q, c];   V = [U[:, :Hs] ; U[:, Hs:]]  [2ny, ldv], the workspace;
+ *   A[kk, v] = chain over t = 0 .. 2ny-1 of w2[kk, t] * V[t, v];   B[kk, v] the same with row Ku + kk;
+ *   Fr[kk, v] = fmaf(A, Gr, fmaf(-B, Gi, Fr_old)),   Fi[kk, v] = fmaf(A, Gi, fmaf(B, Gr, Fi_old)),
+ *   F_old = 0.0f when `first`, and F is then not read.
+ * F and g: fp32 [2Ku, ldv], 16-byte aligned, the real rows first, then the imaginary rows; columns Hs .. ldv-1 are never
+ * read into a stored value and never written.  Every padded K position is a zero formed in registers on both operands: the
+ * workspace and, when `first`, F may hold anything, NaNs included.
+ *
+ * sprk_align_synthesize: the spectrum back to pixels, once per movie (stages 3 and 4).  2 <= by, bx <= 16384,
+ * 1 <= Hs <= bx/2 + 1, 1 <= Ku <= by + 1.  w3 [2by, roundup(2Ku, 4)], w4 [bx, roundup(2Hs, 4)].
+ *   Zr[i, v] = chain over t = 0 .. 2Ku-1 of w3[i, t] * F[t, v];   Zi the same with row by + i;
+ *   Z = [Zr, Zi]  [by, roundup(2Hs, 4)], the workspace;
+ *   y[i, j]  = chain over t = 0 .. 2Hs-1 of Z[i, t] * w4[j, t],   y [by, bx] fp32, 16-byte aligned.
+ *
+ * Refused (SPRK_EINVAL, nothing launched): another mode, other sizes, an anchor that is no sample value of the mode, null
+ * or misaligned pointers (ws 16-byte aligned as well); a short workspace: SPRK_EWORKSPACE.  The *_ws_bytes functions return
+ * 0 for sizes that are refused.  Two launches each on `stream`, no host synchronisation, no atomics. */
+size_t sprk_align_spectrum_ws_bytes(int ny, int nx, int Hs);
+int sprk_align_spectrum(const void *raw, int mode, int ny, int nx, int Ku, int Hs, const float *w1, const float *w2,
+                        const float *g, float anchor, float *F, int first, void *ws, size_t ws_bytes, void *stream);
+size_t sprk_align_synthesize_ws_bytes(int by, int Hs);
+int sprk_align_synthesize(const float *F, int Ku, int Hs, int by, int bx, const float *w3, const float *w4, float *y, void *ws,
+                          size_t ws_bytes, void *stream);
+
 /* ---- tiled power spectra (`joint ctf`)-----------------------------------------------------
  * sprk_psd_tiles: the summed half-plane power spectrum of T x T tiles of ONE raw micrograph (raw as for sprk_ingest_bin:
  * [ny,nx] samples of mode 0 / 1 / 2 / 6, 16-byte aligned start; rows may be only itemsize-aligned).  T a multiple of 16 in

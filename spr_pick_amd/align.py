@@ -16,7 +16,10 @@ A sub-pixel shift with periodic edges is the same kind of operator as the Fourie
 ``shift_matrix64`` = (S/B) IDFT_S . crop . diag(e^{-2 pi i k delta / B}) . DFT_B per axis.  What leaves a frame at one edge
 wraps round to the other, as in every Fourier shift; nothing is tapered.
 
-Out of scope: gain and dark references, dose weighting, patch-wise (local) motion, TIFF and EER input.
+With a dose per frame (``dose``; ``joint align --dose``) a second, dose-weighted sum is formed beside the plain one, in
+Fourier space (``dose.sum_frames_weighted``); the plain sum and the shifts are what they are without it.
+
+Out of scope: gain and dark references, patch-wise (local) motion, TIFF and EER input.
 
 Coordinates and signs: x runs along nx (columns), y along ny (rows).  ``{name}_shifts.txt`` lists, per frame, the
 displacement (dx, dy) of the frame's content in raw pixels against the movie's mean position (mean zero over the frames);
@@ -302,12 +305,31 @@ def sum_frames(movie, by, bx, shifts_y, shifts_x):
     return y
 
 
+def _dose_args(dose, pre_dose, kv, apix):
+    """None without a dose (the other three must then be at their defaults), else the checked (dose, pre_dose, kv, apix)"""
+    if dose is None:
+        if pre_dose != 0.0 or kv != 300.0 or apix is not None:
+            raise ValueError("pre_dose, kv and apix belong to the dose weighting: give dose as well")
+        return None
+    from . import dose as dose_mod
+    return dose_mod.check_dose_args(dose, pre_dose, kv, apix)
+
+
 def align_movie(path, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_shift=DEFAULT_MAX_SHIFT, iters=DEFAULT_ITERS,
-                no_align=False, device="cuda", resident_bytes=RESIDENT_BYTES):
-    """One movie -> (sum float32 CUDA [by, bx], drift float64 [Z, 2] (dx, dy) in raw pixels, header, info)."""
+                no_align=False, device="cuda", resident_bytes=RESIDENT_BYTES, dose=None, pre_dose=0.0, kv=300.0, apix=None):
+    """One movie -> (sum float32 CUDA [by, bx], drift float64 [Z, 2] (dx, dy) in raw pixels, header, info).  With ``dose``
+    (e/A^2 per frame; ``pre_dose`` before frame 0, ``kv`` in 200..300, ``apix`` or else the header's pixel size):
+    info["dose_weighted"] is the dose-weighted sum of the same frames at the same shifts, float32 CUDA [by, bx]."""
     align_size, max_shift, iters = check_align_args(align_size, max_shift, iters)
+    weighting = _dose_args(dose, pre_dose, kv, apix)
     with Movie(path, device, resident_bytes) as movie:
         h = movie.header
+        if weighting is not None and weighting[3] is None:
+            from .ctf import header_apix
+            if header_apix(h) is None:
+                raise ValueError("%s: dose weighting needs the pixel size, and the movie's header states none: give --apix"
+                                 % path)
+            weighting = weighting[:3] + (header_apix(h),)
         ny, nx, Z = h.ny, h.nx, h.nz
         by, bx = ingest.resample_geometry(ny, nx, ftbin)
         sy, sx = np.zeros(Z), np.zeros(Z)
@@ -326,6 +348,11 @@ def align_movie(path, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_shift=DEFAULT_
             sy, sx = ry * (ny / Sy), rx * (nx / Sx)
             info = dict(info, reduced=(Sy, Sx))
         total = sum_frames(movie, by, bx, sy, sx)
+        if weighting is not None:
+            from . import dose as dose_mod
+            info = dict(info, dose_weighted=dose_mod.sum_frames_weighted(movie, by, bx, sy, sx, apix=weighting[3],
+                                                                         dose=weighting[0], pre_dose=weighting[1],
+                                                                         kv=weighting[2]))
     return total, np.stack([0.0 - sx, 0.0 - sy], axis=1), h, info             # 0.0 - x: no "-0.0000" in the table
 
 
@@ -350,22 +377,26 @@ def write_sum(path, image, header, by, bx):
 
 
 def align_dataset(movies, out_dir, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_shift=DEFAULT_MAX_SHIFT, iters=DEFAULT_ITERS,
-                  no_align=False, device="cuda", resident_bytes=RESIDENT_BYTES):
+                  no_align=False, device="cuda", resident_bytes=RESIDENT_BYTES, dose=None, pre_dose=0.0, kv=300.0, apix=None):
     """``joint align``: for every movie of the table / directory ``movies``: ``out_dir/{name}.mrc`` (the aligned sum, float32
     [by, bx] with (by, bx) = ``ingest.resample_geometry(ny, nx, ftbin)``) and ``out_dir/{name}_shifts.txt`` (frame, dx, dy in
     raw pixels, mean zero), plus ``out_dir/images.txt`` (image_name, path) for the commands that follow.
-    -> {name: {"frames", "shape", "shifts": [[dx, dy], ...], "iterations", "edge_frames"}}."""
+    With ``dose`` (``align_movie``) also ``out_dir/{name}_DW.mrc``, the dose-weighted sum, and ``out_dir/images_DW.txt``; the
+    other files are byte for byte what they are without it.
+    -> {name: {"frames", "shape", "shifts": [[dx, dy], ...], "iterations", "edge_frames"[, "dose_weighted": path]}}."""
     ftbin = ingest.check_ftbin(ftbin)
     check_align_args(align_size, max_shift, iters)
+    _dose_args(dose, pre_dose, kv, apix)
     rows = micrograph_io.read_image_table(movies)
     if not rows:
         raise ValueError("no movies found in %s" % movies)
     for _, _, path in rows:
         ingest.require_mrc(path)
     os.makedirs(out_dir, exist_ok=True)
-    results, lines = {}, ["image_name\tpath"]
+    results, lines, lines_dw = {}, ["image_name\tpath"], ["image_name\tpath"]
     for _, name, path in rows:
-        total, drift, header, info = align_movie(path, ftbin, align_size, max_shift, iters, no_align, device, resident_bytes)
+        total, drift, header, info = align_movie(path, ftbin, align_size, max_shift, iters, no_align, device, resident_bytes,
+                                                 dose, pre_dose, kv, apix)
         by, bx = total.shape
         out = os.path.join(out_dir, name + ".mrc")
         write_sum(out, total.cpu().numpy(), header, by, bx)
@@ -374,8 +405,16 @@ def align_dataset(movies, out_dir, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_s
         lines.append("%s\t%s" % (name, out))
         results[name] = {"frames": int(header.nz), "shape": [int(by), int(bx)], "shifts": [[float(dx), float(dy)] for dx, dy in drift],
                          "iterations": info["iterations"], "edge_frames": info["edge_frames"]}
+        if dose is not None:
+            out_dw = os.path.join(out_dir, name + "_DW.mrc")
+            write_sum(out_dw, info["dose_weighted"].cpu().numpy(), header, by, bx)
+            lines_dw.append("%s\t%s" % (name, out_dw))
+            results[name]["dose_weighted"] = out_dw
         logger.info("%s: %d frames of %dx%d -> %dx%d, %d iteration(s), largest displacement %.2f raw pixels", name, header.nz,
                     header.ny, header.nx, by, bx, info["iterations"], float(np.abs(drift).max()))
     with open(os.path.join(out_dir, "images.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
+    if dose is not None:
+        with open(os.path.join(out_dir, "images_DW.txt"), "w") as f:
+            f.write("\n".join(lines_dw) + "\n")
     return results

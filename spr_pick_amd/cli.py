@@ -4,7 +4,8 @@ flag -> configuration mapping, plus ``joint bin`` (the README's ``newstack -bin`
 (particle stacks from the pick tables and the raw micrographs, on the GPU) and ``joint ctf`` (tiled power spectra of the raw
 micrographs on the GPU, one fitted defocus each, or with ``--astigmatism`` two and an angle, ``micrographs_ctf.star`` for
 ``joint extract --ctf``, which with ``--ctf_correct`` also phase-flips the stacks) and ``joint align`` (whole-frame motion
-correction of movies on the GPU, the sums the other commands start from).  Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
+correction of movies on the GPU, the sums the other commands start from; with ``--dose`` a dose-weighted sum beside the plain one).
+Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
 under ``python -m torch.distributed.run --nproc-per-node N -m spr_pick_amd -- ...`` (keep the ``--``)."""
 import argparse
 
@@ -138,6 +139,13 @@ def _check_ctf(ns):
 def _check_align(ns):
     from .align import check_align_args
     check_align_args(ns.align_size, ns.max_shift, ns.iters)
+    if ns.dose is None:
+        for flag in ("pre_dose", "kv", "apix"):
+            if getattr(ns, flag) is not None:
+                raise ValueError("--%s belongs to the dose weighting: give --dose E as well" % flag)
+        return
+    from .dose import check_dose_args
+    check_dose_args(ns.dose, 0.0 if ns.pre_dose is None else ns.pre_dose, 300.0 if ns.kv is None else ns.kv, ns.apix)
 
 
 def build_parser():
@@ -266,8 +274,10 @@ def build_parser():
 
     al_help = ("Whole-frame motion correction of gain-corrected movies (MRC stacks) on the GPU: shifts estimated by iterated "
                "cross-correlation, frames shifted, summed and (--ftbin) Fourier-cropped (replaces a MotionCor2 / "
-               "relion_motioncorr run before everything else).  Not covered: gain and dark references, dose weighting, "
-               "patch-wise (local) motion, TIFF and EER input.")
+               "relion_motioncorr run before everything else).  With --dose also a dose-weighted sum per movie, "
+               "{name}_DW.mrc: give the plain sums (images.txt) to `joint ctf`, the weighted ones (images_DW.txt) to `joint "
+               "eval` / `joint extract`, and pass those tables, not the directory, which then holds both.  Not covered: gain "
+               "and dark references, patch-wise (local) motion, TIFF and EER input.")
     al = cmds.add_parser("align", help=al_help, description=al_help)
     al.add_argument("--movies", "-d", required=True, metavar="T",
                     help="Table (image_name, path) or directory of MRC movie stacks (modes 0 / 1 / 2 / 6, at least 2 frames, "
@@ -285,6 +295,17 @@ def build_parser():
     al.add_argument("--iters", type=int, default=6, metavar="I",
                     help="iterations of the estimate at most (default 6; it stops when no shift moves by 0.01 reduced pixel)")
     al.add_argument("--no_align", action="store_true", help="sum (and crop) the frames as they are: all shifts zero")
+    al.add_argument("--dose", type=float, metavar="E",
+                    help="dose weighting (Grant & Grigorieff 2015, as in unblur): the exposure per frame in e/A^2 (> 0); writes "
+                         "{name}_DW.mrc and images_DW.txt beside the plain sums, which stay what they are without it")
+    al.add_argument("--pre_dose", type=float, metavar="P", help="exposure before the first frame, e/A^2 (>= 0, default 0; "
+                                                                "needs --dose)")
+    al.add_argument("--kv", type=float, metavar="V",
+                    help="acceleration voltage in 200..300 kV (default 300; needs --dose).  The critical exposure is scaled by 1 at "
+                         "300 kV and 0.8 at 200 kV; in between the scale is interpolated linearly, which is this program's choice")
+    al.add_argument("--apix", type=float, metavar="A",
+                    help="pixel size of the frames in Angstrom (default: the movie header's; a movie whose header states none is "
+                         "refused; needs --dose)")
     al.check = _check_align
     return parser
 
@@ -382,7 +403,10 @@ def run_align(args):
     import json
     from . import align
     res = align.align_dataset(args["movies"], args["out"], ftbin=args["ftbin"], align_size=args["align_size"],
-                              max_shift=args["max_shift"], iters=args["iters"], no_align=args["no_align"])
+                              max_shift=args["max_shift"], iters=args["iters"], no_align=args["no_align"],
+                              **({} if args.get("dose") is None else
+                                 {"dose": args["dose"], "pre_dose": args["pre_dose"] or 0.0, "kv": args["kv"] or 300.0,
+                                  "apix": args.get("apix")}))
     print(json.dumps({"movies": res}))
     return res
 

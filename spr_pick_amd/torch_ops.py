@@ -806,6 +806,100 @@ _register("align_accumulate", "(Tensor raw, int mode, int ny, int nx, int by, in
           "Tensor(a!) y, bool first) -> ()", _align_accumulate, _align_accumulate_fake)
 
 
+# dose-weighted sums (dose.py: csrc/alignsum.hip): the movie accumulated in Fourier space
+def _up4(n):
+    return -(-int(n) // 4) * 4
+
+
+def align_spectrum_shapes(ny, nx, by, bx, Ku):
+    """-> the shapes of w1, w2, w3, w4 and of F / g for a [ny, nx] frame, a [by, bx] sum and Ku kept rows (Hs = bx // 2 + 1)"""
+    Hs = bx // 2 + 1
+    return ((2 * Hs, _up4(nx)), (2 * Ku, _up4(2 * ny)), (2 * by, _up4(2 * Ku)), (bx, _up4(2 * Hs)), (2 * Ku, _up4(Hs)))
+
+
+def _matrix_check(who, name, m, shape, like):
+    if m.dtype != torch.float32 or tuple(m.shape) != tuple(shape) or m.device != like.device:
+        raise _lib.SprkError("%s: %s must be float32 [%d, %d] on %s, got %s %s on %s"
+                             % (who, name, shape[0], shape[1], like.device, m.dtype, tuple(m.shape), m.device))
+
+
+def _align_spectrum_check(raw, mode, ny, nx, w1, w2, g, F):
+    if mode not in MRC_ITEMSIZE:
+        raise _lib.SprkError("align_spectrum: unsupported MRC mode %d" % mode)
+    if not (2 <= ny <= INGEST_MAX_SIDE and 2 <= nx <= INGEST_MAX_SIDE):
+        raise _lib.SprkError("align_spectrum: a %dx%d frame (2 <= ny, nx <= %d)" % (ny, nx, INGEST_MAX_SIDE))
+    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
+        raise _lib.SprkError("align_spectrum: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
+                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+    if w1.dim() != 2 or w2.dim() != 2 or w1.shape[0] % 2 or w2.shape[0] % 2:
+        raise _lib.SprkError("align_spectrum: w1 must be [2Hs, roundup(nx, 4)] and w2 [2Ku, roundup(2ny, 4)], got %s and %s"
+                             % (tuple(w1.shape), tuple(w2.shape)))
+    Hs, Ku = w1.shape[0] // 2, w2.shape[0] // 2
+    if not (1 <= Hs <= nx // 2 + 1 and 1 <= Ku <= ny + 1):
+        raise _lib.SprkError("align_spectrum: %d kept rows and %d kept columns of a %dx%d frame (1 <= Ku <= ny + 1, "
+                             "1 <= Hs <= nx / 2 + 1)" % (Ku, Hs, ny, nx))
+    for name, m, shape in (("w1", w1, (2 * Hs, _up4(nx))), ("w2", w2, (2 * Ku, _up4(2 * ny))), ("g", g, (2 * Ku, _up4(Hs))),
+                           ("F", F, (2 * Ku, _up4(Hs)))):
+        _matrix_check("align_spectrum", name, m, shape, raw)
+    return Ku, Hs
+
+
+def _align_spectrum(raw, mode, ny, nx, w1, w2, g, anchor, F, first):
+    """raw, mode and anchor as ``align_accumulate``'s; w1 [2Hs, roundup(nx, 4)], w2 [2Ku, roundup(2ny, 4)]; g, F float32
+    [2Ku, roundup(Hs, 4)], real rows over imaginary rows: F (+)= g . crop(DFT2(D)), in place (overwritten when ``first``)
+    (sprk_align_spectrum)."""
+    Ku, Hs = _align_spectrum_check(raw, mode, ny, nx, w1, w2, g, F)
+    if not all(t.is_contiguous() for t in (raw, w1, w2, g, F)):
+        raise _lib.SprkError("align_spectrum: raw, w1, w2, g and F must be contiguous")
+    L = _lib.lib()
+    ws = _ws(L.sprk_align_spectrum_ws_bytes(int(ny), int(nx), Hs), raw)
+    check(L.sprk_align_spectrum(_p(raw), int(mode), int(ny), int(nx), Ku, Hs, _p(w1), _p(w2), _p(g), float(anchor), _p(F),
+                                1 if first else 0, _p(ws), ws.numel(), _stream(raw)), "sprk_align_spectrum")
+
+
+def _align_spectrum_fake(raw, mode, ny, nx, w1, w2, g, anchor, F, first):
+    _align_spectrum_check(raw, mode, ny, nx, w1, w2, g, F)
+
+
+_register("align_spectrum", "(Tensor raw, int mode, int ny, int nx, Tensor w1, Tensor w2, Tensor g, float anchor, "
+          "Tensor(a!) F, bool first) -> ()", _align_spectrum, _align_spectrum_fake)
+
+
+def _align_synthesize_check(F, by, bx, w3, w4):
+    if not (2 <= by <= INGEST_MAX_SIDE and 2 <= bx <= INGEST_MAX_SIDE):
+        raise _lib.SprkError("align_synthesize: a %dx%d sum (2 <= by, bx <= %d)" % (by, bx, INGEST_MAX_SIDE))
+    if F.dtype != torch.float32 or F.dim() != 2 or F.shape[0] % 2 or not 1 <= F.shape[0] // 2 <= by + 1:
+        raise _lib.SprkError("align_synthesize: F must be float32 [2Ku, roundup(Hs, 4)] with 1 <= Ku <= by + 1 = %d, got %s %s"
+                             % (by + 1, F.dtype, tuple(F.shape)))
+    Ku, Hs = F.shape[0] // 2, bx // 2 + 1
+    for name, m, shape in (("F", F, (2 * Ku, _up4(Hs))), ("w3", w3, (2 * by, _up4(2 * Ku))), ("w4", w4, (bx, _up4(2 * Hs)))):
+        _matrix_check("align_synthesize", name, m, shape, F)
+    return Ku, Hs
+
+
+def _align_synthesize(F, by, bx, w3, w4):
+    """F float32 [2Ku, roundup(Hs, 4)] with Hs = bx // 2 + 1; w3 [2by, roundup(2Ku, 4)], w4 [bx, roundup(2Hs, 4)] -> the sum
+    float32 [by, bx] (sprk_align_synthesize)."""
+    Ku, Hs = _align_synthesize_check(F, by, bx, w3, w4)
+    if not all(t.is_contiguous() for t in (F, w3, w4)):
+        raise _lib.SprkError("align_synthesize: F, w3 and w4 must be contiguous")
+    L = _lib.lib()
+    y = _f32(F, (by, bx))
+    ws = _ws(L.sprk_align_synthesize_ws_bytes(int(by), Hs), F)
+    check(L.sprk_align_synthesize(_p(F), Ku, Hs, int(by), int(bx), _p(w3), _p(w4), _p(y), _p(ws), ws.numel(), _stream(F)),
+          "sprk_align_synthesize")
+    return y
+
+
+def _align_synthesize_fake(F, by, bx, w3, w4):
+    _align_synthesize_check(F, by, bx, w3, w4)
+    return F.new_empty((by, bx))
+
+
+_register("align_synthesize", "(Tensor F, int by, int bx, Tensor w3, Tensor w4) -> Tensor", _align_synthesize,
+          _align_synthesize_fake)
+
+
 # ---- particle extraction (extract.py: raw MRC samples + pick coordinates -> normalised particle stack) ------------------------
 EXTRACT_MAX_BOX = 1024                           # sprk_extract_boxes: the int64 sum of squares stays below 2^63 up to here
 EXTRACT_NORMALIZE, EXTRACT_INVERT = 1, 2         # SPRK_EXTRACT_*
