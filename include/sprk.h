@@ -717,6 +717,26 @@ size_t sprk_align_synthesize_ws_bytes(int by, int Hs);
 int sprk_align_synthesize(const float *F, int Ku, int Hs, int by, int bx, const float *w3, const float *w4, float *y, void *ws,
                           size_t ws_bytes, void *stream);
 
+/* ---- raw detector movies in (`joint align --gain / --dark / --defects / --hot_sigma`) -----------
+ * sprk_movie_correct: one frame of a movie (raw: [ny, nx] samples of mode 0 / 1 / 2 / 6) decoded, dark-subtracted,
+ * gain-multiplied and repaired where the fix map says so.  Per pixel p = (y, x), d the sample as fp32:
+ *   c(p) = d;  with dark: c = d - dark[p], one fp32 subtraction;  with gain: c = c * gain[p], one fp32 multiplication;
+ *   nothing is fused;
+ *   fix[p] == 0, or no fix map:  out[p] = c(p);
+ *   fix[p] == r > 0:  r = min(r, SPRK_FIX_MAX_RADIUS); the window is rows max(0, y-r) .. min(ny-1, y+r) and the same for the
+ *     columns, walked in row-major order over the pixels q with fix[q] == 0: S = S + c(q) in fp32 from 0.0f, n their count;
+ *     out[p] = S / (float)n, the correctly rounded fp32 quotient, or 0.0f when n == 0;
+ *   with sum:  sum[p] = out[p] when `first` (sum is then not read), else sum[p] + out[p]: one fp32 chain per pixel in call
+ *     order.
+ * The window recomputes c(q) from raw, gain and dark: the frame is finished in one launch, and the sample, gain and dark of
+ * a pixel with fix[p] > 0 reach no output, NaN and Inf included.  gain, dark [ny, nx] fp32, fix [ny, nx] bytes, sum [ny, nx]
+ * fp32: each may be NULL; out [ny, nx] fp32.  Refused (SPRK_EINVAL, nothing launched): a null raw or out, another mode, ny
+ * or nx outside 1 .. 16384, a pointer that is not 16-byte aligned, out equal to raw, gain, dark or sum.  One launch on
+ * `stream` (a hipStream_t), no workspace, no atomics, no host synchronisation. */
+#define SPRK_FIX_MAX_RADIUS 8
+int sprk_movie_correct(const void *raw, int mode, int ny, int nx, const float *gain, const float *dark,
+                       const uint8_t *fix, float *out, float *sum, int first, void *stream);
+
 /* ---- tiled power spectra (`joint ctf`)-----------------------------------------------------
  * sprk_psd_tiles: the summed half-plane power spectrum of T x T tiles of ONE raw micrograph (raw as for sprk_ingest_bin:
  * [ny,nx] samples of mode 0 / 1 / 2 / 6, 16-byte aligned start; rows may be only itemsize-aligned).  T a multiple of 16 in

@@ -1,7 +1,10 @@
 """``joint align``: whole-frame motion correction of movies on the device — the step before ``joint bin`` /
 ``joint eval --bin`` / ``joint ctf`` / ``joint extract``, in place of a MotionCor2 or ``relion_motioncorr`` run.
 
-A movie is an MRC stack of Z >= 2 short-exposure frames (modes 0 / 1 / 2 / 6), gain-corrected.  Per movie:
+A movie is an MRC stack of Z >= 2 short-exposure frames (modes 0 / 1 / 2 / 6): gain-corrected, or as the detector wrote it
+together with its references (``gain``, ``dark``, ``defects``, ``hot_sigma``; ``joint align --gain ...``): every frame then
+passes ``torch.ops.sprk.movie_correct`` first (``moviefix.CorrectedMovie``), and what follows sees float32
+frames whose fixed pattern is gone.  Per movie:
 
 * every frame is uploaded through two pinned slots (``MovieReader``) and Fourier-cropped to about ``align_size`` pixels a
   side (``align_geometry``; ``torch.ops.sprk.ingest_resample``), its mean taken out;
@@ -19,7 +22,7 @@ wraps round to the other, as in every Fourier shift; nothing is tapered.
 With a dose per frame (``dose``; ``joint align --dose``) a second, dose-weighted sum is formed beside the plain one, in
 Fourier space (``dose.sum_frames_weighted``); the plain sum and the shifts are what they are without it.
 
-Out of scope: gain and dark references, patch-wise (local) motion, TIFF and EER input.
+Out of scope: patch-wise (local) motion, TIFF and EER input, and gain references meant to be divided by.
 
 Coordinates and signs: x runs along nx (columns), y along ny (rows).  ``{name}_shifts.txt`` lists, per frame, the
 displacement (dx, dy) of the frame's content in raw pixels against the movie's mean position (mean zero over the frames);
@@ -315,15 +318,36 @@ def _dose_args(dose, pre_dose, kv, apix):
     return dose_mod.check_dose_args(dose, pre_dose, kv, apix)
 
 
+def _references(gain, gain_rot, gain_flip, dark, defects, hot_sigma):
+    """None when every one of them is at its default (``moviefix`` is then not even imported), else the checked
+    ``moviefix.References`` of a run"""
+    if gain is None and gain_rot == 0 and gain_flip is None and dark is None and defects is None and hot_sigma is None:
+        return None
+    from . import moviefix
+    return moviefix.References(gain, gain_rot, gain_flip, dark, defects, hot_sigma)
+
+
 def align_movie(path, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_shift=DEFAULT_MAX_SHIFT, iters=DEFAULT_ITERS,
-                no_align=False, device="cuda", resident_bytes=RESIDENT_BYTES, dose=None, pre_dose=0.0, kv=300.0, apix=None):
+                no_align=False, device="cuda", resident_bytes=RESIDENT_BYTES, dose=None, pre_dose=0.0, kv=300.0, apix=None,
+                gain=None, gain_rot=0, gain_flip=None, dark=None, defects=None, hot_sigma=None, references=None):
     """One movie -> (sum float32 CUDA [by, bx], drift float64 [Z, 2] (dx, dy) in raw pixels, header, info).  With ``dose``
     (e/A^2 per frame; ``pre_dose`` before frame 0, ``kv`` in 200..300, ``apix`` or else the header's pixel size):
-    info["dose_weighted"] is the dose-weighted sum of the same frames at the same shifts, float32 CUDA [by, bx]."""
+    info["dose_weighted"] is the dose-weighted sum of the same frames at the same shifts, float32 CUDA [by, bx].
+    With ``gain`` / ``dark`` (paths of single-image MRC references; ``gain_rot`` quarter turns, then ``gain_flip`` "ud" /
+    "lr"), ``defects`` (a file of ``x y w h`` rectangles) or ``hot_sigma`` (``moviefix``; ``references``: a run's
+    ``moviefix.References`` in their place): the frames are corrected first, and info["defects"] = {"static", "hot", "fix"}."""
     align_size, max_shift, iters = check_align_args(align_size, max_shift, iters)
     weighting = _dose_args(dose, pre_dose, kv, apix)
+    if references is None:
+        references = _references(gain, gain_rot, gain_flip, dark, defects, hot_sigma)
     with Movie(path, device, resident_bytes) as movie:
         h = movie.header
+        fixed = None
+        if references is not None and references.active:
+            from . import moviefix
+            movie, fixed = moviefix.prepare(movie, *references.for_frames(h.ny, h.nx, movie._reader.device),
+                                            references.hot_sigma)
+            h = movie.header                                     # the movie's with mode 2: the frames are float32 now
         if weighting is not None and weighting[3] is None:
             from .ctf import header_apix
             if header_apix(h) is None:
@@ -353,6 +377,8 @@ def align_movie(path, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_shift=DEFAULT_
             info = dict(info, dose_weighted=dose_mod.sum_frames_weighted(movie, by, bx, sy, sx, apix=weighting[3],
                                                                          dose=weighting[0], pre_dose=weighting[1],
                                                                          kv=weighting[2]))
+        if fixed is not None:
+            info = dict(info, defects=fixed)
     return total, np.stack([0.0 - sx, 0.0 - sy], axis=1), h, info             # 0.0 - x: no "-0.0000" in the table
 
 
@@ -377,16 +403,21 @@ def write_sum(path, image, header, by, bx):
 
 
 def align_dataset(movies, out_dir, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_shift=DEFAULT_MAX_SHIFT, iters=DEFAULT_ITERS,
-                  no_align=False, device="cuda", resident_bytes=RESIDENT_BYTES, dose=None, pre_dose=0.0, kv=300.0, apix=None):
+                  no_align=False, device="cuda", resident_bytes=RESIDENT_BYTES, dose=None, pre_dose=0.0, kv=300.0, apix=None,
+                  gain=None, gain_rot=0, gain_flip=None, dark=None, defects=None, hot_sigma=None):
     """``joint align``: for every movie of the table / directory ``movies``: ``out_dir/{name}.mrc`` (the aligned sum, float32
     [by, bx] with (by, bx) = ``ingest.resample_geometry(ny, nx, ftbin)``) and ``out_dir/{name}_shifts.txt`` (frame, dx, dy in
     raw pixels, mean zero), plus ``out_dir/images.txt`` (image_name, path) for the commands that follow.
     With ``dose`` (``align_movie``) also ``out_dir/{name}_DW.mrc``, the dose-weighted sum, and ``out_dir/images_DW.txt``; the
     other files are byte for byte what they are without it.
-    -> {name: {"frames", "shape", "shifts": [[dx, dy], ...], "iterations", "edge_frames"[, "dose_weighted": path]}}."""
+    With ``gain``, ``dark``, ``defects`` or ``hot_sigma`` (``align_movie``; the references are read and uploaded once, and
+    every movie's frames must have their size) also ``out_dir/{name}_defects.mrc``, the fix map (mode 0).
+    -> {name: {"frames", "shape", "shifts": [[dx, dy], ...], "iterations", "edge_frames"[, "dose_weighted": path]
+               [, "defects": {"static": n, "hot": n}]}}."""
     ftbin = ingest.check_ftbin(ftbin)
     check_align_args(align_size, max_shift, iters)
     _dose_args(dose, pre_dose, kv, apix)
+    references = _references(gain, gain_rot, gain_flip, dark, defects, hot_sigma)
     rows = micrograph_io.read_image_table(movies)
     if not rows:
         raise ValueError("no movies found in %s" % movies)
@@ -396,7 +427,7 @@ def align_dataset(movies, out_dir, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_s
     results, lines, lines_dw = {}, ["image_name\tpath"], ["image_name\tpath"]
     for _, name, path in rows:
         total, drift, header, info = align_movie(path, ftbin, align_size, max_shift, iters, no_align, device, resident_bytes,
-                                                 dose, pre_dose, kv, apix)
+                                                 dose, pre_dose, kv, apix, references=references)
         by, bx = total.shape
         out = os.path.join(out_dir, name + ".mrc")
         write_sum(out, total.cpu().numpy(), header, by, bx)
@@ -410,6 +441,10 @@ def align_dataset(movies, out_dir, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_s
             write_sum(out_dw, info["dose_weighted"].cpu().numpy(), header, by, bx)
             lines_dw.append("%s\t%s" % (name, out_dw))
             results[name]["dose_weighted"] = out_dw
+        if "defects" in info:
+            from . import moviefix
+            moviefix.write_fix_map(os.path.join(out_dir, name + "_defects.mrc"), info["defects"]["fix"].cpu().numpy())
+            results[name]["defects"] = {"static": info["defects"]["static"], "hot": info["defects"]["hot"]}
         logger.info("%s: %d frames of %dx%d -> %dx%d, %d iteration(s), largest displacement %.2f raw pixels", name, header.nz,
                     header.ny, header.nx, by, bx, info["iterations"], float(np.abs(drift).max()))
     with open(os.path.join(out_dir, "images.txt"), "w") as f:

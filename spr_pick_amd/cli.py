@@ -139,6 +139,10 @@ def _check_ctf(ns):
 def _check_align(ns):
     from .align import check_align_args
     check_align_args(ns.align_size, ns.max_shift, ns.iters)
+    from .moviefix import check_fix_args
+    if ns.gain is None and (ns.gain_rot is not None or ns.gain_flip is not None):
+        raise ValueError("--gain_rot and --gain_flip turn the gain reference: give --gain G as well")
+    check_fix_args(ns.gain, ns.gain_rot or 0, ns.gain_flip, ns.dark, ns.defects, ns.hot_sigma)
     if ns.dose is None:
         for flag in ("pre_dose", "kv", "apix"):
             if getattr(ns, flag) is not None:
@@ -272,16 +276,19 @@ def build_parser():
                          "A + 550 < --min_defocus)")
     cf.check = _check_ctf
 
-    al_help = ("Whole-frame motion correction of gain-corrected movies (MRC stacks) on the GPU: shifts estimated by iterated "
+    al_help = ("Whole-frame motion correction of movies (MRC stacks) on the GPU: shifts estimated by iterated "
                "cross-correlation, frames shifted, summed and (--ftbin) Fourier-cropped (replaces a MotionCor2 / "
-               "relion_motioncorr run before everything else).  With --dose also a dose-weighted sum per movie, "
+               "relion_motioncorr run before everything else).  Movies as the detector wrote them are corrected first "
+               "(--gain, --dark, --defects, --hot_sigma); a fixed pattern left in the frames holds every estimated shift at "
+               "zero.  With --dose also a dose-weighted sum per movie, "
                "{name}_DW.mrc: give the plain sums (images.txt) to `joint ctf`, the weighted ones (images_DW.txt) to `joint "
-               "eval` / `joint extract`, and pass those tables, not the directory, which then holds both.  Not covered: gain "
-               "and dark references, patch-wise (local) motion, TIFF and EER input.")
+               "eval` / `joint extract`, and pass those tables, not the directory, which then holds both.  Not covered: "
+               "patch-wise (local) motion, TIFF and EER input, and references meant to be divided by.")
     al = cmds.add_parser("align", help=al_help, description=al_help)
     al.add_argument("--movies", "-d", required=True, metavar="T",
                     help="Table (image_name, path) or directory of MRC movie stacks (modes 0 / 1 / 2 / 6, at least 2 frames, "
-                         "at most 16384 pixels a side, gain-corrected).")
+                         "at most 16384 pixels a side; gain-corrected, or raw together with --gain / --dark / --defects / "
+                         "--hot_sigma).")
     al.add_argument("--out", "-o", required=True,
                     help="Directory for {name}.mrc (the aligned sum, float32), {name}_shifts.txt (frame, dx, dy in raw pixels, "
                          "mean zero) and images.txt.")
@@ -306,6 +313,24 @@ def build_parser():
     al.add_argument("--apix", type=float, metavar="A",
                     help="pixel size of the frames in Angstrom (default: the movie header's; a movie whose header states none is "
                          "refused; needs --dose)")
+    al.add_argument("--gain", metavar="G",
+                    help="gain reference, a single-image MRC (mode 0 / 1 / 2 / 6) of the frames' size: every sample is "
+                         "MULTIPLIED by it (a reference meant to be divided by is not covered: invert it first).  Pixels "
+                         "whose gain is not finite or not above 0 are replaced by the mean of the good pixels around them.  "
+                         "Also writes {name}_defects.mrc, the map of the replaced pixels, as every flag of this group does")
+    al.add_argument("--gain_rot", type=int, choices=(0, 1, 2, 3), metavar="{0,1,2,3}",
+                    help="quarter turns of the gain reference, counter-clockwise as numpy.rot90 (default 0; needs --gain)")
+    al.add_argument("--gain_flip", choices=("ud", "lr"),
+                    help="flip the gain reference upside down or left to right, after the turn (needs --gain)")
+    al.add_argument("--dark", metavar="D",
+                    help="dark reference, a single-image MRC of the frames' size, subtracted from every sample before the gain")
+    al.add_argument("--defects", metavar="FILE",
+                    help="defect file in MotionCor2's layout: one rectangle `x y w h` per line (x the column, y the row of its "
+                         "first sample; # starts a comment); its pixels are replaced like those of a bad gain")
+    al.add_argument("--hot_sigma", type=float, metavar="S",
+                    help="also replace hot pixels: those of the movie's plain sum more than S standard deviations above its "
+                         "mean, found in up to 4 rounds (finite, > 0; 6 is recommended; off by default).  Works without "
+                         "--gain, for gain-corrected movies that still have hot pixels")
     al.check = _check_align
     return parser
 
@@ -406,7 +431,10 @@ def run_align(args):
                               max_shift=args["max_shift"], iters=args["iters"], no_align=args["no_align"],
                               **({} if args.get("dose") is None else
                                  {"dose": args["dose"], "pre_dose": args["pre_dose"] or 0.0, "kv": args["kv"] or 300.0,
-                                  "apix": args.get("apix")}))
+                                  "apix": args.get("apix")}),
+                              **{k: args[k] for k in ("gain", "dark", "defects", "hot_sigma") if args.get(k) is not None},
+                              **({} if args.get("gain") is None else
+                                 {"gain_rot": args["gain_rot"] or 0, "gain_flip": args["gain_flip"]}))
     print(json.dumps({"movies": res}))
     return res
 

@@ -900,6 +900,44 @@ _register("align_synthesize", "(Tensor F, int by, int bx, Tensor w3, Tensor w4) 
           _align_synthesize_fake)
 
 
+# raw detector movies in (moviefix.py: csrc/moviefix.hip): dark, gain and the repair of marked pixels, one frame per call
+FIX_MAX_RADIUS = 8                               # SPRK_FIX_MAX_RADIUS: larger values of the fix map are clamped to it
+
+
+def _movie_correct_check(raw, mode, ny, nx, gain, dark, fix, out, sum):
+    if mode not in MRC_ITEMSIZE:
+        raise _lib.SprkError("movie_correct: unsupported MRC mode %d" % mode)
+    if not (1 <= ny <= INGEST_MAX_SIDE and 1 <= nx <= INGEST_MAX_SIDE):
+        raise _lib.SprkError("movie_correct: a %dx%d frame (both sides in 1..%d)" % (ny, nx, INGEST_MAX_SIDE))
+    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
+        raise _lib.SprkError("movie_correct: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
+                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+    for name, t, dtype in (("gain", gain, torch.float32), ("dark", dark, torch.float32), ("fix", fix, torch.uint8),
+                           ("out", out, torch.float32), ("sum", sum, torch.float32)):
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != (ny, nx) or t.device != raw.device):
+            raise _lib.SprkError("movie_correct: %s must be %s [%d, %d] on %s, got %s %s on %s"
+                                 % (name, dtype, ny, nx, raw.device, t.dtype, tuple(t.shape), t.device))
+
+
+def _movie_correct(raw, mode, ny, nx, gain, dark, fix, out, sum, first):
+    """raw: uint8 CUDA tensor holding one frame's ny*nx samples; gain, dark float32 [ny, nx] or None; fix uint8 [ny, nx] or
+    None (0: keep, r > 0: the mean of the good pixels within r, at most ``FIX_MAX_RADIUS``); out float32 [ny, nx],
+    overwritten; sum float32 [ny, nx] or None: out is written to it when ``first``, else added (sprk_movie_correct)."""
+    _movie_correct_check(raw, mode, ny, nx, gain, dark, fix, out, sum)
+    if not all(t is None or t.is_contiguous() for t in (raw, gain, dark, fix, out, sum)):
+        raise _lib.SprkError("movie_correct: raw, gain, dark, fix, out and sum must be contiguous")
+    check(_lib.lib().sprk_movie_correct(_p(raw), int(mode), int(ny), int(nx), _p(gain), _p(dark), _p(fix), _p(out), _p(sum),
+                                        1 if first else 0, _stream(raw)), "sprk_movie_correct")
+
+
+def _movie_correct_fake(raw, mode, ny, nx, gain, dark, fix, out, sum, first):
+    _movie_correct_check(raw, mode, ny, nx, gain, dark, fix, out, sum)
+
+
+_register("movie_correct", "(Tensor raw, int mode, int ny, int nx, Tensor? gain, Tensor? dark, Tensor? fix, Tensor(a!) out, "
+          "Tensor(b!)? sum, bool first) -> ()", _movie_correct, _movie_correct_fake)
+
+
 # ---- particle extraction (extract.py: raw MRC samples + pick coordinates -> normalised particle stack) ------------------------
 EXTRACT_MAX_BOX = 1024                           # sprk_extract_boxes: the int64 sum of squares stays below 2^63 up to here
 EXTRACT_NORMALIZE, EXTRACT_INVERT = 1, 2         # SPRK_EXTRACT_*
