@@ -737,6 +737,29 @@ int sprk_align_synthesize(const float *F, int Ku, int Hs, int by, int bx, const 
 int sprk_movie_correct(const void *raw, int mode, int ny, int nx, const float *gain, const float *dark,
                        const uint8_t *fix, float *out, float *sum, int first, void *stream);
 
+/* ---- local motion correction (`joint align --patch`) ---------------------------------------------
+ * sprk_align_warp: one fp32 frame src [ny, nx] resampled through a smooth displacement field into a running sum y [ny, nx]:
+ *   out(i, j) = src(i + sy(i, j), j + sx(i, j)) with periodic edges;   y = out when `first` (y is then not read), else
+ *   y + out, one fp32 add.
+ * cy, cx: 6 coefficients each of sy and sx, HOST pointers read during the call and passed on by value (no device read, no
+ * synchronisation).  inv_nx = 1.0f / (float)nx and inv_ny = 1.0f / (float)ny, rounded on the host.  Per pixel and axis, in
+ * fp32, every fmaf one rounding and every other product or difference one rounding (nothing else is fused):
+ *   u = fmaf((float)j, inv_nx, -0.5f),  v = fmaf((float)i, inv_ny, -0.5f),  uu = u * u,  uv = u * v,  vv = v * v;
+ *   s = c[0];  s = fmaf(c[1], u, s);  s = fmaf(c[2], v, s);  s = fmaf(c[3], uu, s);  s = fmaf(c[4], uv, s);
+ *   s = fmaf(c[5], vv, s);   s = fminf(fmaxf(s, -16.0f), 16.0f)   (a NaN, which only an overflow can make, becomes -16);
+ *   fl = floorf(s),  t = s - fl (exact),  tt = t * t,  the first tap at i0 - 1 with i0 = i + (int)fl (j0 likewise);
+ *   w0 = fmaf(fmaf(-0.5f, t, 1.0f), t, -0.5f) * t,    w1 = fmaf(fmaf(1.5f, t, -2.5f), tt, 1.0f),
+ *   w2 = fmaf(fmaf(-1.5f, t, 2.0f), t, 0.5f) * t,     w3 = fmaf(0.5f, t, -0.5f) * tt          (Catmull-Rom, Horner form);
+ *   r_a = fmaf chain from 0.0f over b = 0 .. 3 ascending of wx_b * src[(i0 - 1 + a) mod ny, (j0 - 1 + b) mod nx];
+ *   out = fmaf chain from 0.0f over a = 0 .. 3 ascending of wy_a * r_a.
+ * The clamp to +-SPRK_WARP_MAX_SHIFT is part of the contract: it bounds what a workgroup stages, so no coefficient set
+ * reads out of bounds.  With all coefficients zero the weights are (-0, 1, 0, 0) and out == src on finite data; a constant
+ * integer shift is a roll, value for value.  1 <= ny, nx <= 16384 (the taps wrap as often as it takes).
+ * Refused (SPRK_EINVAL, nothing launched): a null pointer, other sizes, a coefficient that is not finite, src or y not
+ * 4-byte aligned, y == src.  One launch on `stream`, no workspace, no atomics, no host synchronisation. */
+#define SPRK_WARP_MAX_SHIFT 16
+int sprk_align_warp(const float *src, int ny, int nx, const float *cy, const float *cx, float *y, int first, void *stream);
+
 /* ---- tiled power spectra (`joint ctf`)-----------------------------------------------------
  * sprk_psd_tiles: the summed half-plane power spectrum of T x T tiles of ONE raw micrograph (raw as for sprk_ingest_bin:
  * [ny,nx] samples of mode 0 / 1 / 2 / 6, 16-byte aligned start; rows may be only itemsize-aligned).  T a multiple of 16 in

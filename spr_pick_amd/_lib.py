@@ -148,6 +148,7 @@ _SIGS = {
     "sprk_align_synthesize_ws_bytes": (c_sz, [c_i, c_i]),
     "sprk_align_synthesize": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_vp, c_sz, c_vp]),
     "sprk_movie_correct": (c_i, [c_vp, c_i, c_i, c_i, c_f, c_f, c_vp, c_f, c_f, c_i, c_vp]),
+    "sprk_align_warp": (c_i, [c_f, c_i, c_i, c_vp, c_vp, c_f, c_i, c_vp]),
     "sprk_psd_tiles_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "sprk_psd_tiles": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i, c_f, c_vp, c_sz, c_vp]),
     "sprk_ctf_score_ws_bytes": (c_sz, [c_i, c_i]),

@@ -22,7 +22,11 @@ wraps round to the other, as in every Fourier shift; nothing is tapered.
 With a dose per frame (``dose``; ``joint align --dose``) a second, dose-weighted sum is formed beside the plain one, in
 Fourier space (``dose.sum_frames_weighted``); the plain sum and the shifts are what they are without it.
 
-Out of scope: patch-wise (local) motion, TIFF and EER input, and gain references meant to be divided by.
+With ``patch`` (``joint align --patch PY,PX``) one smooth local field per movie is fitted after the whole-frame estimate and
+every frame is warped by it before it is summed (``localmotion``): ``torch.ops.sprk.align_warp``.
+
+Out of scope: local motion finer than that one smooth field (per-particle polishing), TIFF and EER input, and gain
+references meant to be divided by.
 
 Coordinates and signs: x runs along nx (columns), y along ny (rows).  ``{name}_shifts.txt`` lists, per frame, the
 displacement (dx, dy) of the frame's content in raw pixels against the movie's mean position (mean zero over the frames);
@@ -327,16 +331,35 @@ def _references(gain, gain_rot, gain_flip, dark, defects, hot_sigma):
     return moviefix.References(gain, gain_rot, gain_flip, dark, defects, hot_sigma)
 
 
+def _patch_args(patch, patch_shift, patch_iters, no_align):
+    """None without ``patch`` (the other two must then be unset), else the checked ((PY, PX), R, I)"""
+    if patch is None:
+        if patch_shift is not None or patch_iters is not None:
+            raise ValueError("patch_shift and patch_iters belong to the local motion: give patch as well")
+        return None
+    if no_align:
+        raise ValueError("patch fits a local field on top of the whole-frame shifts: it does not go with no_align")
+    from . import localmotion
+    return localmotion.check_patch_args(patch, localmotion.DEFAULT_PATCH_SHIFT if patch_shift is None else patch_shift,
+                                        localmotion.DEFAULT_PATCH_ITERS if patch_iters is None else patch_iters)
+
+
 def align_movie(path, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_shift=DEFAULT_MAX_SHIFT, iters=DEFAULT_ITERS,
                 no_align=False, device="cuda", resident_bytes=RESIDENT_BYTES, dose=None, pre_dose=0.0, kv=300.0, apix=None,
-                gain=None, gain_rot=0, gain_flip=None, dark=None, defects=None, hot_sigma=None, references=None):
+                gain=None, gain_rot=0, gain_flip=None, dark=None, defects=None, hot_sigma=None, references=None, patch=None,
+                patch_shift=None, patch_iters=None):
     """One movie -> (sum float32 CUDA [by, bx], drift float64 [Z, 2] (dx, dy) in raw pixels, header, info).  With ``dose``
     (e/A^2 per frame; ``pre_dose`` before frame 0, ``kv`` in 200..300, ``apix`` or else the header's pixel size):
     info["dose_weighted"] is the dose-weighted sum of the same frames at the same shifts, float32 CUDA [by, bx].
     With ``gain`` / ``dark`` (paths of single-image MRC references; ``gain_rot`` quarter turns, then ``gain_flip`` "ud" /
     "lr"), ``defects`` (a file of ``x y w h`` rectangles) or ``hot_sigma`` (``moviefix``; ``references``: a run's
-    ``moviefix.References`` in their place): the frames are corrected first, and info["defects"] = {"static", "hot", "fix"}."""
+    ``moviefix.References`` in their place): the frames are corrected first, and info["defects"] = {"static", "hot", "fix"}.
+    With ``patch`` = (PY, PX) (``patch_shift``: the half width of the patches' correlation window in reduced pixels,
+    ``patch_iters``: iterations at most; ``localmotion``): every frame is also warped by the fitted local field, and
+    info["local"] = {"patch", "reduced", "qx", "qy" ([3, 6], raw pixels), "iterations", "moved", "dropped", "geometry",
+    "measured", "fitted" ([Z, P, 2] (y, x), raw pixels)}."""
     align_size, max_shift, iters = check_align_args(align_size, max_shift, iters)
+    patch = _patch_args(patch, patch_shift, patch_iters, no_align)
     weighting = _dose_args(dose, pre_dose, kv, apix)
     if references is None:
         references = _references(gain, gain_rot, gain_flip, dark, defects, hot_sigma)
@@ -371,12 +394,33 @@ def align_movie(path, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_shift=DEFAULT_
             ry, rx, info = estimate_shifts(reduced, max_shift, iters, os.path.basename(path))
             sy, sx = ry * (ny / Sy), rx * (nx / Sx)
             info = dict(info, reduced=(Sy, Sx))
-        total = sum_frames(movie, by, bx, sy, sx)
+        summed, anchor_term = movie, None
+        if patch is not None:
+            from . import localmotion
+            for f in range(Z):                                   # the reduced frames laid on each other, as estimate_shifts does
+                shifted = reduced[f].clone()
+                torch.ops.sprk.align_accumulate(_flat_bytes(shifted), 2, Sy, Sx, Sy, Sx, shift_matrix(Sy, Sy, ry[f], dev),
+                                                shift_matrix(Sx, Sx, rx[f], dev), 0.0, reduced[f], True)
+            qy, qx, local = localmotion.estimate_field(reduced, *patch, name=os.path.basename(path))
+            scale = np.array([ny / Sy, nx / Sx])                 # they differ slightly
+            local = dict(local, patch=patch[0], reduced=(Sy, Sx), qy=qy * scale[0], qx=qx * scale[1],
+                         measured=local["measured"] * scale, fitted=local["fitted"] * scale)
+            info = dict(info, local=local)
+            summed = localmotion.LocalMovie(movie, sy, sx, local["qy"], local["qx"])
+            anchor_term = summed.anchor_term
+            sy, sx = np.zeros(Z), np.zeros(Z)                    # the frames of ``summed`` are shifted already
+        total = sum_frames(summed, by, bx, sy, sx)
+        if anchor_term:
+            total += anchor_term
         if weighting is not None:
             from . import dose as dose_mod
-            info = dict(info, dose_weighted=dose_mod.sum_frames_weighted(movie, by, bx, sy, sx, apix=weighting[3],
+            info = dict(info, dose_weighted=dose_mod.sum_frames_weighted(summed, by, bx, sy, sx, apix=weighting[3],
                                                                          dose=weighting[0], pre_dose=weighting[1],
                                                                          kv=weighting[2]))
+            if anchor_term:
+                info["dose_weighted"] += anchor_term
+        if patch is not None:
+            sy, sx = summed.shifts_y, summed.shifts_x
         if fixed is not None:
             info = dict(info, defects=fixed)
     return total, np.stack([0.0 - sx, 0.0 - sy], axis=1), h, info             # 0.0 - x: no "-0.0000" in the table
@@ -404,7 +448,8 @@ def write_sum(path, image, header, by, bx):
 
 def align_dataset(movies, out_dir, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_shift=DEFAULT_MAX_SHIFT, iters=DEFAULT_ITERS,
                   no_align=False, device="cuda", resident_bytes=RESIDENT_BYTES, dose=None, pre_dose=0.0, kv=300.0, apix=None,
-                  gain=None, gain_rot=0, gain_flip=None, dark=None, defects=None, hot_sigma=None):
+                  gain=None, gain_rot=0, gain_flip=None, dark=None, defects=None, hot_sigma=None, patch=None, patch_shift=None,
+                  patch_iters=None):
     """``joint align``: for every movie of the table / directory ``movies``: ``out_dir/{name}.mrc`` (the aligned sum, float32
     [by, bx] with (by, bx) = ``ingest.resample_geometry(ny, nx, ftbin)``) and ``out_dir/{name}_shifts.txt`` (frame, dx, dy in
     raw pixels, mean zero), plus ``out_dir/images.txt`` (image_name, path) for the commands that follow.
@@ -412,11 +457,14 @@ def align_dataset(movies, out_dir, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_s
     other files are byte for byte what they are without it.
     With ``gain``, ``dark``, ``defects`` or ``hot_sigma`` (``align_movie``; the references are read and uploaded once, and
     every movie's frames must have their size) also ``out_dir/{name}_defects.mrc``, the fix map (mode 0).
+    With ``patch`` (``align_movie``) also ``out_dir/{name}_local.txt`` (``localmotion.write_local``); without it no other
+    file changes a byte.
     -> {name: {"frames", "shape", "shifts": [[dx, dy], ...], "iterations", "edge_frames"[, "dose_weighted": path]
-               [, "defects": {"static": n, "hot": n}]}}."""
+               [, "defects": {"static": n, "hot": n}][, "local": {"path", "patch", "iterations", "dropped", "qx", "qy"}]}}."""
     ftbin = ingest.check_ftbin(ftbin)
     check_align_args(align_size, max_shift, iters)
     _dose_args(dose, pre_dose, kv, apix)
+    _patch_args(patch, patch_shift, patch_iters, no_align)
     references = _references(gain, gain_rot, gain_flip, dark, defects, hot_sigma)
     rows = micrograph_io.read_image_table(movies)
     if not rows:
@@ -427,7 +475,8 @@ def align_dataset(movies, out_dir, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_s
     results, lines, lines_dw = {}, ["image_name\tpath"], ["image_name\tpath"]
     for _, name, path in rows:
         total, drift, header, info = align_movie(path, ftbin, align_size, max_shift, iters, no_align, device, resident_bytes,
-                                                 dose, pre_dose, kv, apix, references=references)
+                                                 dose, pre_dose, kv, apix, references=references, patch=patch,
+                                                 patch_shift=patch_shift, patch_iters=patch_iters)
         by, bx = total.shape
         out = os.path.join(out_dir, name + ".mrc")
         write_sum(out, total.cpu().numpy(), header, by, bx)
@@ -445,6 +494,13 @@ def align_dataset(movies, out_dir, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_s
             from . import moviefix
             moviefix.write_fix_map(os.path.join(out_dir, name + "_defects.mrc"), info["defects"]["fix"].cpu().numpy())
             results[name]["defects"] = {"static": info["defects"]["static"], "hot": info["defects"]["hot"]}
+        if "local" in info:
+            from . import localmotion
+            local = info["local"]
+            out_local = os.path.join(out_dir, name + "_local.txt")
+            localmotion.write_local(out_local, local)
+            results[name]["local"] = {"path": out_local, "patch": list(local["patch"]), "iterations": local["iterations"],
+                                      "dropped": local["dropped"], "qx": local["qx"].tolist(), "qy": local["qy"].tolist()}
         logger.info("%s: %d frames of %dx%d -> %dx%d, %d iteration(s), largest displacement %.2f raw pixels", name, header.nz,
                     header.ny, header.nx, by, bx, info["iterations"], float(np.abs(drift).max()))
     with open(os.path.join(out_dir, "images.txt"), "w") as f:

@@ -4,7 +4,8 @@ flag -> configuration mapping, plus ``joint bin`` (the README's ``newstack -bin`
 (particle stacks from the pick tables and the raw micrographs, on the GPU) and ``joint ctf`` (tiled power spectra of the raw
 micrographs on the GPU, one fitted defocus each, or with ``--astigmatism`` two and an angle, ``micrographs_ctf.star`` for
 ``joint extract --ctf``, which with ``--ctf_correct`` also phase-flips the stacks) and ``joint align`` (whole-frame motion
-correction of movies on the GPU, the sums the other commands start from; with ``--dose`` a dose-weighted sum beside the plain one).
+correction of movies on the GPU, the sums the other commands start from; with ``--dose`` a dose-weighted sum beside the plain
+one, with ``--patch`` a smooth local field on top of the whole-frame shifts).
 Run as ``python -m spr_pick_amd ...``; for several GPUs launch it
 under ``python -m torch.distributed.run --nproc-per-node N -m spr_pick_amd -- ...`` (keep the ``--``)."""
 import argparse
@@ -143,6 +144,17 @@ def _check_align(ns):
     if ns.gain is None and (ns.gain_rot is not None or ns.gain_flip is not None):
         raise ValueError("--gain_rot and --gain_flip turn the gain reference: give --gain G as well")
     check_fix_args(ns.gain, ns.gain_rot or 0, ns.gain_flip, ns.dark, ns.defects, ns.hot_sigma)
+    if ns.patch is None:
+        for flag in ("patch_shift", "patch_iters"):
+            if getattr(ns, flag) is not None:
+                raise ValueError("--%s belongs to the local motion: give --patch PY,PX as well" % flag)
+    else:
+        from . import localmotion
+        if ns.no_align:
+            raise ValueError("--patch fits a local field on top of the whole-frame shifts: it does not go with --no_align")
+        localmotion.check_patch_args(localmotion.parse_patch(ns.patch),
+                                     localmotion.DEFAULT_PATCH_SHIFT if ns.patch_shift is None else ns.patch_shift,
+                                     localmotion.DEFAULT_PATCH_ITERS if ns.patch_iters is None else ns.patch_iters)
     if ns.dose is None:
         for flag in ("pre_dose", "kv", "apix"):
             if getattr(ns, flag) is not None:
@@ -280,10 +292,13 @@ def build_parser():
                "cross-correlation, frames shifted, summed and (--ftbin) Fourier-cropped (replaces a MotionCor2 / "
                "relion_motioncorr run before everything else).  Movies as the detector wrote them are corrected first "
                "(--gain, --dark, --defects, --hot_sigma); a fixed pattern left in the frames holds every estimated shift at "
-               "zero.  With --dose also a dose-weighted sum per movie, "
+               "zero.  With --patch PY,PX one smooth local field per movie (MotionCor2's form: a quadratic in the position, a "
+               "cubic in time) is fitted to PY x PX patches after the whole-frame estimate, and every frame is warped by it "
+               "before it is summed; {name}_local.txt reports it.  With --dose also a dose-weighted sum per movie, "
                "{name}_DW.mrc: give the plain sums (images.txt) to `joint ctf`, the weighted ones (images_DW.txt) to `joint "
                "eval` / `joint extract`, and pass those tables, not the directory, which then holds both.  Not covered: "
-               "patch-wise (local) motion, TIFF and EER input, and references meant to be divided by.")
+               "local motion finer than the one smooth field of --patch (per-particle polishing), TIFF and EER input, and "
+               "references meant to be divided by.")
     al = cmds.add_parser("align", help=al_help, description=al_help)
     al.add_argument("--movies", "-d", required=True, metavar="T",
                     help="Table (image_name, path) or directory of MRC movie stacks (modes 0 / 1 / 2 / 6, at least 2 frames, "
@@ -302,6 +317,17 @@ def build_parser():
     al.add_argument("--iters", type=int, default=6, metavar="I",
                     help="iterations of the estimate at most (default 6; it stops when no shift moves by 0.01 reduced pixel)")
     al.add_argument("--no_align", action="store_true", help="sum (and crop) the frames as they are: all shifts zero")
+    al.add_argument("--patch", metavar="PY,PX",
+                    help="local motion correction: fit one smooth field to PY x PX patches (3..16 each; 5,5 is MotionCor2's "
+                         "usual choice for a 4096^2 frame) and warp every frame by it, Catmull-Rom taps (0.88 of the signal at "
+                         "half Nyquist for a half-pixel shift, none at Nyquist: sums that are cropped with --ftbin 2 lose "
+                         "little).  Writes {name}_local.txt.  Needs at least 4 frames; not with --no_align")
+    al.add_argument("--patch_shift", type=int, metavar="R",
+                    help="half width of the patches' correlation window in pixels of the reduced frames (1..31, default 6; "
+                         "2R+1 must fit a patch; needs --patch)")
+    al.add_argument("--patch_iters", type=int, metavar="I",
+                    help="iterations of the local estimate at most (default 4; it stops when no patch-centre value of the "
+                         "field moves by 0.01 reduced pixel; needs --patch)")
     al.add_argument("--dose", type=float, metavar="E",
                     help="dose weighting (Grant & Grigorieff 2015, as in unblur): the exposure per frame in e/A^2 (> 0); writes "
                          "{name}_DW.mrc and images_DW.txt beside the plain sums, which stay what they are without it")
@@ -427,12 +453,18 @@ def run_ctf(args):
 def run_align(args):
     import json
     from . import align
+    if args.get("patch") is not None:
+        from .localmotion import parse_patch
+        args = dict(args, patch=parse_patch(args["patch"]))
     res = align.align_dataset(args["movies"], args["out"], ftbin=args["ftbin"], align_size=args["align_size"],
                               max_shift=args["max_shift"], iters=args["iters"], no_align=args["no_align"],
                               **({} if args.get("dose") is None else
                                  {"dose": args["dose"], "pre_dose": args["pre_dose"] or 0.0, "kv": args["kv"] or 300.0,
                                   "apix": args.get("apix")}),
                               **{k: args[k] for k in ("gain", "dark", "defects", "hot_sigma") if args.get(k) is not None},
+                              **({} if args.get("patch") is None else
+                                 {"patch": tuple(args["patch"]), "patch_shift": args["patch_shift"],
+                                  "patch_iters": args["patch_iters"]}),
                               **({} if args.get("gain") is None else
                                  {"gain_rot": args["gain_rot"] or 0, "gain_flip": args["gain_flip"]}))
     print(json.dumps({"movies": res}))

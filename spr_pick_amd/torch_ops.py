@@ -938,6 +938,52 @@ _register("movie_correct", "(Tensor raw, int mode, int ny, int nx, Tensor? gain,
           "Tensor(b!)? sum, bool first) -> ()", _movie_correct, _movie_correct_fake)
 
 
+# local motion (localmotion.py: csrc/warp.hip): one frame through a quadratic displacement field, Catmull-Rom taps
+WARP_MAX_SHIFT = 16                              # SPRK_WARP_MAX_SHIFT: the field is clamped to +- this many pixels
+WARP_TERMS = 6                                   # coefficients per axis: 1, u, v, u u, u v, v v
+
+
+def _align_warp_check(src, cy, cx, y):
+    if src.dtype != torch.float32 or src.dim() != 2:
+        raise _lib.SprkError("align_warp: src must be float32 [ny, nx], got %s %s" % (src.dtype, tuple(src.shape)))
+    ny, nx = src.shape
+    if not (1 <= ny <= INGEST_MAX_SIDE and 1 <= nx <= INGEST_MAX_SIDE):
+        raise _lib.SprkError("align_warp: a %dx%d frame (both sides in 1..%d)" % (ny, nx, INGEST_MAX_SIDE))
+    if y.dtype != torch.float32 or tuple(y.shape) != (ny, nx) or y.device != src.device:
+        raise _lib.SprkError("align_warp: y must be float32 [%d, %d] on %s, got %s %s on %s"
+                             % (ny, nx, src.device, y.dtype, tuple(y.shape), y.device))
+    if len(cy) != WARP_TERMS or len(cx) != WARP_TERMS:
+        raise _lib.SprkError("align_warp: %d + %d coefficients (%d per axis: 1, u, v, uu, uv, vv)"
+                             % (len(cy), len(cx), WARP_TERMS))
+    c32 = (ctypes.c_float * WARP_TERMS)(*cy), (ctypes.c_float * WARP_TERMS)(*cx)    # rounded to float32 here
+    for c in c32:
+        for v in c:
+            if v != v or v in (float("inf"), float("-inf")):
+                raise _lib.SprkError("align_warp: every coefficient must be finite in float32, got %s and %s"
+                                     % (list(cy), list(cx)))
+    return c32
+
+
+def _align_warp(src, cy, cx, y, first):
+    """src float32 CUDA [ny, nx]; cy, cx: the 6 coefficients each of the row and column displacement (1, u, v, uu, uv, vv;
+    u = j / nx - 1/2, v = i / ny - 1/2), passed by value; y float32 [ny, nx]: out(i, j) = src(i + sy, j + sx), periodic,
+    Catmull-Rom, |s| clamped to ``WARP_MAX_SHIFT``, written to y when ``first``, else added (sprk_align_warp)."""
+    c32y, c32x = _align_warp_check(src, cy, cx, y)
+    if not (src.is_contiguous() and y.is_contiguous()):
+        raise _lib.SprkError("align_warp: src and y must be contiguous")
+    if src.data_ptr() == y.data_ptr():
+        raise _lib.SprkError("align_warp: y must not be src")
+    check(_lib.lib().sprk_align_warp(_p(src), int(src.shape[0]), int(src.shape[1]), c32y, c32x, _p(y), 1 if first else 0,
+                                     _stream(src)), "sprk_align_warp")
+
+
+def _align_warp_fake(src, cy, cx, y, first):
+    _align_warp_check(src, cy, cx, y)
+
+
+_register("align_warp", "(Tensor src, float[] cy, float[] cx, Tensor(a!) y, bool first) -> ()", _align_warp, _align_warp_fake)
+
+
 # ---- particle extraction (extract.py: raw MRC samples + pick coordinates -> normalised particle stack) ------------------------
 EXTRACT_MAX_BOX = 1024                           # sprk_extract_boxes: the int64 sum of squares stays below 2^63 up to here
 EXTRACT_NORMALIZE, EXTRACT_INVERT = 1, 2         # SPRK_EXTRACT_*
