@@ -760,6 +760,65 @@ int sprk_movie_correct(const void *raw, int mode, int ny, int nx, const float *g
 #define SPRK_WARP_MAX_SHIFT 16
 int sprk_align_warp(const float *src, int ny, int nx, const float *cy, const float *cx, float *y, int first, void *stream);
 
+/* ---- reference-free 2-D classification (`joint class2d`) ------------------------------------------
+ * The rigid transform T(src, ct, st, dy, dx) of an fp32 image src [S, S] (S even, 2..128; c = S / 2), per output pixel
+ * (i, j), in fp32, every fmaf one rounding and every other product or difference one rounding (nothing else is fused):
+ *   y = (float)(i - c),  x = (float)(j - c);
+ *   u = fmaf(ct, y, -(st * x)),  v = fmaf(st, y, ct * x)                (the inner product rounded first);
+ *   fu = floorf(u),  tu = u - fu;   fv = floorf(v),  tv = v - fv;   the first tap at (i0, j0) = ((int)fu + c + dy,
+ *   (int)fv + c + dx);   s[a][b] = src[i0 + a, j0 + b], or 0.0f where that lies outside [0, S) (formed in registers, never
+ *   read: the edges are not periodic);
+ *   r_a = fmaf(tv, s[a][1], (1.0f - tv) * s[a][0]),  a = 0, 1;     T = fmaf(tu, r_1, (1.0f - tu) * r_0).
+ * With (ct, st) = (1, 0) this is the shifted copy T(i, j) = src[i + dy, j + dx], zero-filled, value for value on finite data.
+ * (ct, st) come from cs [A_n, 2] fp32 on the device, row a = (cos, sin) of 2 pi a / A_n formed in float64 and rounded once
+ * (spr_pick_amd.class2d.angle_table); 1 <= A_n <= 720.  Every index read from device memory (a source, an angle, a member,
+ * a packed pixel, a class offset) is clamped into its array and a shift to +-256 (past +-S every tap is outside): no
+ * content of these arrays makes a kernel read or write out of bounds.
+ *
+ * sprk_class_transform: M output images; output m is T of src[idx[m]] (src [n_src, S, S]) at the angle cs[ang[m]] and the
+ * shift (dy, dx) = shift[m] (int32 [M, 2]); idx, ang, shift int32 on the device.  flags:
+ *   SPRK_CLASS_MASK: pixels with (i-c)^2 + (j-c)^2 > radius^2 become 0.0f (integer arithmetic; 0 <= radius <= S);
+ *   SPRK_CLASS_NORMALIZE (implies the mask): with v the masked image and `count` the pixels inside the mask,
+ *     part[t] = fp64 sum, from 0.0, over the linear pixels e = t, t + 256, ... ascending of (double)v[e],  t = 0 .. 255;
+ *     sum = the halving tree over part (h = 128, 64, .. 1: part[t] += part[t + h] for t < h);
+ *     mean = (float)(sum / (double)count);   w[e] = v[e] - mean inside the mask (one fp32 subtraction), 0.0f outside;
+ *     q = the same partial sums and tree over (double)w[e] * (double)w[e];   norm = sqrtf((float)q), correctly rounded;
+ *     out[e] = w[e] / norm, the correctly rounded fp32 quotient; all zeros unless count > 0 and norm > 0.
+ *   The statistics are formed over the whole image whatever the output form.
+ * Output: pix == NULL: out [M, S, S].  Else pix is int32 [D] on the device, linear pixel indices (ascending in the callers'
+ * use), 1 <= D <= S*S: out[m * ldo + q] = the value at pixel pix[q] for q < D and 0.0f for q = D .. ldo-1; ldo >= D a
+ * multiple of 4.  src and out 16-byte aligned.  One workgroup per output, the source image staged in LDS.
+ *
+ * sprk_class_score: for Q [N, ldq] and B [Mb, ldb], row-major fp32, 16-byte aligned, ldq and ldb multiples of 4 and at
+ * least D, data taken to be finite:
+ *   s[n, m] = fmaf chain from 0.0f over d = 0 .. D-1 ascending of Q[n, d] * B[m, d]
+ * on v_mfma_f32_16x16x4_f32, one accumulator per score, K never split (the bytes do not depend on the tiling);
+ *   best_index[n] = the lowest m with s[n, m] == max over m of s[n, m] (int32 [N]),  best_score[n] = s[n, best_index[n]].
+ * Rows and columns of padding take no part: a row whose scores are all negative reports a negative best.  scores: NULL, or
+ * fp32 [N, lds] (lds >= Mb) that receives s[n, m] for m < Mb; columns Mb .. lds-1 are not written.
+ * 1 <= N; 1 <= Mb <= 65536; 4 <= D <= 16384, a multiple of 4.
+ *
+ * sprk_class_average: class sums in a fixed order.  members int32 [N]: particle indices grouped by class; offsets int32
+ * [K + 1]: class k's members are members[offsets[k] .. offsets[k+1] - 1] (offsets clamped to 0 .. N).  ang int32 [n_src] and
+ * shift int32 [n_src, 2]: each PARTICLE's angle index and shift.  Per class k with count = offsets[k+1] - offsets[k] > 0 and
+ * per pixel:
+ *   sum = 0.0f;  sum = sum + T(src[p], cs[ang[p]], shift[p]) over the members p in list order, one fp32 add each;
+ *   out[k] = sum * (1.0f / (float)count)                (the reciprocal rounded, then one multiplication);
+ * no mask and no normalisation.  A class with count <= 0 leaves out[k] untouched.  out [K, S, S] fp32, not src;
+ * 1 <= K <= 65535.  One workgroup per class and 256 pixels, the particles read straight from memory.
+ *
+ * All three: refused (SPRK_EINVAL, nothing launched): sizes outside the limits, unknown flags, a stride too small or not a
+ * multiple of 4, null or misaligned pointers.  One launch on `stream`, no workspace, no atomics, no host synchronisation. */
+#define SPRK_CLASS_MASK 1
+#define SPRK_CLASS_NORMALIZE 2
+int sprk_class_transform(const float *src, int n_src, int S, const int *idx, const int *ang, const int *shift, int M,
+                         const float *cs, int A_n, int radius, int flags, const int *pix, int D, int ldo, float *out,
+                         void *stream);
+int sprk_class_score(const float *Q, int ldq, int N, const float *B, int ldb, int Mb, int D, float *scores, long lds,
+                     float *best_score, int *best_index, void *stream);
+int sprk_class_average(const float *src, int n_src, int S, const int *ang, const int *shift, const float *cs, int A_n,
+                       const int *members, int N, const int *offsets, int K, float *out, void *stream);
+
 /* ---- tiled power spectra (`joint ctf`)-----------------------------------------------------
  * sprk_psd_tiles: the summed half-plane power spectrum of T x T tiles of ONE raw micrograph (raw as for sprk_ingest_bin:
  * [ny,nx] samples of mode 0 / 1 / 2 / 6, 16-byte aligned start; rows may be only itemsize-aligned).  T a multiple of 16 in

@@ -137,6 +137,11 @@ def _check_ctf(ns):
         check_astigmatism(MAX_ASTIGMATISM if ns.max_astigmatism is None else ns.max_astigmatism, ns.min_defocus)
 
 
+def _check_class2d(ns):
+    from .class2d import check_class2d_args
+    check_class2d_args(ns.classes, ns.angle_step, ns.max_shift, ns.radius, ns.iters)
+
+
 def _check_align(ns):
     from .align import check_align_args
     check_align_args(ns.align_size, ns.max_shift, ns.iters)
@@ -358,6 +363,28 @@ def build_parser():
                          "mean, found in up to 4 rounds (finite, > 0; 6 is recommended; off by default).  Works without "
                          "--gain, for gain-corrected movies that still have hot pixels")
     al.check = _check_align
+
+    c2_help = ("Reference-free 2-D class averages of extracted particles on the GPU: a multi-reference alignment over "
+               "in-plane angles and integer shifts that starts from one class and splits the largest classes until there "
+               "are K (replaces a first relion_refine / EMAN2 2-D classification run when the aim is to judge the picks).  "
+               "Reads the particles.star and the float32 stacks of `joint extract --scale 64` (or 128).  Not covered: CTF "
+               "weighting of the averages, soft (probabilistic) assignment, sub-pixel shifts, boxes that are not 64 or 128 "
+               "pixels.")
+    c2 = cmds.add_parser("class2d", help=c2_help, description=c2_help)
+    c2.add_argument("--particles", "-p", required=True, metavar="STAR",
+                    help="particles.star of `joint extract`; the {name}.mrcs stacks of _rlnImageName lie beside it")
+    c2.add_argument("--classes", "-k", type=int, required=True, metavar="K", help="number of classes (1..the particle count)")
+    c2.add_argument("--out", "-o", required=True,
+                    help="Directory for classes.mrcs (K float32 averages), particles_class2d.star (the input rows plus "
+                         "_rlnClassNumber, _rlnAnglePsi, _rlnOriginX, _rlnOriginY) and class2d.txt.")
+    c2.add_argument("--angle_step", type=float, default=5.0, metavar="A",
+                    help="in-plane angle step in degrees; 360 / A must be an integer in 1..720 (default 5)")
+    c2.add_argument("--max_shift", type=int, default=3, metavar="R", help="shifts searched, +-R pixels (1..31, default 3)")
+    c2.add_argument("--radius", type=int, metavar="P",
+                    help="mask radius in pixels (default and at most S/2 - R - 2 for a box of S pixels)")
+    c2.add_argument("--iters", type=int, default=8, metavar="I",
+                    help="iterations per level at most (default 8, at least 2; a level stops when no assignment changes)")
+    c2.check = _check_class2d
     return parser
 
 
@@ -471,6 +498,18 @@ def run_align(args):
     return res
 
 
+def run_class2d(args, parser):
+    import json
+    from . import class2d
+    try:
+        res = class2d.class2d_dataset(args["particles"], args["out"], args["classes"], angle_step=args["angle_step"],
+                                      max_shift=args["max_shift"], radius=args.get("radius"), iters=args["iters"])
+    except ValueError as e:                      # what only the stacks can tell: their side, their number
+        parser.error(str(e))
+    print(json.dumps(res))
+    return res
+
+
 def start(argv=None):
     import sys
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -488,4 +527,6 @@ def start(argv=None):
         return run_ctf(args)
     if args["command"] == "align":
         return run_align(args)
+    if args["command"] == "class2d":
+        return run_class2d(args, parser)
     return run_eval(args)

@@ -984,6 +984,160 @@ def _align_warp_fake(src, cy, cx, y, first):
 _register("align_warp", "(Tensor src, float[] cy, float[] cx, Tensor(a!) y, bool first) -> ()", _align_warp, _align_warp_fake)
 
 
+# ---- reference-free 2-D classification (class2d.py: csrc/class2d.hip) ----------------------------------------------------------
+CLASS_MAX_SIDE = 128                             # sprk_class_transform / _average: S even, at most this
+CLASS_MAX_ANGLES = 720                           # rows of the cos / sin table at most
+CLASS_MASK, CLASS_NORMALIZE = 1, 2               # SPRK_CLASS_*
+CLASS_MAX_BANK = 65536                           # sprk_class_score: bank rows at most
+CLASS_MAX_D = 16384                              # ... and columns (a multiple of 4, at least 4)
+
+
+def _is_i32(t, shape, dev):
+    return t.dtype == torch.int32 and tuple(t.shape) == tuple(shape) and t.device == dev
+
+
+def _class_images(who, src, cs):
+    if src.dtype != torch.float32 or src.dim() != 3 or src.shape[1] != src.shape[2] or src.shape[0] < 1:
+        raise _lib.SprkError("%s: src must be float32 [n, S, S], got %s %s" % (who, src.dtype, tuple(src.shape)))
+    S = src.shape[1]
+    if not (2 <= S <= CLASS_MAX_SIDE and S % 2 == 0):
+        raise _lib.SprkError("%s: images of side %d (even, 2..%d)" % (who, S, CLASS_MAX_SIDE))
+    if cs.dtype != torch.float32 or cs.dim() != 2 or cs.shape[1] != 2 or not 1 <= cs.shape[0] <= CLASS_MAX_ANGLES \
+            or cs.device != src.device:
+        raise _lib.SprkError("%s: cs must be float32 [A_n, 2] (cos, sin; 1 <= A_n <= %d) on %s, got %s %s on %s"
+                             % (who, CLASS_MAX_ANGLES, src.device, cs.dtype, tuple(cs.shape), cs.device))
+    return int(src.shape[0]), int(S), int(cs.shape[0])
+
+
+def _class_transform_check(src, idx, ang, shift, cs, radius, flags, pix, out):
+    n_src, S, A_n = _class_images("class_transform", src, cs)
+    M = idx.shape[0] if idx.dim() == 1 else 0
+    if M < 1 or not (_is_i32(idx, (M,), src.device) and _is_i32(ang, (M,), src.device) and _is_i32(shift, (M, 2), src.device)):
+        raise _lib.SprkError("class_transform: idx and ang must be int32 [M] and shift int32 [M, 2] on %s (M >= 1), got %s, %s, "
+                             "%s" % (src.device, tuple(idx.shape), tuple(ang.shape), tuple(shift.shape)))
+    if flags & ~(CLASS_MASK | CLASS_NORMALIZE):
+        raise _lib.SprkError("class_transform: unknown flags 0x%x" % flags)
+    if flags and not 0 <= radius <= S:
+        raise _lib.SprkError("class_transform: mask radius %d (0..%d)" % (radius, S))
+    if out.dtype != torch.float32 or out.device != src.device:
+        raise _lib.SprkError("class_transform: out must be float32 on %s, got %s on %s" % (src.device, out.dtype, out.device))
+    if pix is None:
+        if tuple(out.shape) != (M, S, S):
+            raise _lib.SprkError("class_transform: out must be [%d, %d, %d], got %s" % (M, S, S, tuple(out.shape)))
+        return n_src, S, A_n, M, 0, 0
+    D = pix.shape[0] if pix.dim() == 1 else 0
+    if not (1 <= D <= S * S and _is_i32(pix, (D,), src.device)):
+        raise _lib.SprkError("class_transform: pix must be int32 [D] on %s with 1 <= D <= S*S = %d, got %s %s"
+                             % (src.device, S * S, pix.dtype, tuple(pix.shape)))
+    if out.dim() != 2 or out.shape[0] != M or out.shape[1] < D or out.shape[1] % 4:
+        raise _lib.SprkError("class_transform: the packed out must be [%d, ldo] with ldo a multiple of 4, at least D = %d, got "
+                             "%s" % (M, D, tuple(out.shape)))
+    return n_src, S, A_n, M, D, int(out.shape[1])
+
+
+def _class_transform(src, idx, ang, shift, cs, radius, flags, pix, out):
+    """src float32 [n, S, S]; idx, ang int32 [M]; shift int32 [M, 2] (dy, dx); cs float32 [A_n, 2]: out[m] = the rigid
+    transform of src[idx[m]] by the angle cs[ang[m]] and its shift, bilinear, zero beyond the edges; flags CLASS_MASK /
+    CLASS_NORMALIZE with the mask ``radius``; out float32 [M, S, S], or with pix (int32 [D] linear pixel indices) the packed
+    [M, ldo], columns D .. ldo-1 zeros (sprk_class_transform)."""
+    n_src, S, A_n, M, D, ldo = _class_transform_check(src, idx, ang, shift, cs, radius, flags, pix, out)
+    for t in (src, idx, ang, shift, cs, out) + (() if pix is None else (pix,)):
+        if not t.is_contiguous():
+            raise _lib.SprkError("class_transform: every tensor must be contiguous")
+    check(_lib.lib().sprk_class_transform(_p(src), n_src, S, _p(idx), _p(ang), _p(shift), M, _p(cs), A_n, int(radius),
+                                          int(flags), _p(pix), D, ldo, _p(out), _stream(src)), "sprk_class_transform")
+
+
+def _class_transform_fake(src, idx, ang, shift, cs, radius, flags, pix, out):
+    _class_transform_check(src, idx, ang, shift, cs, radius, flags, pix, out)
+
+
+_register("class_transform", "(Tensor src, Tensor idx, Tensor ang, Tensor shift, Tensor cs, int radius, int flags, Tensor? pix, "
+          "Tensor(a!) out) -> ()", _class_transform, _class_transform_fake)
+
+
+def _class_score_check(Q, B, D, scores, best_score, best_index):
+    if Q.dtype != torch.float32 or Q.dim() != 2 or B.dtype != torch.float32 or B.dim() != 2 or B.device != Q.device:
+        raise _lib.SprkError("class_score: Q [N, ldq] and B [Mb, ldb] must be float32 on one device, got %s %s and %s %s"
+                             % (Q.dtype, tuple(Q.shape), B.dtype, tuple(B.shape)))
+    N, ldq = Q.shape
+    Mb, ldb = B.shape
+    if not (N >= 1 and 1 <= Mb <= CLASS_MAX_BANK and 4 <= D <= CLASS_MAX_D and D % 4 == 0):
+        raise _lib.SprkError("class_score: %d rows against a bank of %d with D = %d (N >= 1, 1 <= Mb <= %d, D a multiple of 4 in "
+                             "4..%d)" % (N, Mb, D, CLASS_MAX_BANK, CLASS_MAX_D))
+    if ldq < D or ldq % 4 or ldb < D or ldb % 4:
+        raise _lib.SprkError("class_score: row strides %d and %d (multiples of 4, at least D = %d)" % (ldq, ldb, D))
+    if best_score.dtype != torch.float32 or tuple(best_score.shape) != (N,) or best_score.device != Q.device \
+            or not _is_i32(best_index, (N,), Q.device):
+        raise _lib.SprkError("class_score: best_score must be float32 [%d] and best_index int32 [%d] on %s"
+                             % (N, N, Q.device))
+    if scores is not None and (scores.dtype != torch.float32 or scores.dim() != 2 or scores.shape[0] != N
+                               or scores.shape[1] < Mb or scores.device != Q.device):
+        raise _lib.SprkError("class_score: scores must be float32 [%d, at least %d] on %s, got %s %s"
+                             % (N, Mb, Q.device, scores.dtype, tuple(scores.shape)))
+    return int(N), int(ldq), int(Mb), int(ldb)
+
+
+def _class_score(Q, B, D, scores, best_score, best_index):
+    """Q float32 [N, ldq], B float32 [Mb, ldb] (columns D .. ld-1 zeros): s[n, m] = the fmaf chain over d < D of Q[n, d] *
+    B[m, d] on MFMA; best_score[n] its maximum over m, best_index[n] the lowest m that attains it; scores (or None) receives
+    s in its columns 0 .. Mb-1 (sprk_class_score)."""
+    N, ldq, Mb, ldb = _class_score_check(Q, B, D, scores, best_score, best_index)
+    for t in (Q, B, best_score, best_index) + (() if scores is None else (scores,)):
+        if not t.is_contiguous():
+            raise _lib.SprkError("class_score: every tensor must be contiguous")
+    check(_lib.lib().sprk_class_score(_p(Q), ldq, N, _p(B), ldb, Mb, int(D), _p(scores),
+                                      0 if scores is None else int(scores.shape[1]), _p(best_score), _p(best_index),
+                                      _stream(Q)), "sprk_class_score")
+
+
+def _class_score_fake(Q, B, D, scores, best_score, best_index):
+    _class_score_check(Q, B, D, scores, best_score, best_index)
+
+
+_register("class_score", "(Tensor Q, Tensor B, int D, Tensor(a!)? scores, Tensor(b!) best_score, Tensor(c!) best_index) -> ()",
+          _class_score, _class_score_fake)
+
+
+def _class_average_check(src, ang, shift, cs, members, offsets, out):
+    n_src, S, A_n = _class_images("class_average", src, cs)
+    if not (_is_i32(ang, (n_src,), src.device) and _is_i32(shift, (n_src, 2), src.device)):
+        raise _lib.SprkError("class_average: ang must be int32 [%d] and shift int32 [%d, 2] on %s (one per particle), got %s "
+                             "and %s" % (n_src, n_src, src.device, tuple(ang.shape), tuple(shift.shape)))
+    N = members.shape[0] if members.dim() == 1 else 0
+    K = offsets.shape[0] - 1 if offsets.dim() == 1 else 0
+    if not (N >= 1 and 1 <= K <= 65535 and _is_i32(members, (N,), src.device) and _is_i32(offsets, (K + 1,), src.device)):
+        raise _lib.SprkError("class_average: members must be int32 [N >= 1] and offsets int32 [K + 1] (1 <= K <= 65535) on %s, "
+                             "got %s %s and %s %s" % (src.device, members.dtype, tuple(members.shape), offsets.dtype,
+                                                      tuple(offsets.shape)))
+    if out.dtype != torch.float32 or tuple(out.shape) != (K, S, S) or out.device != src.device:
+        raise _lib.SprkError("class_average: out must be float32 [%d, %d, %d] on %s, got %s %s"
+                             % (K, S, S, src.device, out.dtype, tuple(out.shape)))
+    return n_src, S, A_n, int(N), int(K)
+
+
+def _class_average(src, ang, shift, cs, members, offsets, out):
+    """src float32 [n, S, S]; ang int32 [n], shift int32 [n, 2]: each particle's angle index and shift; members int32 [N]
+    grouped by class, offsets int32 [K + 1]: out[k] = the fp32 sum, in list order, of the class's transformed members times
+    1 / count; an empty class keeps what out[k] holds (sprk_class_average)."""
+    n_src, S, A_n, N, K = _class_average_check(src, ang, shift, cs, members, offsets, out)
+    for t in (src, ang, shift, cs, members, offsets, out):
+        if not t.is_contiguous():
+            raise _lib.SprkError("class_average: every tensor must be contiguous")
+    if src.data_ptr() == out.data_ptr():
+        raise _lib.SprkError("class_average: out must not be src")
+    check(_lib.lib().sprk_class_average(_p(src), n_src, S, _p(ang), _p(shift), _p(cs), A_n, _p(members), N, _p(offsets), K,
+                                        _p(out), _stream(src)), "sprk_class_average")
+
+
+def _class_average_fake(src, ang, shift, cs, members, offsets, out):
+    _class_average_check(src, ang, shift, cs, members, offsets, out)
+
+
+_register("class_average", "(Tensor src, Tensor ang, Tensor shift, Tensor cs, Tensor members, Tensor offsets, Tensor(a!) out) "
+          "-> ()", _class_average, _class_average_fake)
+
+
 # ---- particle extraction (extract.py: raw MRC samples + pick coordinates -> normalised particle stack) ------------------------
 EXTRACT_MAX_BOX = 1024                           # sprk_extract_boxes: the int64 sum of squares stays below 2^63 up to here
 EXTRACT_NORMALIZE, EXTRACT_INVERT = 1, 2         # SPRK_EXTRACT_*
