@@ -1,9 +1,10 @@
 // Whole-frame motion correction of movies: sprk_align_corr and sprk_align_accumulate (`joint align`).
 //
-// Both entry points are fp32 GEMMs on v_mfma_f32_16x16x4_f32 by the pipeline of mfma_stage.h (its K loop, multiply and
-// accumulator walk; a kernel here is its index set-up, two loader descriptions and an epilogue), and both keep its rule
-// of the bits: one accumulator per output element, its K positions in ascending order, one rounding per product, K never
-// split, so every tiling gives the bytes of the contract's fmaf chain (tests/align_model.py).
+// Both entry points are fp32 GEMMs on v_mfma_f32_16x16x4_f32 by the pipeline of mfma_stage.h (the correlation on its K
+// loop, multiply and accumulator walk with two loaders of its own; the two accumulate kernels each one call of a stage body
+// and a store), and both keep its rule of the bits: one accumulator per output element, its K positions in ascending
+// order, one rounding per product, K never split, so every tiling gives the bytes of the contract's fmaf chain
+// (tests/align_model.py).
 //
 // sprk_align_corr: the cross-correlation window of every reduced frame a_f [Sy, Sx] against its reference r_f, both taken
 // as periodic, for the row shifts i - R and the column shifts j - R, |shift| <= R:
@@ -25,16 +26,17 @@
 //   y[i, j] = fmaf chain over r = 0 .. ny-1 ascending of My[i, r] * U[r, j],
 //             from 0.0f if `first`, else from the y[i, j] already there                         (stage 2).
 // Storing and reloading an fp32 accumulator is lossless, so Z calls give the bits of ONE chain over (frame, r) ascending.
-// The kernels are resample.hip's two stages with the anchor as a kernel argument (no device read, nothing written back)
-// and the accumulators of stage 2 loaded from y; no anchor add and no range.  Padding as there: every padded K position is
+// The kernels call the two stage bodies that resample.hip's call (mfma_stage.h: sample_rows_body, kmajor_rows_body), with
+// the anchor as a kernel argument (no device read, nothing written back) and the accumulators of stage 2 loaded from y; no
+// anchor add and no range.  Padding as there: every padded K position is
 // a zero formed in registers on BOTH operands (the workspace is uninitialised memory), and with `first` y is not read.
 // Two launches on the caller's stream, no host synchronisation, no atomics.
 #include <cstdint>
-#include <limits>
 #include <type_traits>
 
 #include "common.h"
 #include "mfma_stage.h"
+#include "mrc_host.h"
 
 namespace {
 
@@ -43,7 +45,6 @@ constexpr int kMaxShift = 31;                    // R at most: the 63 x 63 windo
 constexpr int kMaxFrames = 65535;                // the grid's second dimension
 constexpr int kRowsThreads = 256;                // accumulate, stage 1: four waves
 constexpr int kRowsTile = 64;                    // ... on 64 rows x 64 columns of U
-constexpr int kRowsTN = kRowsTile / 16;
 
 // ---- the operands of the correlation --------------------------------------------------------------------------------------
 // Both loaders take K position c0 = y' * Sx + x0 (a multiple of kKC; Sx is one as well) and keep mfma_stage.h's rule:
@@ -150,25 +151,10 @@ template <typename T>
 __global__ __launch_bounds__(kRowsThreads) void accumulate_rows_kernel(const T *__restrict__ raw, int ny, int nx, int bx,
                                                                        const float *__restrict__ mx, int ldmx, T first,
                                                                        float *__restrict__ u, int ldu) {
-    __shared__ __align__(16) float As[kRowsTile * kLd];        // [64 rows of D][kLd]
-    __shared__ __align__(16) float Ms[kRowsTile * kLd];        // [64 rows of Mx][kLd]
-    const int r0 = blockIdx.y * kRowsTile, j0 = blockIdx.x * kRowsTile;
-    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
-    const int Kp4 = (nx + 3) & ~3;
-
-    const SampleRows<T, kRowsThreads> d{raw, nx, ny, nx, r0, first, lds_ptr(As)};
-    const MatrixRows<kRowsTile, kRowsThreads, RowsFrom> m{mx, ldmx, bx, Kp4, nx, RowsFrom{j0, bx}, lds_ptr(Ms)};
-    const bool active = r0 + wave * 16 < ny;                   // wave-uniform
-    f32x4 acc[kRowsTN];
-#pragma unroll
-    for (int t = 0; t < kRowsTN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    k_loop(Kp4, d, m, active,
-           [&](int ks) { multiply<BtRows, true>(acc, a_frag(As, wave, lr, lk), BtRows::frag(Ms, lr, lk), ks); });
-    if (active) {
-        for_each_output(acc, r0, j0, wave, lk, lr, [&](int r, int j, float v) {
-            if (r < ny && j < ldu) u[(long)r * ldu + j] = v;
-        });
-    }
+    sample_rows_body<true>(raw, nx, ny, nx, first, mx, ldmx, bx, blockIdx.y * kRowsTile, blockIdx.x * kRowsTile,
+                           [=](int r, int j, float v) {
+                               if (r < ny && j < ldu) u[(long)r * ldu + j] = v;
+                           });
 }
 
 // ---- accumulate, stage 2: y[i0 .. i0+16*WM-1, j0 .. j0+16*TN-1] (+)= My U ----------------------------------------------------
@@ -177,39 +163,13 @@ template <int WM, int TN>
 __global__ __launch_bounds__(64 * WM) void accumulate_cols_kernel(const float *__restrict__ my, int ldmy,
                                                                   const float *__restrict__ u, int ldu, int ny, int by,
                                                                   int bx, float *__restrict__ y, int first) {
-    constexpr int kThreads = 64 * WM, kRows = 16 * WM, W = 16 * TN;
-    using URows = KMajorRows<W, kThreads, false>;
-    __shared__ __align__(16) float As[kRows * kLd];            // [rows of My][kLd]
-    __shared__ __align__(16) float Bs[kKC * URows::kLdb];      // [rows of U = K][kLdb]
-    const int i0 = blockIdx.y * kRows, j0 = blockIdx.x * W;
-    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
-    const int Kp4 = (ny + 3) & ~3;
-
-    const MatrixRows<kRows, kThreads, RowsFrom> a{my, ldmy, by, Kp4, ny, RowsFrom{i0, by}, lds_ptr(As)};
-    const URows b{u, ldu, ny, j0, ldu, lds_ptr(Bs)};
-    const bool active = i0 + wave * 16 < by;                   // wave-uniform
-    f32x4 acc[TN];
-#pragma unroll
-    for (int t = 0; t < TN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    if (active && !first) {                                    // the chain goes on where the frame before left it
-#pragma unroll
-        for (int t = 0; t < TN; ++t)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int i = i0 + wave * 16 + lk * 4 + g, j = j0 + t * 16 + lr;
-                if (i < by && j < bx) acc[t][g] = y[(long)i * bx + j];
-            }
-    }
-    k_loop(Kp4, a, b, active,
-           [&](int ks) { multiply<KMajor<W>, true>(acc, a_frag(As, wave, lr, lk), KMajor<W>::frag(Bs, lr, lk), ks); });
-    if (active) {
-        for_each_output(acc, i0, j0, wave, lk, lr, [&](int i, int j, float v) {
-            if (i < by && j < bx) y[(long)i * bx + j] = v;
-        });
-    }
+    // the chain goes on where the frame before left it
+    kmajor_rows_body<WM, TN>(my, ldmy, by, ny, u, ldu, bx, first ? nullptr : y, blockIdx.y * 16 * WM, blockIdx.x * 16 * TN,
+                             [=](int i, int j, float v) {
+                                 if (i < by && j < bx) y[(long)i * bx + j] = v;
+                             });
 }
 
-inline int ldu_of(int bx) { return (bx + 3) & ~3; }
 inline bool sizes_ok(int ny, int nx, int by, int bx) {
     return 2 <= by && by <= ny && ny <= kMaxSide && 2 <= bx && bx <= nx && nx <= kMaxSide;
 }
@@ -218,14 +178,14 @@ template <typename T>
 int launch_rows(const void *raw, int ny, int nx, int bx, const float *mx, int ldmx, float anchor, float *u, hipStream_t s) {
     const dim3 grid(sprk::cdiv(bx, kRowsTile), sprk::cdiv(ny, kRowsTile));
     hipLaunchKernelGGL(accumulate_rows_kernel<T>, grid, dim3(kRowsThreads), 0, s, (const T *)raw, ny, nx, bx, mx, ldmx,
-                       (T)anchor, u, ldu_of(bx));
+                       (T)anchor, u, sprk::roundup4(bx));
     return sprk::check_launch("align_accumulate (rows)");
 }
 
 template <int WM, int TN>
 int launch_cols(const float *my, int ldmy, const float *u, int ny, int by, int bx, float *y, int first, hipStream_t s) {
     const dim3 grid(sprk::cdiv(bx, 16 * TN), sprk::cdiv(by, 16 * WM));
-    hipLaunchKernelGGL((accumulate_cols_kernel<WM, TN>), grid, dim3(64 * WM), 0, s, my, ldmy, u, ldu_of(bx), ny, by, bx, y,
+    hipLaunchKernelGGL((accumulate_cols_kernel<WM, TN>), grid, dim3(64 * WM), 0, s, my, ldmy, u, sprk::roundup4(bx), ny, by, bx, y,
                        first);
     return sprk::check_launch("align_accumulate (columns)");
 }
@@ -236,13 +196,6 @@ int launch_corr(const float *a, const float *r, long r_stride, int Z, int Sy, in
     const dim3 grid(sprk::cdiv(n, 16 * WM) * sprk::cdiv(n, 16 * TN), Z);
     hipLaunchKernelGGL((align_corr_kernel<WM, TN>), grid, dim3(64 * WM), 0, s, a, r, r_stride, Sy, Sx, R, cc);
     return sprk::check_launch("align_corr");
-}
-
-// the anchor of an integer mode is a sample value: the kernel subtracts it in integers
-template <typename T>
-bool anchor_is_sample(float anchor) {
-    return anchor >= (float)std::numeric_limits<T>::min() && anchor <= (float)std::numeric_limits<T>::max() &&
-           (float)(T)anchor == anchor;
 }
 
 }  // namespace
@@ -282,43 +235,32 @@ int sprk_align_corr(const float *a, const float *r, long r_stride, int Z, int Sy
 
 size_t sprk_align_accumulate_ws_bytes(int ny, int nx, int by, int bx) {
     if (!sizes_ok(ny, nx, by, bx)) return 0;
-    return (size_t)ny * ldu_of(bx) * sizeof(float);
+    return (size_t)ny * sprk::roundup4(bx) * sizeof(float);
 }
 
 int sprk_align_accumulate(const void *raw, int mode, int ny, int nx, int by, int bx, const float *my, int ldmy,
                           const float *mx, int ldmx, float anchor, float *y, int first, void *ws, size_t ws_bytes,
                           void *stream) {
-    SPRK_REQUIRE(mode == SPRK_MRC_INT8 || mode == SPRK_MRC_INT16 || mode == SPRK_MRC_FLOAT32 || mode == SPRK_MRC_UINT16,
-                 "align_accumulate: unsupported MRC mode %d (0, 1, 2 and 6 are)", mode);
+    SPRK_REQUIRE_MRC_MODE("align_accumulate", mode);
     SPRK_REQUIRE(sizes_ok(ny, nx, by, bx),
                  "align_accumulate: a %dx%d frame resampled to %dx%d (2 <= by <= ny <= %d and 2 <= bx <= nx <= %d)", ny, nx, by,
                  bx, kMaxSide, kMaxSide);
-    SPRK_REQUIRE(ldmy >= ((ny + 3) & ~3) && ldmy % 4 == 0,
+    SPRK_REQUIRE(ldmy >= sprk::roundup4(ny) && ldmy % 4 == 0,
                  "align_accumulate: row stride ldmy %d of the row matrix (a multiple of 4, at least roundup(ny, 4) = %d)", ldmy,
-                 (ny + 3) & ~3);
-    SPRK_REQUIRE(ldmx >= ((nx + 3) & ~3) && ldmx % 4 == 0,
+                 sprk::roundup4(ny));
+    SPRK_REQUIRE(ldmx >= sprk::roundup4(nx) && ldmx % 4 == 0,
                  "align_accumulate: row stride ldmx %d of the column matrix (a multiple of 4, at least roundup(nx, 4) = %d)",
-                 ldmx, (nx + 3) & ~3);
-    SPRK_REQUIRE(mode == SPRK_MRC_INT8    ? anchor_is_sample<int8_t>(anchor)
-                 : mode == SPRK_MRC_INT16 ? anchor_is_sample<int16_t>(anchor)
-                 : mode == SPRK_MRC_UINT16 ? anchor_is_sample<uint16_t>(anchor)
-                                           : anchor == 0.0f,
+                 ldmx, sprk::roundup4(nx));
+    SPRK_REQUIRE(anchor_ok(mode, anchor),
                  "align_accumulate: anchor %g (a sample value of mode %d; 0 for float32)", (double)anchor, mode);
     SPRK_REQUIRE(raw && my && mx && y, "align_accumulate: null pointer");
-    SPRK_REQUIRE(((uintptr_t)raw & 15) == 0 && ((uintptr_t)my & 15) == 0 && ((uintptr_t)mx & 15) == 0 &&
-                     ((uintptr_t)y & 15) == 0 && ((uintptr_t)ws & 15) == 0,
+    SPRK_REQUIRE(sprk::aligned16(raw, my, mx, y, ws),
                  "align_accumulate: the sample buffer, the matrices, the sum and the workspace must start 16-byte aligned");
     if (int rc = sprk::check_ws("align_accumulate", ws, ws_bytes, sprk_align_accumulate_ws_bytes(ny, nx, by, bx))) return rc;
     hipStream_t s = (hipStream_t)stream;
     float *u = (float *)ws;
-    int rc;
-    switch (mode) {
-        case SPRK_MRC_INT8: rc = launch_rows<int8_t>(raw, ny, nx, bx, mx, ldmx, anchor, u, s); break;
-        case SPRK_MRC_INT16: rc = launch_rows<int16_t>(raw, ny, nx, bx, mx, ldmx, anchor, u, s); break;
-        case SPRK_MRC_FLOAT32: rc = launch_rows<float>(raw, ny, nx, bx, mx, ldmx, anchor, u, s); break;
-        default: rc = launch_rows<uint16_t>(raw, ny, nx, bx, mx, ldmx, anchor, u, s); break;
-    }
-    if (rc) return rc;
+    if (int rc = dispatch_mrc(mode, [&](auto t) { return launch_rows<decltype(t)>(raw, ny, nx, bx, mx, ldmx, anchor, u, s); }))
+        return rc;
     // 64 x 64 tiles on four waves, unless they would leave compute units without a workgroup
     return (long)sprk::cdiv(by, 64) * sprk::cdiv(bx, 64) < sprk::num_cus()
                ? launch_cols<2, 2>(my, ldmy, u, ny, by, bx, y, first, s)

@@ -19,27 +19,28 @@
 // hold anything.
 //
 // Two launches per entry point on the caller's stream; no host synchronisation, no atomics.
-//   spectrum_rows_kernel<T> (stage 1) and synthesize_out_kernel (stage 4): the pipeline of mfma_stage.h, one workgroup of
-//     four waves per 64 x 64 outputs, a wave on 16 rows with four accumulators; both operands in chunks of 64 K positions
-//     through LDS, two chunks fetched ahead from clamped addresses.
-//   paired_cols_kernel<kStage> (stages 2 and 3): the paired form of that pipeline, a wave holds the accumulators of rows u
-//     and M + u of its 16 rows (A and B, Zr and Zi), so that the complex multiply-add of stage 2 is its epilogue.
+//   spectrum_rows_kernel<T> (stage 1) and synthesize_out_kernel (stage 4): sample_rows_body and matrix_rows_body of
+//     mfma_stage.h (a kernel is its index set-up, one call of a body and its store), one workgroup of four waves per
+//     64 x 64 outputs, a wave on 16 rows with four accumulators; both operands in chunks of 64 K positions through LDS, two
+//     chunks fetched ahead from clamped addresses.
+//   paired_cols_kernel<kStage> (stages 2 and 3): the paired form of that pipeline (paired_rows_body), a wave holds the
+//     accumulators of rows u and M + u of its 16 rows (A and B, Zr and Zi), so that the complex multiply-add of stage 2 is
+//     its epilogue.
 //
 // Compiled with -ffp-contract=off (Makefile): the four fmaf of the epilogue are the operations the contract names and
 // nothing else.
 #include <cstdint>
-#include <limits>
 #include <type_traits>
 
 #include "common.h"
 #include "mfma_stage.h"
+#include "mrc_host.h"
 
 namespace {
 
 constexpr int kMaxSide = 16384;                  // a side of a frame at most: V's 2 ny * roundup(Hs, 4) stays below 2^31
 constexpr int kThreads = 256;                    // four waves, every kernel
 constexpr int kTile = 64;                        // 64 x 64 outputs per workgroup, every stage
-constexpr int kTN = kTile / 16;
 
 struct Geo {
     int ny, nx, by, bx, Hs, Ku;
@@ -52,29 +53,9 @@ struct Geo {
 template <typename T>
 __global__ __launch_bounds__(kThreads) void spectrum_rows_kernel(const T *__restrict__ raw, Geo g, T first,
                                                                  const float *__restrict__ w1, float *__restrict__ v_out) {
-    __shared__ __align__(16) float As[kTile * kLd];            // [64 rows of D][kLd]
-    __shared__ __align__(16) float Ms[kTile * kLd];            // [64 rows of W1][kLd]
-    const int ny = g.ny, Hs = g.Hs, N = 2 * g.Hs, Kp = g.ld1;
-    const int r0 = blockIdx.y * kTile, q0 = blockIdx.x * kTile;
-    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
-
     // rows and columns past the frame are fetched from its last row / column; rows of W1 past 2Hs are staged as zeros
-    const SampleRows<T, kThreads> d{raw, g.nx, ny, g.nx, r0, first, lds_ptr(As)};
-    const MatrixRows<kTile, kThreads, RowsFrom> m{w1, g.ld1, N, g.ld1, g.nx, RowsFrom{q0, N}, lds_ptr(Ms)};
-    const bool active = r0 + wave * 16 < ny;                   // wave-uniform
-    f32x4 acc[kTN];
-#pragma unroll
-    for (int t = 0; t < kTN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    k_loop(Kp, d, m, active,
-           [&](int ks) { multiply<BtRows, true>(acc, a_frag(As, wave, lr, lk), BtRows::frag(Ms, lr, lk), ks); });
-    if (active) {
-        for_each_output(acc, r0, q0, wave, lk, lr, [&](int r, int q, float u) {
-            // the sine half goes below the cosine half
-            const int part = q >= Hs;
-            float *p = v_out + (long)(part * ny + r) * g.ldv + (q - part * Hs);
-            if (r < ny && q < N) *p = u;
-        });
-    }
+    sample_rows_body<true>(raw, g.nx, g.ny, g.nx, first, w1, g.ld1, 2 * g.Hs, blockIdx.y * kTile, blockIdx.x * kTile,
+                           [=](int r, int q, float u) { store_v_split(v_out, g.ldv, g.ny, g.Hs, r, q, u); });
 }
 
 // ---- stages 2 and 3: rows u0 .. and M + u0 .. of W times the K-major operand ---------------------------------------------
@@ -85,82 +66,49 @@ template <int kStage>
 __global__ __launch_bounds__(kThreads) void paired_cols_kernel(Geo g, const float *__restrict__ w,
                                                                const float *__restrict__ b_in, const float *__restrict__ gf,
                                                                int first, float *__restrict__ c_out) {
-    using BRows = KMajorRows<kTile, kThreads, true>;
-    __shared__ __align__(16) float As[2 * kTile * kLd];        // [64 rows u, then 64 rows M + u][kLd]
-    __shared__ __align__(16) float Bs[kKC * BRows::kLdb];      // [rows of the operand = K][kLdb]
     const int Hs = g.Hs, ldv = g.ldv;
     const int M = kStage == 2 ? g.Ku : g.by, K = kStage == 2 ? 2 * g.ny : 2 * g.Ku, ldw = kStage == 2 ? g.ld2 : g.ld3;
-    const int Kp = (K + 3) & ~3;
-    const int u0 = blockIdx.y * kTile, v0 = blockIdx.x * kTile;
-    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
-
     // A: rows u and M + u of W, the K positions at or past K staged as zeros.  B: columns Hs .. ldv-1 of the operand were
     // never written: staged as zeros, like every row at or past K
-    const MatrixRows<2 * kTile, kThreads, RowPairs> a{w, ldw, 2 * M, ldw, K, RowPairs{u0, M}, lds_ptr(As)};
-    const BRows b{b_in, ldv, K, v0, Hs, lds_ptr(Bs)};
-    const bool active = u0 + wave * 16 < M;                    // wave-uniform
-    f32x4 re[kTN], im[kTN];                                    // A and B, Zr and Zi
-#pragma unroll
-    for (int t = 0; t < kTN; ++t) re[t] = im[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    k_loop(Kp, a, b, active, [&](int ks) {
-        multiply_pair<KMajor<kTile>>(re, im, a_frag(As, wave, lr, lk), KMajor<kTile>::frag(Bs, lr, lk), ks);
-    });
-    if (active) {
-        for_each_output(re, im, u0, v0, wave, lk, lr, [&](int u, int v, float x, float y) {
+    paired_rows_body(w, ldw, M, K, b_in, ldv, Hs, blockIdx.y * kTile, blockIdx.x * kTile, [=](int u, int v, float x, float y) {
+        if constexpr (kStage == 2) {
             if (u < M && v < Hs) {
-                if constexpr (kStage == 2) {
-                    const long at_re = (long)u * ldv + v, at_im = (long)(M + u) * ldv + v;
-                    const float gr = gf[at_re], gi = gf[at_im];
-                    float fr = 0.0f, fi = 0.0f;
-                    if (!first) {
-                        fr = c_out[at_re];
-                        fi = c_out[at_im];
-                    }
-                    c_out[at_re] = __fmaf_rn(x, gr, __fmaf_rn(-y, gi, fr));
-                    c_out[at_im] = __fmaf_rn(x, gi, __fmaf_rn(y, gr, fi));
-                } else {
-                    c_out[(long)u * g.ldz + v] = x;
-                    c_out[(long)u * g.ldz + Hs + v] = y;
+                const long at_re = (long)u * ldv + v, at_im = (long)(M + u) * ldv + v;
+                const float gr = gf[at_re], gi = gf[at_im];
+                float fr = 0.0f, fi = 0.0f;
+                if (!first) {
+                    fr = c_out[at_re];
+                    fi = c_out[at_im];
                 }
+                c_out[at_re] = __fmaf_rn(x, gr, __fmaf_rn(-y, gi, fr));
+                c_out[at_im] = __fmaf_rn(x, gi, __fmaf_rn(y, gr, fi));
             }
-        });
-    }
+        } else {
+            store_zr_zi(c_out, g.ldz, M, Hs, u, v, x, y);
+        }
+    });
 }
 
 // ---- stage 4: Y rows i0 .., columns j0 .. ---------------------------------------------------------------------------------
 // grid (ceil(bx / 64), ceil(by / 64))
 __global__ __launch_bounds__(kThreads) void synthesize_out_kernel(Geo g, const float *__restrict__ z_in,
                                                                   const float *__restrict__ w4, float *__restrict__ out) {
-    __shared__ __align__(16) float As[kTile * kLd];            // [64 rows of Z][kLd]
-    __shared__ __align__(16) float Ms[kTile * kLd];            // [64 rows of W4][kLd]
-    const int by = g.by, bx = g.bx, K = 2 * g.Hs, Kp = g.ldz;
-    const int i0 = blockIdx.y * kTile, j0 = blockIdx.x * kTile;
-    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
-
+    const int by = g.by, bx = g.bx;
     // rows of Z at or past by, rows of W4 at or past bx and the K positions at or past 2Hs are staged as zeros
-    const MatrixRows<kTile, kThreads, RowsFrom> z{z_in, g.ldz, by, g.ldz, K, RowsFrom{i0, by}, lds_ptr(As)};
-    const MatrixRows<kTile, kThreads, RowsFrom> m{w4, g.ldz, bx, g.ldz, K, RowsFrom{j0, bx}, lds_ptr(Ms)};
-    const bool active = i0 + wave * 16 < by;                   // wave-uniform
-    f32x4 acc[kTN];
-#pragma unroll
-    for (int t = 0; t < kTN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    k_loop(Kp, z, m, active,
-           [&](int ks) { multiply<BtRows, true>(acc, a_frag(As, wave, lr, lk), BtRows::frag(Ms, lr, lk), ks); });
-    if (active) {
-        for_each_output(acc, i0, j0, wave, lk, lr, [&](int i, int j, float y) {
-            if (i < by && j < bx) out[(long)i * bx + j] = y;
-        });
-    }
+    matrix_rows_body<true>(z_in, g.ldz, by, w4, g.ldz, bx, 2 * g.Hs, blockIdx.y * kTile, blockIdx.x * kTile,
+                           [=](int i, int j, float y) {
+                               if (i < by && j < bx) out[(long)i * bx + j] = y;
+                           });
 }
 
-inline int up4(int n) { return (n + 3) & ~3; }
+using sprk::roundup4;
 // a [rows, cols] image (the frame, or the sum) with Ku kept rows and Hs kept columns of its spectrum
 inline bool sizes_ok(int rows, int cols, int Ku, int Hs) {
     return 2 <= rows && rows <= kMaxSide && 2 <= cols && cols <= kMaxSide && 1 <= Hs && Hs <= cols / 2 + 1 && 1 <= Ku &&
            Ku <= rows + 1;
 }
 inline Geo geo_of(int ny, int nx, int by, int bx, int Ku, int Hs) {
-    return Geo{ny, nx, by, bx, Hs, Ku, up4(Hs), up4(2 * Hs), up4(nx), up4(2 * ny), up4(2 * Ku)};
+    return Geo{ny, nx, by, bx, Hs, Ku, roundup4(Hs), roundup4(2 * Hs), roundup4(nx), roundup4(2 * ny), roundup4(2 * Ku)};
 }
 
 template <typename T>
@@ -170,51 +118,32 @@ int launch_rows(const void *raw, const Geo &g, float anchor, const float *w1, fl
     return sprk::check_launch("align_spectrum (stage 1)");
 }
 
-// the anchor of an integer mode is a sample value: the kernel subtracts it in integers
-template <typename T>
-bool anchor_is_sample(float anchor) {
-    return anchor >= (float)std::numeric_limits<T>::min() && anchor <= (float)std::numeric_limits<T>::max() &&
-           (float)(T)anchor == anchor;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t sprk_align_spectrum_ws_bytes(int ny, int nx, int Hs) {
     if (!sizes_ok(ny, nx, 1, Hs)) return 0;
-    return (size_t)2 * ny * up4(Hs) * sizeof(float);
+    return (size_t)2 * ny * roundup4(Hs) * sizeof(float);
 }
 
 int sprk_align_spectrum(const void *raw, int mode, int ny, int nx, int Ku, int Hs, const float *w1, const float *w2,
                         const float *g, float anchor, float *F, int first, void *ws, size_t ws_bytes, void *stream) {
-    SPRK_REQUIRE(mode == SPRK_MRC_INT8 || mode == SPRK_MRC_INT16 || mode == SPRK_MRC_FLOAT32 || mode == SPRK_MRC_UINT16,
-                 "align_spectrum: unsupported MRC mode %d (0, 1, 2 and 6 are)", mode);
+    SPRK_REQUIRE_MRC_MODE("align_spectrum", mode);
     SPRK_REQUIRE(sizes_ok(ny, nx, Ku, Hs),
                  "align_spectrum: a %dx%d frame with %d kept rows and %d kept columns (2 <= ny, nx <= %d, 1 <= Ku <= ny + 1, "
                  "1 <= Hs <= nx / 2 + 1)", ny, nx, Ku, Hs, kMaxSide);
-    SPRK_REQUIRE(mode == SPRK_MRC_INT8    ? anchor_is_sample<int8_t>(anchor)
-                 : mode == SPRK_MRC_INT16 ? anchor_is_sample<int16_t>(anchor)
-                 : mode == SPRK_MRC_UINT16 ? anchor_is_sample<uint16_t>(anchor)
-                                           : anchor == 0.0f,
+    SPRK_REQUIRE(anchor_ok(mode, anchor),
                  "align_spectrum: anchor %g (a sample value of mode %d; 0 for float32)", (double)anchor, mode);
     SPRK_REQUIRE(raw && w1 && w2 && g && F, "align_spectrum: null pointer");
-    SPRK_REQUIRE(((uintptr_t)raw & 15) == 0 && ((uintptr_t)w1 & 15) == 0 && ((uintptr_t)w2 & 15) == 0 &&
-                     ((uintptr_t)g & 15) == 0 && ((uintptr_t)F & 15) == 0 && ((uintptr_t)ws & 15) == 0,
+    SPRK_REQUIRE(sprk::aligned16(raw, w1, w2, g, F, ws),
                  "align_spectrum: the sample buffer, the matrices, the filter, the spectrum and the workspace must start "
                  "16-byte aligned");
     if (int rc = sprk::check_ws("align_spectrum", ws, ws_bytes, sprk_align_spectrum_ws_bytes(ny, nx, Hs))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const Geo geo = geo_of(ny, nx, 0, 0, Ku, Hs);
     float *v = (float *)ws;
-    int rc;
-    switch (mode) {
-        case SPRK_MRC_INT8: rc = launch_rows<int8_t>(raw, geo, anchor, w1, v, s); break;
-        case SPRK_MRC_INT16: rc = launch_rows<int16_t>(raw, geo, anchor, w1, v, s); break;
-        case SPRK_MRC_FLOAT32: rc = launch_rows<float>(raw, geo, anchor, w1, v, s); break;
-        default: rc = launch_rows<uint16_t>(raw, geo, anchor, w1, v, s); break;
-    }
-    if (rc) return rc;
+    if (int rc = dispatch_mrc(mode, [&](auto t) { return launch_rows<decltype(t)>(raw, geo, anchor, w1, v, s); })) return rc;
     hipLaunchKernelGGL(paired_cols_kernel<2>, dim3(sprk::cdiv(Hs, kTile), sprk::cdiv(Ku, kTile)), dim3(kThreads), 0, s, geo, w2,
                        (const float *)v, g, first, F);
     return sprk::check_launch("align_spectrum (stage 2)");
@@ -222,7 +151,7 @@ int sprk_align_spectrum(const void *raw, int mode, int ny, int nx, int Ku, int H
 
 size_t sprk_align_synthesize_ws_bytes(int by, int Hs) {
     if (by < 2 || by > kMaxSide || Hs < 1 || Hs > kMaxSide / 2 + 1) return 0;
-    return (size_t)by * up4(2 * Hs) * sizeof(float);
+    return (size_t)by * roundup4(2 * Hs) * sizeof(float);
 }
 
 int sprk_align_synthesize(const float *F, int Ku, int Hs, int by, int bx, const float *w3, const float *w4, float *y, void *ws,
@@ -231,8 +160,7 @@ int sprk_align_synthesize(const float *F, int Ku, int Hs, int by, int bx, const 
                  "align_synthesize: a %dx%d sum from %d kept rows and %d kept columns (2 <= by, bx <= %d, 1 <= Ku <= by + 1, "
                  "1 <= Hs <= bx / 2 + 1)", by, bx, Ku, Hs, kMaxSide);
     SPRK_REQUIRE(F && w3 && w4 && y, "align_synthesize: null pointer");
-    SPRK_REQUIRE(((uintptr_t)F & 15) == 0 && ((uintptr_t)w3 & 15) == 0 && ((uintptr_t)w4 & 15) == 0 &&
-                     ((uintptr_t)y & 15) == 0 && ((uintptr_t)ws & 15) == 0,
+    SPRK_REQUIRE(sprk::aligned16(F, w3, w4, y, ws),
                  "align_synthesize: the spectrum, the matrices, the sum and the workspace must start 16-byte aligned");
     if (int rc = sprk::check_ws("align_synthesize", ws, ws_bytes, sprk_align_synthesize_ws_bytes(by, Hs))) return rc;
     hipStream_t s = (hipStream_t)stream;

@@ -17,12 +17,12 @@
 // formed in fp64 in a fixed order (thread t its pixels t, t + 256, ... ascending, then a halving tree over the 256 partials),
 // whatever the output form: packed and unpacked calls give the same values.
 //
-// class_score_kernel: s = Q B^T on v_mfma_f32_16x16x4_f32 by the pipeline of mfma_stage.h (both operands MatrixRows, B as
-// the BtRows operand), K never split: every score is the fmaf chain over d ascending from 0.0f.  A workgroup of four waves
-// owns 64 rows of Q and walks the column tiles of 64 bank rows in ascending order; a lane keeps the running best of its four
-// rows over its own columns (ascending, a strictly greater score replaces: the lowest index of a tie stays), and at the end
-// the 16 lanes that share a row are combined, the lower index winning a tie.  Padded rows and columns are staged as zeros
-// and never compared or stored.
+// class_score_kernel: s = Q B^T on v_mfma_f32_16x16x4_f32 by matrix_rows_body of mfma_stage.h (both operands MatrixRows, B
+// as the BtRows operand), once per column tile, K never split: every score is the fmaf chain over d ascending from 0.0f.
+// A workgroup of four waves owns 64 rows of Q and walks the column tiles of 64 bank rows in ascending order; a lane keeps
+// the running best of its four rows over its own columns (ascending, a strictly greater score replaces: the lowest index
+// of a tie stays), and at the end the 16 lanes that share a row are combined, the lower index winning a tie.  Padded rows
+// and columns are staged as zeros and never compared or stored.
 //
 // class_average_kernel: one workgroup per (class, 256 output pixels); a thread owns one pixel and adds the transform value
 // of the class's members in list order (one fp32 add each, from 0.0f), read straight from memory, then multiplies once by
@@ -42,7 +42,6 @@ constexpr int kMaxAngles = 720;
 constexpr int kMaxShiftAbs = 256;                // a shift is clamped here: past +-S every tap is outside anyway
 constexpr int kThreads = 256;
 constexpr int kTile = 64;                        // score: rows of Q per workgroup, bank rows per column tile
-constexpr int kTN = kTile / 16;
 constexpr int kMaxBank = 65536;
 constexpr int kMaxD = 16384;
 
@@ -162,13 +161,8 @@ __global__ __launch_bounds__(kThreads) void class_score_kernel(const float *__re
                                                                const float *__restrict__ B, int ldb, int Mb, int D,
                                                                float *__restrict__ scores, long lds,
                                                                float *__restrict__ best_score, int *__restrict__ best_index) {
-    __shared__ __align__(16) float As[kTile * kLd];            // [64 rows of Q][kLd]
-    __shared__ __align__(16) float Bs[kTile * kLd];            // [64 bank rows][kLd]
     const int r0 = blockIdx.x * kTile;
     const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
-
-    // rows of Q at or past N and bank rows at or past Mb are staged as zeros; D is a multiple of 4: no K position is padded
-    const MatrixRows<kTile, kThreads, RowsFrom> q{Q, ldq, N, D, D, RowsFrom{r0, N}, lds_ptr(As)};
     const bool active = r0 + wave * 16 < N;                    // wave-uniform
     float bv[4];                                               // the running best of rows r0 + wave*16 + lk*4 + g
     int bi[4];
@@ -177,26 +171,19 @@ __global__ __launch_bounds__(kThreads) void class_score_kernel(const float *__re
         bv[g] = -__builtin_inff();
         bi[g] = 0x7fffffff;
     }
+    // rows of Q at or past N and bank rows at or past Mb are staged as zeros; D is a multiple of 4: no K position is padded
     for (int c0 = 0; c0 < Mb; c0 += kTile) {
-        const MatrixRows<kTile, kThreads, RowsFrom> b{B, ldb, Mb, D, D, RowsFrom{c0, Mb}, lds_ptr(Bs)};
-        f32x4 acc[kTN];
-#pragma unroll
-        for (int t = 0; t < kTN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        k_loop(D, q, b, active,
-               [&](int ks) { multiply<BtRows, true>(acc, a_frag(As, wave, lr, lk), BtRows::frag(Bs, lr, lk), ks); });
-        if (active) {
-            int walk = 0;                                      // for_each_output: tiles in order, g ascending within a tile
-            for_each_output(acc, r0, c0, wave, lk, lr, [&](int n, int m, float v) {
-                const int g = walk++ & 3;
-                if (n < N && m < Mb) {
-                    if (scores) scores[(long)n * lds + m] = v;
-                    if (v > bv[g]) {                           // this lane's columns come in ascending order
-                        bv[g] = v;
-                        bi[g] = m;
-                    }
+        int walk = 0;                                          // for_each_output: tiles in order, g ascending within a tile
+        matrix_rows_body<true>(Q, ldq, N, B, ldb, Mb, D, r0, c0, [=, &walk, &bv, &bi](int n, int m, float v) {
+            const int g = walk++ & 3;
+            if (n < N && m < Mb) {
+                if (scores) scores[(long)n * lds + m] = v;
+                if (v > bv[g]) {                               // this lane's columns come in ascending order
+                    bv[g] = v;
+                    bi[g] = m;
                 }
-            });
-        }
+            }
+        });
     }
     if (!active) return;
     // the 16 lanes lr of a row: the greater score, and of equal scores the lower index

@@ -4,6 +4,7 @@
 
 #include <atomic>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 
@@ -62,7 +63,13 @@ inline int finish_or_defer(const sprk_reduce_item &it, sprk_reduce_item *out, hi
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 inline int roundup(int a, int b) { return (a + b - 1) / b * b; }
+__host__ __device__ constexpr int roundup4(int n) { return (n + 3) & ~3; }   // K and row strides of the fp32 MFMA stages
 inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }   // workspace parts start 16-byte aligned
+// every one of the pointers starts 16-byte aligned (a null pointer does)
+template <typename... P>
+bool aligned16(const P *...p) {
+    return ((... | (uintptr_t)p) & 15) == 0;
+}
 inline int pow2_ceil(int v) {
     int p = 1;
     while (p < v) p <<= 1;

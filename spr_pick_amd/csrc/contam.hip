@@ -30,6 +30,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "range_dev.h"
 
 namespace {
 
@@ -46,14 +47,6 @@ struct Ctl {
     unsigned long long seeds, covered;
     double thr_lo, thr_hi;
 };
-
-__device__ __forceinline__ unsigned int enc(float f) {
-    const unsigned int b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float dec(unsigned int e) {
-    return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
-}
 
 // cv2::borderInterpolate(p, len, BORDER_REFLECT_101)
 __device__ __forceinline__ int reflect101(int p, int len) {
@@ -76,18 +69,8 @@ __global__ void contam_init_kernel(Ctl *__restrict__ ctl) {
     }
 }
 
-__device__ __forceinline__ unsigned int wave_min(unsigned int v) {
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned int)__shfl_xor((int)v, o, 64));
-    return v;
-}
-__device__ __forceinline__ unsigned int wave_max(unsigned int v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned int)__shfl_xor((int)v, o, 64));
-    return v;
-}
-
 __global__ __launch_bounds__(kThreads) void contam_minmax_kernel(const float *__restrict__ img, long n,
                                                                  Ctl *__restrict__ ctl) {
-    __shared__ unsigned int red[2][kThreads / 64];
     unsigned int lo = 0xffffffffu, hi = 0u;
     for (long e = (long)blockIdx.x * kThreads + threadIdx.x; e < n; e += (long)gridDim.x * kThreads) {
         const float f = img[e];
@@ -97,23 +80,9 @@ __global__ __launch_bounds__(kThreads) void contam_minmax_kernel(const float *__
             hi = max(hi, k);
         }
     }
-    lo = wave_min(lo);
-    hi = wave_max(hi);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][wave] = lo;
-        red[1][wave] = hi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kThreads / 64; ++w) {
-            lo = min(lo, red[0][w]);
-            hi = max(hi, red[1][w]);
-        }
-        if (lo != 0xffffffffu) {
-            atomicMin(&ctl->min_enc, lo);
-            atomicMax(&ctl->max_enc, hi);
-        }
+    if (block_reduce<kThreads>(lo, hi) && lo != 0xffffffffu) {
+        atomicMin(&ctl->min_enc, lo);
+        atomicMax(&ctl->max_enc, hi);
     }
 }
 

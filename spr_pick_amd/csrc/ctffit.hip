@@ -104,8 +104,7 @@ int sprk_ctf_score(const float *bins, int ldb, int n, const float *cand, int nca
     SPRK_REQUIRE(ldb >= n && ldb % 4 == 0, "ctf_score: row stride ldb %d of the bins (a multiple of 4, at least the %d bins)",
                  ldb, n);
     SPRK_REQUIRE(bins && cand && out, "ctf_score: null pointer");
-    SPRK_REQUIRE(((uintptr_t)bins & 15) == 0 && ((uintptr_t)cand & 15) == 0 && ((uintptr_t)out & 15) == 0 &&
-                     ((uintptr_t)ws & 15) == 0,
+    SPRK_REQUIRE(sprk::aligned16(bins, cand, out, ws),
                  "ctf_score: the bins, the candidates, the output and the workspace must start 16-byte aligned");
     const size_t need = sprk_ctf_score_ws_bytes(n, ncand);
     if (need)

@@ -35,6 +35,7 @@
 #include "common.h"
 #include "box_dev.h"
 #include "mfma_stage.h"
+#include "mrc_host.h"
 
 namespace {
 
@@ -276,7 +277,7 @@ __global__ __launch_bounds__(kThreads) void extract_scale_kernel(const T *__rest
     }
     const T *origin = raw + y0 * nx + x0;                      // samples read: origin[r*nx + q], 0 <= r, q < B
     const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
-    const int Bp4 = (B + 3) & ~3, Bp16 = (B + 15) & ~15, Sp16 = (S + 15) & ~15;
+    const int Bp4 = sprk::roundup4(B), Bp16 = (B + 15) & ~15, Sp16 = (S + 15) & ~15;
     const T first = origin[0];                                 // every lane the same address: a broadcast
     const float anchor = kFloat ? 0.0f : (float)first;
 
@@ -471,38 +472,29 @@ int launch_scale(const void *raw, int ny, int nx, const int *xy, int P, int B, i
 
 extern "C" int sprk_extract_scale(const void *raw, int mode, int ny, int nx, const int *xy, int P, int box, int side,
                                   const float *m, int ldm, int bg_radius, int flags, float *out, int *status, void *stream) {
-    SPRK_REQUIRE(mode == SPRK_MRC_INT8 || mode == SPRK_MRC_INT16 || mode == SPRK_MRC_FLOAT32 || mode == SPRK_MRC_UINT16,
-                 "extract_scale: unsupported MRC mode %d (0, 1, 2 and 6 are)", mode);
+    SPRK_REQUIRE_MRC_MODE("extract_scale", mode);
     SPRK_REQUIRE(box >= 2 && box <= kMaxBox && side >= 2 && side <= box,
                  "extract_scale: box %d with output side %d (2 <= side <= box <= %d)", box, side, kMaxBox);
-    SPRK_REQUIRE(ldm >= ((box + 3) & ~3) && ldm % 4 == 0,
+    SPRK_REQUIRE(ldm >= sprk::roundup4(box) && ldm % 4 == 0,
                  "extract_scale: row stride ldm %d of the matrix (a multiple of 4, at least roundup(box, 4) = %d)", ldm,
-                 (box + 3) & ~3);
+                 sprk::roundup4(box));
     SPRK_REQUIRE(bg_radius >= 0, "extract_scale: background radius %d (>= 0)", bg_radius);
     SPRK_REQUIRE((flags & ~(SPRK_EXTRACT_NORMALIZE | SPRK_EXTRACT_INVERT)) == 0, "extract_scale: unknown flags 0x%x", flags);
     SPRK_REQUIRE(ny > 0 && nx > 0 && (long)ny * nx < (1L << 31), "extract_scale: bad image size %dx%d", ny, nx);
     SPRK_REQUIRE(P >= 0, "extract_scale: %d particles", P);
     if (P == 0) return SPRK_OK;
     SPRK_REQUIRE(raw && xy && m && out && status, "extract_scale: null pointer");
-    SPRK_REQUIRE(((uintptr_t)raw & 15) == 0, "extract_scale: the sample buffer must start 16-byte aligned");
-    SPRK_REQUIRE(((uintptr_t)m & 15) == 0, "extract_scale: the matrix must start 16-byte aligned");
+    SPRK_REQUIRE(sprk::aligned16(raw), "extract_scale: the sample buffer must start 16-byte aligned");
+    SPRK_REQUIRE(sprk::aligned16(m), "extract_scale: the matrix must start 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    switch (mode) {
-        case SPRK_MRC_INT8:
-            return launch_scale<int8_t>(raw, ny, nx, xy, P, box, side, m, ldm, bg_radius, flags, out, status, s);
-        case SPRK_MRC_INT16:
-            return launch_scale<int16_t>(raw, ny, nx, xy, P, box, side, m, ldm, bg_radius, flags, out, status, s);
-        case SPRK_MRC_FLOAT32:
-            return launch_scale<float>(raw, ny, nx, xy, P, box, side, m, ldm, bg_radius, flags, out, status, s);
-        default:
-            return launch_scale<uint16_t>(raw, ny, nx, xy, P, box, side, m, ldm, bg_radius, flags, out, status, s);
-    }
+    return dispatch_mrc(mode, [&](auto t) {
+        return launch_scale<decltype(t)>(raw, ny, nx, xy, P, box, side, m, ldm, bg_radius, flags, out, status, s);
+    });
 }
 
 extern "C" int sprk_extract_boxes(const void *raw, int mode, int ny, int nx, const int *xy, int P, int box, int bin,
                                   int bg_radius, int flags, float *out, int *status, void *stream) {
-    SPRK_REQUIRE(mode == SPRK_MRC_INT8 || mode == SPRK_MRC_INT16 || mode == SPRK_MRC_FLOAT32 || mode == SPRK_MRC_UINT16,
-                 "extract_boxes: unsupported MRC mode %d (0, 1, 2 and 6 are)", mode);
+    SPRK_REQUIRE_MRC_MODE("extract_boxes", mode);
     SPRK_REQUIRE(bin >= 1 && bin <= SPRK_INGEST_MAX_BIN, "extract_boxes: bin factor %d (1..%d)", bin, SPRK_INGEST_MAX_BIN);
     // box <= 1024 is what keeps the int64 sum of squares of the integer modes below 2^63 (see the kernel)
     SPRK_REQUIRE(box >= 2 && box <= kMaxBox && box % bin == 0 && box / bin >= 2,
@@ -514,12 +506,9 @@ extern "C" int sprk_extract_boxes(const void *raw, int mode, int ny, int nx, con
     SPRK_REQUIRE(P >= 0, "extract_boxes: %d particles", P);
     if (P == 0) return SPRK_OK;
     SPRK_REQUIRE(raw && xy && out && status, "extract_boxes: null pointer");
-    SPRK_REQUIRE(((uintptr_t)raw & 15) == 0, "extract_boxes: the sample buffer must start 16-byte aligned");
+    SPRK_REQUIRE(sprk::aligned16(raw), "extract_boxes: the sample buffer must start 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    switch (mode) {
-        case SPRK_MRC_INT8: return launch_extract<int8_t>(raw, ny, nx, xy, P, box, bin, bg_radius, flags, out, status, s);
-        case SPRK_MRC_INT16: return launch_extract<int16_t>(raw, ny, nx, xy, P, box, bin, bg_radius, flags, out, status, s);
-        case SPRK_MRC_FLOAT32: return launch_extract<float>(raw, ny, nx, xy, P, box, bin, bg_radius, flags, out, status, s);
-        default: return launch_extract<uint16_t>(raw, ny, nx, xy, P, box, bin, bg_radius, flags, out, status, s);
-    }
+    return dispatch_mrc(mode, [&](auto t) {
+        return launch_extract<decltype(t)>(raw, ny, nx, xy, P, box, bin, bg_radius, flags, out, status, s);
+    });
 }

@@ -18,12 +18,14 @@
 // its own box.  Four launches per batch on the caller's stream, five with SPRK_EXTRACT_NORMALIZE; no host synchronisation,
 // no atomics.  grid.z is the particle of the batch, and a box that is not entirely inside the image leaves every stage at
 // once (stage 4 writes its zeros and its status 1): none of its samples is read.
-//   filter_rows_kernel<T> (stage 1) and filter_out_kernel (stage 4): the pipeline of mfma_stage.h, one workgroup of four
-//     waves per 64 x 64 outputs, a wave on 16 rows with four accumulators; both operands in chunks of 64 K positions through
-//     LDS, two chunks fetched ahead from clamped addresses (stage 1: sample rows against matrix rows; stage 4: matrix rows
-//     on both sides).
-//   filter_cols_kernel<kStage> (stages 2 and 3): the paired form of that pipeline, a wave holds the accumulators of rows u
-//     and M + u of its 16 rows (Re and Im, Zr and Zi), so the filter is applied in the epilogue of stage 2 without a second pass.
+//   filter_rows_kernel<T> (stage 1) and filter_out_kernel (stage 4): sample_rows_body and matrix_rows_body of
+//     mfma_stage.h (a kernel is its index set-up, one call of a body and its store), one workgroup of four waves per
+//     64 x 64 outputs, a wave on 16 rows with four accumulators; both operands in chunks of 64 K positions through LDS, two
+//     chunks fetched ahead from clamped addresses (stage 1: sample rows against matrix rows; stage 4: matrix rows on both
+//     sides).
+//   filter_cols_kernel<kStage> (stages 2 and 3): the paired form of that pipeline (paired_rows_body), a wave holds the
+//     accumulators of rows u and M + u of its 16 rows (Re and Im, Zr and Zi), so the filter is applied in the epilogue of
+//     stage 2 without a second pass.
 //   filter_norm_kernel: one workgroup per particle over its Y in `out`: normalize_box (box_dev.h), the background sums in
 //     double and the final store that extract_scale_kernel ends with.
 //
@@ -35,6 +37,7 @@
 #include "common.h"
 #include "box_dev.h"
 #include "mfma_stage.h"
+#include "mrc_host.h"
 
 namespace {
 
@@ -42,7 +45,6 @@ constexpr int kMinSide = 16, kMaxBox = 1024;
 constexpr int kThreads = kBoxThreads;            // four waves, every kernel
 constexpr int kWaves = kBoxWaves;
 constexpr int kTile = 64;                        // 64 x 64 outputs per workgroup, every stage
-constexpr int kTN = kTile / 16;
 constexpr int kMaxBatch = 65535;                 // grid.z
 constexpr size_t kBudget = (size_t)256 << 20;    // the library's own choice of a batch keeps the workspace near this
 
@@ -66,34 +68,15 @@ template <typename T>
 __global__ __launch_bounds__(kThreads) void filter_rows_kernel(const T *__restrict__ raw, Geo g, const int *__restrict__ xy,
                                                                int p0, const float *__restrict__ w1,
                                                                float *__restrict__ v_out) {
-    __shared__ __align__(16) float As[kTile * kLd];            // [64 rows of D][kLd]
-    __shared__ __align__(16) float Ms[kTile * kLd];            // [64 rows of W1][kLd]
-    const int B = g.B, Hs = g.Hs, N = 2 * g.Hs, Kp = g.ld1;
+    const int B = g.B;
     long offset;
     if (!box_origin(xy, p0 + blockIdx.z, g, offset)) return;   // before any sample is addressed; the same in every lane
     const T *__restrict__ origin = raw + offset;               // samples read: origin[r*nx + q], 0 <= r, q < B
-    const int r0 = blockIdx.y * kTile, q0 = blockIdx.x * kTile;
-    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
     const T first = origin[0];                                 // every lane the same address: a broadcast
-
+    float *__restrict__ vp = v_out + (long)blockIdx.z * 2 * B * g.ldv;
     // rows and columns past the box are fetched from its last row / column; rows of W1 past 2Hs are staged as zeros
-    const SampleRows<T, kThreads> d{origin, g.nx, B, B, r0, first, lds_ptr(As)};
-    const MatrixRows<kTile, kThreads, RowsFrom> m{w1, g.ld1, N, g.ld1, B, RowsFrom{q0, N}, lds_ptr(Ms)};
-    const bool active = r0 + wave * 16 < B;                    // wave-uniform
-    f32x4 acc[kTN];
-#pragma unroll
-    for (int t = 0; t < kTN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    k_loop(Kp, d, m, active,
-           [&](int ks) { multiply<BtRows, false>(acc, a_frag(As, wave, lr, lk), BtRows::frag(Ms, lr, lk), ks); });
-    if (active) {
-        float *__restrict__ vp = v_out + (long)blockIdx.z * 2 * B * g.ldv;
-        for_each_output(acc, r0, q0, wave, lk, lr, [&](int r, int q, float u) {
-            // the sine half goes below the cosine half; the address is formed outside the condition, so once per tile
-            const int part = q >= Hs;
-            float *p = vp + (long)(part * B + r) * g.ldv + (q - part * Hs);
-            if (r < B && q < N) *p = u;
-        });
-    }
+    sample_rows_body<false>(origin, g.nx, B, B, first, w1, g.ld1, 2 * g.Hs, blockIdx.y * kTile, blockIdx.x * kTile,
+                            [=](int r, int q, float u) { store_v_split(vp, g.ldv, B, g.Hs, r, q, u); });
 }
 
 // ---- stages 2 and 3: rows u0 .. and M + u0 .. of W times the K-major operand of the workspace ---------------------------
@@ -104,44 +87,25 @@ template <int kStage>
 __global__ __launch_bounds__(kThreads) void filter_cols_kernel(Geo g, const int *__restrict__ xy, int p0,
                                                                const float *__restrict__ w, const float *__restrict__ b_in,
                                                                const float *__restrict__ phi, float *__restrict__ c_out) {
-    using BRows = KMajorRows<kTile, kThreads, true>;
-    __shared__ __align__(16) float As[2 * kTile * kLd];        // [64 rows u, then 64 rows M + u][kLd]
-    __shared__ __align__(16) float Bs[kKC * BRows::kLdb];      // [rows of the operand = K][kLdb]
     const int Hs = g.Hs, ldv = g.ldv;
     const int M = kStage == 2 ? g.Ku : g.S, K = kStage == 2 ? 2 * g.B : 2 * g.Ku, ldw = kStage == 2 ? 2 * g.B : g.ld3;
-    const int Kp = (K + 3) & ~3;
     long offset;
     if (!box_origin(xy, p0 + blockIdx.z, g, offset)) return;   // the same in every lane
     const float *__restrict__ bt = b_in + (long)blockIdx.z * K * ldv;
-    const int u0 = blockIdx.y * kTile, v0 = blockIdx.x * kTile;
-    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
-
+    float *__restrict__ ct = c_out + (long)blockIdx.z * (kStage == 2 ? 2 * g.Ku * ldv : g.S * g.ldz);
     // A: rows u and M + u of W, the K positions at or past K staged as zeros.  B: columns Hs .. ldv-1 of the operand were
     // never written: staged as zeros, like every row at or past K
-    const MatrixRows<2 * kTile, kThreads, RowPairs> a{w, ldw, 2 * M, ldw, K, RowPairs{u0, M}, lds_ptr(As)};
-    const BRows b{bt, ldv, K, v0, Hs, lds_ptr(Bs)};
-    const bool active = u0 + wave * 16 < M;                    // wave-uniform
-    f32x4 re[kTN], im[kTN];                                    // Re and Im, Zr and Zi
-#pragma unroll
-    for (int t = 0; t < kTN; ++t) re[t] = im[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    k_loop(Kp, a, b, active, [&](int ks) {
-        multiply_pair<KMajor<kTile>>(re, im, a_frag(As, wave, lr, lk), KMajor<kTile>::frag(Bs, lr, lk), ks);
-    });
-    if (active) {
-        float *__restrict__ ct = c_out + (long)blockIdx.z * (kStage == 2 ? 2 * g.Ku * ldv : g.S * g.ldz);
-        for_each_output(re, im, u0, v0, wave, lk, lr, [&](int u, int v, float x, float y) {
+    paired_rows_body(w, ldw, M, K, bt, ldv, Hs, blockIdx.y * kTile, blockIdx.x * kTile, [=](int u, int v, float x, float y) {
+        if constexpr (kStage == 2) {
             if (u < M && v < Hs) {
-                if constexpr (kStage == 2) {
-                    const float f = phi[u * Hs + v];
-                    ct[(long)u * ldv + v] = __fmul_rn(x, f);
-                    ct[(long)(M + u) * ldv + v] = __fmul_rn(y, f);
-                } else {
-                    ct[(long)u * g.ldz + v] = x;
-                    ct[(long)u * g.ldz + Hs + v] = y;
-                }
+                const float f = phi[u * Hs + v];
+                ct[(long)u * ldv + v] = __fmul_rn(x, f);
+                ct[(long)(M + u) * ldv + v] = __fmul_rn(y, f);
             }
-        });
-    }
+        } else {
+            store_zr_zi(ct, g.ldz, M, Hs, u, v, x, y);
+        }
+    });
 }
 
 // the box's first sample as the float the integer modes add back (times Phi at the origin); float32: not used
@@ -161,12 +125,9 @@ __global__ __launch_bounds__(kThreads) void filter_out_kernel(const void *__rest
                                                               const float *__restrict__ z_in, const float *__restrict__ w4,
                                                               const float *__restrict__ phi, int flags,
                                                               float *__restrict__ out, int *__restrict__ status) {
-    __shared__ __align__(16) float As[kTile * kLd];            // [64 rows of Z][kLd]
-    __shared__ __align__(16) float Ms[kTile * kLd];            // [64 rows of W4][kLd]
-    const int S = g.S, K = 2 * g.Hs, Kp = g.ldz;
+    const int S = g.S, tid = threadIdx.x;
     const int p = p0 + blockIdx.z;
     const int i0 = blockIdx.y * kTile, j0 = blockIdx.x * kTile;
-    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
     const bool normalize = flags & SPRK_EXTRACT_NORMALIZE, invert = flags & SPRK_EXTRACT_INVERT;
     float *__restrict__ o = out + (long)p * S * S;
     long offset;
@@ -180,27 +141,16 @@ __global__ __launch_bounds__(kThreads) void filter_out_kernel(const void *__rest
     }
     const float *__restrict__ zt = z_in + (long)blockIdx.z * S * g.ldz;
     const float anchor = anchor_of(raw, mode, offset), phi0 = phi[(S / 2) * g.Hs];   // Phi at k = 0, v = 0
-
     // rows of Z and of W4 at or past S and the K positions at or past 2Hs are staged as zeros
-    const MatrixRows<kTile, kThreads, RowsFrom> z{zt, g.ldz, S, g.ldz, K, RowsFrom{i0, S}, lds_ptr(As)};
-    const MatrixRows<kTile, kThreads, RowsFrom> m{w4, g.ldz, S, g.ldz, K, RowsFrom{j0, S}, lds_ptr(Ms)};
-    const bool active = i0 + wave * 16 < S;                    // wave-uniform
-    f32x4 acc[kTN];
-#pragma unroll
-    for (int t = 0; t < kTN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    k_loop(Kp, z, m, active,
-           [&](int ks) { multiply<BtRows, false>(acc, a_frag(As, wave, lr, lk), BtRows::frag(Ms, lr, lk), ks); });
-    if (active) {
-        for_each_output(acc, i0, j0, wave, lk, lr, [&](int i, int j, float y) {
-            if (i < S && j < S) {
-                if (!normalize) {
-                    if (mode != SPRK_MRC_FLOAT32) y = __fmaf_rn(phi0, anchor, y);
-                    if (invert) y = -y;
-                }
-                o[i * S + j] = y;
+    matrix_rows_body<false>(zt, g.ldz, S, w4, g.ldz, S, 2 * g.Hs, i0, j0, [=](int i, int j, float y) {
+        if (i < S && j < S) {
+            if (!normalize) {
+                if (mode != SPRK_MRC_FLOAT32) y = __fmaf_rn(phi0, anchor, y);
+                if (invert) y = -y;
             }
-        });
-    }
+            o[i * S + j] = y;
+        }
+    });
     if (!normalize && tid == 0 && blockIdx.x == 0 && blockIdx.y == 0) status[p] = 0;
 }
 
@@ -218,7 +168,8 @@ __global__ __launch_bounds__(kThreads) void filter_norm_kernel(Geo g, const int 
 inline bool sizes_ok(int B, int S) { return S >= kMinSide && S <= B && B <= kMaxBox && B % 2 == 0 && S % 2 == 0; }
 inline Geo geo_of(int B, int S, int ny, int nx) {
     const int Hs = S / 2 + 1, Ku = S + 1;
-    return Geo{B, S, Hs, Ku, (Hs + 3) & ~3, (2 * Hs + 3) & ~3, (B + 3) & ~3, (2 * Ku + 3) & ~3, ny, nx};
+    using sprk::roundup4;
+    return Geo{B, S, Hs, Ku, roundup4(Hs), roundup4(2 * Hs), roundup4(B), roundup4(2 * Ku), ny, nx};
 }
 inline size_t v_bytes(const Geo &g) { return sprk::align16((size_t)2 * g.B * g.ldv * sizeof(float)); }
 inline size_t f_bytes(const Geo &g) { return sprk::align16((size_t)2 * g.Ku * g.ldv * sizeof(float)); }
@@ -251,8 +202,7 @@ size_t sprk_extract_filter_ws_bytes(int P, int box, int side, int max_batch) {
 int sprk_extract_filter(const void *raw, int mode, int ny, int nx, const int *xy, int P, int box, int side, const float *w1,
                         const float *w2, const float *w3, const float *w4, const float *phi, int bg_radius, int flags,
                         int max_batch, float *out, int *status, void *ws, size_t ws_bytes, void *stream) {
-    SPRK_REQUIRE(mode == SPRK_MRC_INT8 || mode == SPRK_MRC_INT16 || mode == SPRK_MRC_FLOAT32 || mode == SPRK_MRC_UINT16,
-                 "extract_filter: unsupported MRC mode %d (0, 1, 2 and 6 are)", mode);
+    SPRK_REQUIRE_MRC_MODE("extract_filter", mode);
     SPRK_REQUIRE(sizes_ok(box, side),
                  "extract_filter: box %d with output side %d (both even, %d <= side <= box <= %d)", box, side, kMinSide,
                  kMaxBox);
@@ -264,9 +214,7 @@ int sprk_extract_filter(const void *raw, int mode, int ny, int nx, const int *xy
     SPRK_REQUIRE(P >= 0, "extract_filter: %d particles", P);
     if (P == 0) return SPRK_OK;
     SPRK_REQUIRE(raw && xy && w1 && w2 && w3 && w4 && phi && out && status, "extract_filter: null pointer");
-    SPRK_REQUIRE(((uintptr_t)raw & 15) == 0 && ((uintptr_t)w1 & 15) == 0 && ((uintptr_t)w2 & 15) == 0 &&
-                     ((uintptr_t)w3 & 15) == 0 && ((uintptr_t)w4 & 15) == 0 && ((uintptr_t)phi & 15) == 0 &&
-                     ((uintptr_t)out & 15) == 0 && ((uintptr_t)ws & 15) == 0,
+    SPRK_REQUIRE(sprk::aligned16(raw, w1, w2, w3, w4, phi, out, ws),
                  "extract_filter: the sample buffer, the matrices, the filter, the output and the workspace must start "
                  "16-byte aligned");
     if (int rc = sprk::check_ws("extract_filter", ws, ws_bytes, sprk_extract_filter_ws_bytes(P, box, side, max_batch)))
@@ -280,13 +228,7 @@ int sprk_extract_filter(const void *raw, int mode, int ny, int nx, const int *xy
     const dim3 block(kThreads);
     for (int p0 = 0; p0 < P; p0 += batch) {
         const int nb = P - p0 < batch ? P - p0 : batch;
-        int rc;
-        switch (mode) {
-            case SPRK_MRC_INT8: rc = launch_rows<int8_t>(raw, g, xy, p0, nb, w1, v, s); break;
-            case SPRK_MRC_INT16: rc = launch_rows<int16_t>(raw, g, xy, p0, nb, w1, v, s); break;
-            case SPRK_MRC_FLOAT32: rc = launch_rows<float>(raw, g, xy, p0, nb, w1, v, s); break;
-            default: rc = launch_rows<uint16_t>(raw, g, xy, p0, nb, w1, v, s); break;
-        }
+        int rc = dispatch_mrc(mode, [&](auto t) { return launch_rows<decltype(t)>(raw, g, xy, p0, nb, w1, v, s); });
         if (rc) return rc;
         hipLaunchKernelGGL(filter_cols_kernel<2>, dim3(sprk::cdiv(g.Hs, kTile), sprk::cdiv(g.Ku, kTile), nb), block, 0, s, g,
                            xy, p0, w2, (const float *)v, phi, f);

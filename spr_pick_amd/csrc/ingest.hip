@@ -56,6 +56,8 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mrc_host.h"
+#include "range_dev.h"
 
 namespace {
 
@@ -63,63 +65,9 @@ constexpr int kThreads = 256;
 constexpr int kTile = 32;
 constexpr int kMaxBlocks = 2048;     // grid cap of the stage-A kernels = number of partial pairs in the workspace
 
-struct Part {
-    unsigned int min_enc, max_enc;   // order-preserving encodings of one workgroup's min / max
-};
-
-__device__ __forceinline__ unsigned int enc(float f) {
-    const unsigned int b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float dec(unsigned int e) {
-    return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
-}
-__device__ __forceinline__ unsigned int wave_min(unsigned int v) {
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned int)__shfl_xor((int)v, o, 64));
-    return v;
-}
-__device__ __forceinline__ unsigned int wave_max(unsigned int v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned int)__shfl_xor((int)v, o, 64));
-    return v;
-}
-
-// the workgroup's min / max (all threads must call); thread 0 returns true and holds the pair in lo / hi
-__device__ __forceinline__ bool block_reduce(unsigned int &lo, unsigned int &hi) {
-    __shared__ unsigned int red[2][kThreads / 64];
-    lo = wave_min(lo);
-    hi = wave_max(hi);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][wave] = lo;
-        red[1][wave] = hi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kThreads / 64; ++w) {
-            lo = min(lo, red[0][w]);
-            hi = max(hi, red[1][w]);
-        }
-        return true;
-    }
-    return false;
-}
-
 // every workgroup stores its pair, also one without a single output (the neutral pair): nothing to initialise
 __device__ __forceinline__ void block_range(unsigned int lo, unsigned int hi, Part *__restrict__ parts) {
-    if (block_reduce(lo, hi)) parts[blockIdx.x] = Part{lo, hi};
-}
-
-__global__ __launch_bounds__(kThreads) void ingest_range_kernel(const Part *__restrict__ parts, int nparts,
-                                                                float *__restrict__ range) {
-    unsigned int lo = 0xffffffffu, hi = 0u;
-    for (int k = threadIdx.x; k < nparts; k += kThreads) {
-        lo = min(lo, parts[k].min_enc);
-        hi = max(hi, parts[k].max_enc);
-    }
-    if (block_reduce(lo, hi)) {
-        range[0] = dec(lo);
-        range[1] = dec(hi);
-    }
+    if (block_reduce<kThreads>(lo, hi)) parts[blockIdx.x] = Part{lo, hi};
 }
 
 // the contract's accumulator: exact int32 for the integer modes, one fp32 add per sample for float32
@@ -607,16 +555,6 @@ constexpr size_t kFlatPartBytes = (size_t)kMaxBlocks * sizeof(Part);     // 16 K
 
 int clip_grid(long n) { return (int)std::min<long>(kClipBlocks, sprk::cdiv(sprk::cdiv(n, 4), kClipThreads)); }
 
-int sample_bytes(int mode) {
-    switch (mode) {
-        case SPRK_MRC_INT8: return 1;
-        case SPRK_MRC_INT16: return 2;
-        case SPRK_MRC_FLOAT32: return 4;
-        case SPRK_MRC_UINT16: return 2;
-        default: return 0;
-    }
-}
-
 // -> the number of workgroups launched (= partial pairs written), or a negative error code
 template <typename T>
 int launch_bin(const void *raw, int ny, int nx, int N, float *binned, Part *parts, hipStream_t s) {
@@ -656,24 +594,19 @@ size_t sprk_ingest_ws_bytes(int ny, int nx, int bin) {
 int sprk_ingest_bin(const void *raw, int mode, int ny, int nx, int bin, float *binned_out, float *range_out, void *ws,
                     size_t ws_bytes, void *stream) {
     SPRK_REQUIRE(raw && binned_out && range_out, "ingest_bin: null pointer");
-    SPRK_REQUIRE(sample_bytes(mode) > 0, "ingest_bin: unsupported MRC mode %d (0, 1, 2 and 6 are)", mode);
+    SPRK_REQUIRE_MRC_MODE("ingest_bin", mode);
     SPRK_REQUIRE(bin >= 1 && bin <= SPRK_INGEST_MAX_BIN, "ingest_bin: bin factor %d (1..%d)", bin, SPRK_INGEST_MAX_BIN);
     SPRK_REQUIRE(ny > 0 && nx > 0 && (long)ny * nx < (1L << 31), "ingest_bin: bad image size %dx%d", ny, nx);
     SPRK_REQUIRE(ny / bin >= 1 && nx / bin >= 1, "ingest_bin: a %dx%d image has no %dx%d block", ny, nx, bin, bin);
-    SPRK_REQUIRE(((uintptr_t)raw & 15) == 0 && ((uintptr_t)binned_out & 15) == 0,
+    SPRK_REQUIRE(sprk::aligned16(raw, binned_out),
                  "ingest_bin: the sample buffer and the output must start 16-byte aligned");
     if (int rc = sprk::check_ws("ingest_bin", ws, ws_bytes, sprk_ingest_ws_bytes(ny, nx, bin))) return rc;
     hipStream_t s = (hipStream_t)stream;
     Part *parts = (Part *)ws;
-    int grid;
-    switch (mode) {
-        case SPRK_MRC_INT8: grid = launch_bin<int8_t>(raw, ny, nx, bin, binned_out, parts, s); break;
-        case SPRK_MRC_INT16: grid = launch_bin<int16_t>(raw, ny, nx, bin, binned_out, parts, s); break;
-        case SPRK_MRC_FLOAT32: grid = launch_bin<float>(raw, ny, nx, bin, binned_out, parts, s); break;
-        default: grid = launch_bin<uint16_t>(raw, ny, nx, bin, binned_out, parts, s); break;
-    }
+    const int grid = dispatch_mrc(
+        mode, [&](auto t) { return launch_bin<decltype(t)>(raw, ny, nx, bin, binned_out, parts, s); });
     if (grid < 0) return grid;
-    hipLaunchKernelGGL(ingest_range_kernel, dim3(1), dim3(kThreads), 0, s, parts, grid, range_out);
+    hipLaunchKernelGGL(ingest_range_kernel<kRangeThreads>, dim3(1), dim3(kRangeThreads), 0, s, parts, grid, range_out);
     return sprk::check_launch("ingest_range");
 }
 
@@ -707,12 +640,12 @@ int sprk_ingest_clip(const float *binned_in, float *binned_out, int by, int bx, 
     SPRK_REQUIRE(k_lo >= 0 && k_lo <= k_hi && k_hi <= n - 1,
                  "ingest_clip: ranks %lld, %lld of %ld elements (0 <= k_lo <= k_hi <= n-1)", k_lo, k_hi, n);
     if (int rc = sprk::check_ws("ingest_clip", ws, ws_bytes, sprk_ingest_clip_ws_bytes(by, bx))) return rc;
-    SPRK_REQUIRE(((uintptr_t)ws & 15) == 0, "ingest_clip: the workspace must start 16-byte aligned");
+    SPRK_REQUIRE(sprk::aligned16(ws), "ingest_clip: the workspace must start 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     ClipState *st = (ClipState *)ws;
     unsigned int *sums = (unsigned int *)(st + 1), *partials = sums + 2 * kClipBins;
     const int grid = clip_grid(n);
-    const int vec_in = ((uintptr_t)binned_in & 15) == 0, vec_out = vec_in && ((uintptr_t)binned_out & 15) == 0;
+    const int vec_in = sprk::aligned16(binned_in), vec_out = vec_in && sprk::aligned16(binned_out);
     for (int pass = 0; pass < kClipPasses; ++pass) {
         hipLaunchKernelGGL(clip_hist_kernel, dim3(grid), dim3(kClipThreads), 0, s, binned_in, n, vec_in, range_in, pass, st,
                            partials);
@@ -742,7 +675,7 @@ int sprk_ingest_flatten(const float *binned_in, float *binned_out, int by, int b
     // a window holds at most 2047^2 values below 2^31: their integer sum stays below 2^53, exact as a double
     SPRK_REQUIRE(R >= 1 && R <= SPRK_INGEST_MAX_FLATTEN, "ingest_flatten: radius %d (1..%d)", R, SPRK_INGEST_MAX_FLATTEN);
     if (int rc = sprk::check_ws("ingest_flatten", ws, ws_bytes, sprk_ingest_flatten_ws_bytes(by, bx, R))) return rc;
-    SPRK_REQUIRE(((uintptr_t)ws & 15) == 0, "ingest_flatten: the workspace must start 16-byte aligned");
+    SPRK_REQUIRE(sprk::aligned16(ws), "ingest_flatten: the workspace must start 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     Part *parts = (Part *)ws;
     unsigned long long *H = (unsigned long long *)((char *)ws + kFlatPartBytes);
@@ -756,7 +689,7 @@ int sprk_ingest_flatten(const float *binned_in, float *binned_out, int by, int b
     hipLaunchKernelGGL(flatten_col_kernel, dim3(grid), dim3(kThreads), 0, s, binned_in, binned_out, by, bx, R, chunk,
                        range_in, H, parts);
     if (int rc = sprk::check_launch("ingest_flatten_col")) return rc;
-    hipLaunchKernelGGL(ingest_range_kernel, dim3(1), dim3(kThreads), 0, s, parts, grid, range_out);
+    hipLaunchKernelGGL(ingest_range_kernel<kRangeThreads>, dim3(1), dim3(kRangeThreads), 0, s, parts, grid, range_out);
     return sprk::check_launch("ingest_flatten_range");
 }
 

@@ -1,11 +1,12 @@
 // The chunked K pipeline of the tiled fp32 GEMMs on v_mfma_f32_16x16x4_f32 whose K loop over one accumulator is a
-// contract's fmaf chain (resample.hip, psd.hip, extractfilter.hip; extract.hip takes the staging helpers only;
-// DESIGN §4.3c).  Not part of the ABI.
+// contract's fmaf chain (resample.hip, psd.hip, extractfilter.hip, align.hip, alignsum.hip, class2d.hip; extract.hip takes
+// the staging helpers only).  Not part of the ABI.
 //
 // A workgroup of THREADS threads (64 per wave) multiplies A [rows, K] by B [K, columns] in chunks of kKC positions of K
 // through LDS, a wave on 16 rows of A with TN accumulators of 16 x 16.  Top to bottom: the operand loaders (what a chunk
 // of each operand is, fetched into registers and staged into LDS), multiply (one staged chunk for one wave), k_loop (the
-// schedule that ties them together) and for_each_output (where a wave's accumulators sit in the output).
+// schedule that ties them together), for_each_output (where a wave's accumulators sit in the output) and the four stage
+// bodies that put these together for one output tile, with the two stores that several kernels end with.
 // The bits: every accumulator takes its K positions in ascending order, four per MFMA, one rounding per product, from
 // 0.0f, K never split; every staged element outside an operand is a zero formed in registers, on BOTH operands wherever
 // K is padded (the other operand may be uninitialised memory, and fma(0, NaN, acc) is NaN).
@@ -13,6 +14,8 @@
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+
+#include "common.h"
 
 namespace {
 
@@ -321,6 +324,133 @@ __device__ __forceinline__ void for_each_output(const f32x4 (&re)[TN], const f32
     for (int t = 0; t < TN; ++t)
 #pragma unroll
         for (int g = 0; g < 4; ++g) f(r0 + wave * 16 + lk * 4 + g, c0 + t * 16 + lr, re[t][g], im[t][g]);
+}
+
+// ---- 5. the stage bodies -------------------------------------------------------------------------------------------------
+// One output tile at rows r0 .., columns c0 .. from start to end: the two staged operands (each body owns its __shared__
+// arrays: a kernel calls one body), the loaders, the wave-uniform `active`, the accumulators, the K loop and the walk.  K is
+// the operands' own extent; it is padded here to Kp = sprk::roundup4(K), the zeros formed at staging on both operands.  A kernel
+// is its index set-up, one call of a body and its store: store(row, column, value) or, paired, store(row, column, re, im),
+// called by the active waves for every element of the tile, those past the output included (the store skips them).
+// The accumulators are declared and zeroed in the body itself, which is inlined by force, and reach mul by reference (3.).
+// A store captures what it needs BY VALUE ([=]; by reference only what it changes): behind captured references the compiler
+// formed the output address anew for every element (60 instructions more in the epilogue of each V-split kernel).
+
+// Sample rows x matrix rows^T, 64 x 64 on four waves: out[r, j] = chain over c < cols of (D[r, c] - first) * M[j, c], D the
+// [rows, cols] samples at `base` (pitch samples per row), M [mrows, ldm] (ldm at least roundup4(cols)).
+template <bool kGrouped, typename S, typename Store>
+__device__ __forceinline__ void sample_rows_body(const S *__restrict__ base, int pitch, int rows, int cols, S first,
+                                                 const float *__restrict__ m, int ldm, int mrows, int r0, int c0,
+                                                 Store store) {
+    constexpr int kThreads = 256, kTN = 4;
+    __shared__ __align__(16) float As[64 * kLd];               // [64 rows of D][kLd]
+    __shared__ __align__(16) float Ms[64 * kLd];               // [64 rows of M][kLd]
+    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
+    const int Kp = sprk::roundup4(cols);
+    const SampleRows<S, kThreads> d{base, pitch, rows, cols, r0, first, lds_ptr(As)};
+    const MatrixRows<64, kThreads, RowsFrom> b{m, ldm, mrows, Kp, cols, RowsFrom{c0, mrows}, lds_ptr(Ms)};
+    const bool active = r0 + wave * 16 < rows;                 // wave-uniform
+    f32x4 acc[kTN];
+#pragma unroll
+    for (int t = 0; t < kTN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    k_loop(Kp, d, b, active,
+           [&](int ks) { multiply<BtRows, kGrouped>(acc, a_frag(As, wave, lr, lk), BtRows::frag(Ms, lr, lk), ks); });
+    if (active) for_each_output(acc, r0, c0, wave, lk, lr, store);
+}
+
+// Matrix rows x K-major rows, 16*WM x 16*TN on WM waves: out[i, j] = chain over r < K of A[i, r] * U[r, j], from 0.0f or,
+// with `init`, from init[i * cols + j]; A [arows, lda], U [K, ldu] with every column below ldu written, cols <= ldu.
+template <int WM, int TN, typename Store>
+__device__ __forceinline__ void kmajor_rows_body(const float *__restrict__ a, int lda, int arows, int K,
+                                                 const float *__restrict__ u, int ldu, int cols, const float *init, int r0,
+                                                 int c0, Store store) {
+    constexpr int kThreads = 64 * WM, kRows = 16 * WM, W = 16 * TN;
+    using URows = KMajorRows<W, kThreads, false>;
+    __shared__ __align__(16) float As[kRows * kLd];            // [rows of A][kLd]
+    __shared__ __align__(16) float Bs[kKC * URows::kLdb];      // [rows of U = K][kLdb]
+    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
+    const int Kp = sprk::roundup4(K);
+    // rows of U at or past K were never written: fetched from row K-1 instead and staged as zeros
+    const MatrixRows<kRows, kThreads, RowsFrom> la{a, lda, arows, Kp, K, RowsFrom{r0, arows}, lds_ptr(As)};
+    const URows lb{u, ldu, K, c0, ldu, lds_ptr(Bs)};
+    const bool active = r0 + wave * 16 < arows;                // wave-uniform
+    f32x4 acc[TN];
+#pragma unroll
+    for (int t = 0; t < TN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    if (active && init) {                                      // the chain goes on where it was left
+#pragma unroll
+        for (int t = 0; t < TN; ++t)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int i = r0 + wave * 16 + lk * 4 + g, j = c0 + t * 16 + lr;
+                if (i < arows && j < cols) acc[t][g] = init[(long)i * cols + j];
+            }
+    }
+    k_loop(Kp, la, lb, active,
+           [&](int ks) { multiply<KMajor<W>, true>(acc, a_frag(As, wave, lr, lk), KMajor<W>::frag(Bs, lr, lk), ks); });
+    if (active) for_each_output(acc, r0, c0, wave, lk, lr, store);
+}
+
+// Paired rows x K-major rows, 64 x 64 on four waves: re[u, v] = chain over t < K of W[u, t] * B[t, v], im with row M + u;
+// W [2M, ldw], B [K, ldb] of which only columns below `end` were ever written.
+template <typename Store>
+__device__ __forceinline__ void paired_rows_body(const float *__restrict__ w, int ldw, int M, int K,
+                                                 const float *__restrict__ b, int ldb, int end, int r0, int c0,
+                                                 Store store) {
+    constexpr int kThreads = 256, kTN = 4;
+    using BRows = KMajorRows<64, kThreads, true>;
+    __shared__ __align__(16) float As[2 * kPairRows * kLd];    // [64 rows u, then 64 rows M + u][kLd]
+    __shared__ __align__(16) float Bs[kKC * BRows::kLdb];      // [rows of B = K][kLdb]
+    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
+    const int Kp = sprk::roundup4(K);
+    const MatrixRows<2 * kPairRows, kThreads, RowPairs> la{w, ldw, 2 * M, Kp, K, RowPairs{r0, M}, lds_ptr(As)};
+    const BRows lb{b, ldb, K, c0, end, lds_ptr(Bs)};
+    const bool active = r0 + wave * 16 < M;                    // wave-uniform
+    f32x4 re[kTN], im[kTN];
+#pragma unroll
+    for (int t = 0; t < kTN; ++t) re[t] = im[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    k_loop(Kp, la, lb, active, [&](int ks) {
+        multiply_pair<KMajor<64>>(re, im, a_frag(As, wave, lr, lk), KMajor<64>::frag(Bs, lr, lk), ks);
+    });
+    if (active) for_each_output(re, im, r0, c0, wave, lk, lr, store);
+}
+
+// Matrix rows x matrix rows^T, 64 x 64 on four waves: out[i, j] = chain over t < K of A[i, t] * B[j, t]; A [arows, lda],
+// B [brows, ldb], both strides at least roundup4(K).
+template <bool kGrouped, typename Store>
+__device__ __forceinline__ void matrix_rows_body(const float *__restrict__ a, int lda, int arows,
+                                                 const float *__restrict__ b, int ldb, int brows, int K, int r0, int c0,
+                                                 Store store) {
+    constexpr int kThreads = 256, kTN = 4;
+    __shared__ __align__(16) float As[64 * kLd];               // [64 rows of A][kLd]
+    __shared__ __align__(16) float Ms[64 * kLd];               // [64 rows of B][kLd]
+    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
+    const int Kp = sprk::roundup4(K);
+    const MatrixRows<64, kThreads, RowsFrom> la{a, lda, arows, Kp, K, RowsFrom{r0, arows}, lds_ptr(As)};
+    const MatrixRows<64, kThreads, RowsFrom> lb{b, ldb, brows, Kp, K, RowsFrom{c0, brows}, lds_ptr(Ms)};
+    const bool active = r0 + wave * 16 < arows;                // wave-uniform
+    f32x4 acc[kTN];
+#pragma unroll
+    for (int t = 0; t < kTN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    k_loop(Kp, la, lb, active,
+           [&](int ks) { multiply<BtRows, kGrouped>(acc, a_frag(As, wave, lr, lk), BtRows::frag(Ms, lr, lk), ks); });
+    if (active) for_each_output(acc, r0, c0, wave, lk, lr, store);
+}
+
+// The two stores that more than one kernel ends with.
+// U[r, q] of a [rows, 2H] tile product into V = [U[:, :H] ; U[:, H:]] [2 rows, ldv]: the sine half goes below the cosine
+// half.  The address is formed outside the condition, so once per tile of the walk and not once per element.
+__device__ __forceinline__ void store_v_split(float *v, int ldv, int rows, int H, int r, int q, float u) {
+    const int part = q >= H;
+    float *p = v + (long)(part * rows + r) * ldv + (q - part * H);
+    if (r < rows && q < 2 * H) *p = u;
+}
+// (Zr, Zi)[u, v] of an [M, H] pair into Z = [Zr, Zi] [M, ldz]
+__device__ __forceinline__ void store_zr_zi(float *z, int ldz, int M, int H, int u, int v, float zr, float zi) {
+    if (u < M && v < H) {
+        z[(long)u * ldz + v] = zr;
+        z[(long)u * ldz + H + v] = zi;
+    }
 }
 
 }  // namespace

@@ -19,6 +19,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "mrc_host.h"
 
 namespace {
 
@@ -111,26 +112,18 @@ int launch(const void *raw, int ny, int nx, const float *gain, const float *dark
     return sprk::check_launch("movie_correct");
 }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int sprk_movie_correct(const void *raw, int mode, int ny, int nx, const float *gain, const float *dark,
                                   const uint8_t *fix, float *out, float *sum, int first, void *stream) {
     SPRK_REQUIRE(raw && out, "movie_correct: null pointer (raw and out are needed)");
-    SPRK_REQUIRE(mode == SPRK_MRC_INT8 || mode == SPRK_MRC_INT16 || mode == SPRK_MRC_FLOAT32 || mode == SPRK_MRC_UINT16,
-                 "movie_correct: unsupported MRC mode %d (0, 1, 2 and 6 are)", mode);
+    SPRK_REQUIRE_MRC_MODE("movie_correct", mode);
     SPRK_REQUIRE(1 <= ny && ny <= kMaxSide && 1 <= nx && nx <= kMaxSide, "movie_correct: a %dx%d frame (both sides in 1..%d)", ny,
                  nx, kMaxSide);
-    SPRK_REQUIRE(aligned16(raw) && aligned16(gain) && aligned16(dark) && aligned16(fix) && aligned16(out) && aligned16(sum),
+    SPRK_REQUIRE(sprk::aligned16(raw, gain, dark, fix, out, sum),
                  "movie_correct: the samples, the references, the fix map, the output and the sum must start 16-byte aligned");
     SPRK_REQUIRE(out != raw && out != gain && out != dark && out != sum,
                  "movie_correct: out must not be raw, gain, dark or sum (the windows read them while out is written)");
     hipStream_t s = (hipStream_t)stream;
-    switch (mode) {
-        case SPRK_MRC_INT8: return launch<int8_t>(raw, ny, nx, gain, dark, fix, out, sum, first, s);
-        case SPRK_MRC_INT16: return launch<int16_t>(raw, ny, nx, gain, dark, fix, out, sum, first, s);
-        case SPRK_MRC_FLOAT32: return launch<float>(raw, ny, nx, gain, dark, fix, out, sum, first, s);
-        default: return launch<uint16_t>(raw, ny, nx, gain, dark, fix, out, sum, first, s);
-    }
+    return dispatch_mrc(mode, [&](auto t) { return launch<decltype(t)>(raw, ny, nx, gain, dark, fix, out, sum, first, s); });
 }

@@ -17,26 +17,26 @@
 // top of what the batches before left there, so the bits do not depend on nb.  Three launches per batch on the caller's
 // stream, no host synchronisation, no atomics:
 //   psd_rows_kernel<T>: one workgroup of four waves per 64 rows x 64 columns of one tile's U (grid.z = the tile), a wave
-//     on 16 rows with four accumulators; the pipeline of mfma_stage.h (fetch two chunks of K ahead from clamped
-//     addresses, zeros formed at staging, staged rows of 66 floats) with plain fragment reads.  2H = T + 2 is never a
-//     multiple of 16: the ragged last column tile is the normal case, its rows of W1 past 2H staged as zeros and its
-//     columns not stored.
+//     on 16 rows with four accumulators; sample_rows_body of mfma_stage.h (fetch two chunks of K ahead from clamped
+//     addresses, zeros formed at staging, staged rows of 66 floats) with plain fragment reads and the V-split store.
+//     2H = T + 2 is never a multiple of 16: the ragged last column tile is the normal case, its rows of W1 past 2H staged
+//     as zeros and its columns not stored.
 //   psd_cols_kernel: one workgroup of four waves per 64 rows u x 64 columns v of one tile's spectrum; the paired form of
-//     the same pipeline: a wave holds the Re and the Im accumulators of its 16 rows (eight of them), so that Q needs no
-//     second pass: A is rows u and T+u of W2, B the chunk of V.
+//     the same pipeline (paired_rows_body): a wave holds the Re and the Im accumulators of its 16 rows (eight of them),
+//     so that Q needs no second pass: A is rows u and T+u of W2, B the chunk of V.
 //   psd_sum_kernel: one thread per element of P over the batch's tiles.
 #include <cstdint>
 #include <type_traits>
 
 #include "common.h"
 #include "mfma_stage.h"
+#include "mrc_host.h"
 
 namespace {
 
 constexpr int kMaxSide = 16384, kMinTile = 16, kMaxTile = 1024;
 constexpr int kThreads = 256;                    // four waves, both stages
 constexpr int kTile = 64;                        // 64 x 64 outputs per workgroup, both stages
-constexpr int kTN = kTile / 16;
 constexpr int kMaxBatch = 65535;                 // grid.z
 constexpr size_t kBudget = (size_t)256 << 20;    // the library's own choice of a batch keeps the workspace near this
 
@@ -51,34 +51,15 @@ template <typename S>
 __global__ __launch_bounds__(kThreads) void psd_rows_kernel(const S *__restrict__ raw, Tiling g, int t0,
                                                             const float *__restrict__ w1, int ldw1,
                                                             float *__restrict__ v_out) {
-    __shared__ __align__(16) float As[kTile * kLd];            // [64 rows of D][kLd]
-    __shared__ __align__(16) float Ms[kTile * kLd];            // [64 rows of W1][kLd]
-    const int T = g.T, H = g.H, N = 2 * g.H, half = T >> 1;
+    const int T = g.T, H = g.H, ldv = g.ldv, half = T >> 1;
     const int tile = t0 + blockIdx.z, ti = tile / g.tx, tj = tile - ti * g.tx;
     const S *__restrict__ base = raw + (long)ti * half * g.nx + (long)tj * half;   // the tile's first sample
-    const int r0 = blockIdx.y * kTile, q0 = blockIdx.x * kTile;
-    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
     const S first = raw[0];                                    // of the micrograph; every lane the same address
-
+    float *__restrict__ vt = v_out + (long)blockIdx.z * 2 * T * ldv;
     // rows and columns past the tile are fetched from its last row / column (inside the image); rows of W1 past 2H are
-    // staged as zeros
-    const SampleRows<S, kThreads> d{base, g.nx, T, T, r0, first, lds_ptr(As)};
-    const MatrixRows<kTile, kThreads, RowsFrom> m{w1, ldw1, N, T, T, RowsFrom{q0, N}, lds_ptr(Ms)};
-    const bool active = r0 + wave * 16 < T;                    // wave-uniform
-    f32x4 acc[kTN];
-#pragma unroll
-    for (int t = 0; t < kTN; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    k_loop(T, d, m, active,                                    // T is a multiple of 16: no K position is padded
-           [&](int ks) { multiply<BtRows, false>(acc, a_frag(As, wave, lr, lk), BtRows::frag(Ms, lr, lk), ks); });
-    if (active) {
-        float *__restrict__ vt = v_out + (long)blockIdx.z * 2 * T * g.ldv;
-        for_each_output(acc, r0, q0, wave, lk, lr, [&](int r, int q, float u) {
-            // the sine half goes below the cosine half; the address is formed outside the condition, so once per tile
-            const int part = q >= H;
-            float *p = vt + (long)(part * T + r) * g.ldv + (q - part * H);
-            if (r < T && q < N) *p = u;
-        });
-    }
+    // staged as zeros.  T is a multiple of 16: no K position is padded
+    sample_rows_body<false>(base, g.nx, T, T, first, w1, ldw1, 2 * H, blockIdx.y * kTile, blockIdx.x * kTile,
+                            [=](int r, int q, float u) { store_v_split(vt, ldv, T, H, r, q, u); });
 }
 
 // ---- stage 2: Q of the batch's tile blockIdx.z, rows u0 .., columns v0 .. ----------------------------------------------
@@ -86,30 +67,14 @@ __global__ __launch_bounds__(kThreads) void psd_rows_kernel(const S *__restrict_
 __global__ __launch_bounds__(kThreads) void psd_cols_kernel(const float *__restrict__ w2, int ldw2,
                                                             const float *__restrict__ v_in, Tiling g,
                                                             float *__restrict__ q_out) {
-    using VRows = KMajorRows<kTile, kThreads, true>;
-    __shared__ __align__(16) float As[2 * kTile * kLd];        // [64 rows u, then 64 rows T+u][kLd]
-    __shared__ __align__(16) float Bs[kKC * VRows::kLdb];      // [rows of V = K][kLdb]
-    const int T = g.T, H = g.H, K = 2 * g.T, ldv = g.ldv;
-    const float *__restrict__ vt = v_in + (long)blockIdx.z * K * ldv;
-    const int u0 = blockIdx.y * kTile, v0 = blockIdx.x * kTile;
-    const int tid = threadIdx.x, wave = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
-
+    const int T = g.T, H = g.H;
+    const float *__restrict__ vt = v_in + (long)blockIdx.z * 2 * T * g.ldv;
+    float *__restrict__ qt = q_out + (long)blockIdx.z * T * H;
     // A: rows u and T + u of W2.  B: columns H .. ldv-1 of V were never written: staged as zeros
-    const MatrixRows<2 * kTile, kThreads, RowPairs> a{w2, ldw2, K, K, K, RowPairs{u0, T}, lds_ptr(As)};
-    const VRows b{vt, ldv, K, v0, H, lds_ptr(Bs)};
-    const bool active = u0 + wave * 16 < T;                    // wave-uniform
-    f32x4 re[kTN], im[kTN];
-#pragma unroll
-    for (int t = 0; t < kTN; ++t) re[t] = im[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    k_loop(K, a, b, active, [&](int ks) {
-        multiply_pair<KMajor<kTile>>(re, im, a_frag(As, wave, lr, lk), KMajor<kTile>::frag(Bs, lr, lk), ks);
-    });
-    if (active) {
-        float *__restrict__ qt = q_out + (long)blockIdx.z * T * H;
-        for_each_output(re, im, u0, v0, wave, lk, lr, [&](int u, int v, float x, float y) {
-            if (u < T && v < H) qt[(long)u * H + v] = __fmaf_rn(y, y, __fmul_rn(x, x));
-        });
-    }
+    paired_rows_body(w2, ldw2, T, 2 * T, vt, g.ldv, H, blockIdx.y * kTile, blockIdx.x * kTile,
+                     [=](int u, int v, float x, float y) {
+                         if (u < T && v < H) qt[(long)u * H + v] = __fmaf_rn(y, y, __fmul_rn(x, x));
+                     });
 }
 
 // ---- the reduction: P (+)= the batch's Q in tile order ------------------------------------------------------------------
@@ -125,8 +90,7 @@ __global__ __launch_bounds__(256) void psd_sum_kernel(const float *__restrict__ 
 inline bool tile_ok(int T) { return T >= kMinTile && T <= kMaxTile && T % 16 == 0; }
 inline bool sizes_ok(int ny, int nx, int T) { return T <= ny && ny <= kMaxSide && T <= nx && nx <= kMaxSide; }
 inline long tiles_of(int ny, int nx, int T) { return (long)((ny - T) / (T / 2) + 1) * ((nx - T) / (T / 2) + 1); }
-inline int ldv_of(int T) { return (T / 2 + 1 + 3) & ~3; }
-inline size_t v_bytes(int T) { return sprk::align16((size_t)2 * T * ldv_of(T) * sizeof(float)); }
+inline size_t v_bytes(int T) { return sprk::align16((size_t)2 * T * sprk::roundup4(T / 2 + 1) * sizeof(float)); }
 inline size_t q_bytes(int T) { return sprk::align16((size_t)T * (T / 2 + 1) * sizeof(float)); }
 // tiles per batch: the caller's, or as many as keep the workspace within kBudget (one at least)
 inline int batch_of(long ntiles, int T, int max_batch) {
@@ -154,8 +118,7 @@ size_t sprk_psd_tiles_ws_bytes(int ny, int nx, int T, int max_batch) {
 
 int sprk_psd_tiles(const void *raw, int mode, int ny, int nx, int T, const float *w1, int ldw1, const float *w2, int ldw2,
                    int max_batch, float *p_out, void *ws, size_t ws_bytes, void *stream) {
-    SPRK_REQUIRE(mode == SPRK_MRC_INT8 || mode == SPRK_MRC_INT16 || mode == SPRK_MRC_FLOAT32 || mode == SPRK_MRC_UINT16,
-                 "psd_tiles: unsupported MRC mode %d (0, 1, 2 and 6 are)", mode);
+    SPRK_REQUIRE_MRC_MODE("psd_tiles", mode);
     SPRK_REQUIRE(tile_ok(T), "psd_tiles: tile side %d (a multiple of 16 in %d..%d)", T, kMinTile, kMaxTile);
     SPRK_REQUIRE(sizes_ok(ny, nx, T), "psd_tiles: a %dx%d image with tiles of %d (tile <= ny <= %d and tile <= nx <= %d)", ny,
                  nx, T, kMaxSide, kMaxSide);
@@ -166,26 +129,19 @@ int sprk_psd_tiles(const void *raw, int mode, int ny, int nx, int T, const float
     SPRK_REQUIRE(ldw2 >= 2 * T && ldw2 % 4 == 0,
                  "psd_tiles: row stride ldw2 %d of W2 (a multiple of 4, at least twice the tile = %d)", ldw2, 2 * T);
     SPRK_REQUIRE(raw && w1 && w2 && p_out, "psd_tiles: null pointer");
-    SPRK_REQUIRE(((uintptr_t)raw & 15) == 0 && ((uintptr_t)w1 & 15) == 0 && ((uintptr_t)w2 & 15) == 0 &&
-                     ((uintptr_t)p_out & 15) == 0 && ((uintptr_t)ws & 15) == 0,
+    SPRK_REQUIRE(sprk::aligned16(raw, w1, w2, p_out, ws),
                  "psd_tiles: the sample buffer, the matrices, the output and the workspace must start 16-byte aligned");
     if (int rc = sprk::check_ws("psd_tiles", ws, ws_bytes, sprk_psd_tiles_ws_bytes(ny, nx, T, max_batch))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int H = T / 2 + 1, n = T * H;
-    const Tiling g{T, H, (nx - T) / (T / 2) + 1, nx, ldv_of(T)};
+    const Tiling g{T, H, (nx - T) / (T / 2) + 1, nx, sprk::roundup4(T / 2 + 1)};
     const long ntiles = tiles_of(ny, nx, T);
     const int batch = batch_of(ntiles, T, max_batch);
     float *v = (float *)ws, *q = (float *)((char *)ws + (size_t)batch * v_bytes(T));
     // V and Q of a batch's tile k start k * 2T * ldv and k * T * H floats into their parts (the kernels' own strides)
     for (long t0 = 0; t0 < ntiles; t0 += batch) {
         const int nb = (int)(ntiles - t0 < batch ? ntiles - t0 : batch);
-        int rc;
-        switch (mode) {
-            case SPRK_MRC_INT8: rc = launch_rows<int8_t>(raw, g, (int)t0, nb, w1, ldw1, v, s); break;
-            case SPRK_MRC_INT16: rc = launch_rows<int16_t>(raw, g, (int)t0, nb, w1, ldw1, v, s); break;
-            case SPRK_MRC_FLOAT32: rc = launch_rows<float>(raw, g, (int)t0, nb, w1, ldw1, v, s); break;
-            default: rc = launch_rows<uint16_t>(raw, g, (int)t0, nb, w1, ldw1, v, s); break;
-        }
+        int rc = dispatch_mrc(mode, [&](auto t) { return launch_rows<decltype(t)>(raw, g, (int)t0, nb, w1, ldw1, v, s); });
         if (rc) return rc;
         hipLaunchKernelGGL(psd_cols_kernel, dim3(sprk::cdiv(H, kTile), sprk::cdiv(T, kTile), nb), dim3(kThreads), 0, s, w2,
                            ldw2, v, g, q);
