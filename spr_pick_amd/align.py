@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from . import ingest, micrograph_io, torch_ops
+from .fourier import shift_matrix, shift_matrix64, shift_matrix_device64      # the shift-and-crop operator
 
 logger = logging.getLogger("joint.align")
 MAX_SHIFT = torch_ops.ALIGN_MAX_SHIFT
@@ -70,82 +71,6 @@ def align_geometry(ny, nx, align_size=DEFAULT_ALIGN_SIZE):
     Sx = min(max(Sx, 64), nx // 64 * 64)
     Sy = min(max((2 * ny * Sx + nx) // (2 * nx), 2), ny)
     return Sy, Sx
-
-
-# ---- the shift-and-crop operator --------------------------------------------------------------------------------------------
-def _wrap_delta(B, delta):
-    delta = float(delta)
-    if not np.isfinite(delta):
-        raise ValueError("shift must be finite, got %r" % (delta,))
-    return delta - B * np.round(delta / B)                       # the operator has period B in delta
-
-
-def shift_matrix64(B, S, delta):
-    """Shift B periodic samples by ``delta`` samples (out(t) = in(t - delta)) and Fourier-crop them to S, as a real [S, B]
-    matrix in float64: (S/B) IDFT_S . crop . diag(e^{-2 pi i k delta / B}) . DFT_B with its sum over k in closed form, a
-    Dirichlet kernel at u = s B / S - b - delta.  With x = pi u / B:
-        M[s, b] = (1/B) sin(S x) / sin(x)                for odd S,
-        the same times cos(x)                            for even S (the +-S/2 term is shared at half weight each),
-        S / B where sin(x) == 0.
-    The integer part t = s B - b S of S u is reduced exactly (to (-S B / 2, S B / 2], and to (-B, B] for the numerator, whose
-    argument is folded about +-pi/2) before ``delta`` enters, so that the sines keep their relative accuracy.  Every row
-    sums to 1; ``delta`` = 0 is ``ingest.resample_matrix64`` (within 1e-12), the identity for S == B."""
-    B, S = int(B), int(S)
-    if not 2 <= S <= B:
-        raise ValueError("shift_matrix: 2 <= S <= B, got B = %d, S = %d" % (B, S))
-    delta = _wrap_delta(B, delta)
-    period = S * B
-    t = (np.arange(S, dtype=np.int64)[:, None] * B - np.arange(B, dtype=np.int64)[None, :] * S) % period
-    t = np.where(2 * t > period, t - period, t)
-    tn = t % (2 * B)
-    tn = np.where(tn > B, tn - 2 * B, tn)
-    w = (tn - S * delta) / B                                     # the numerator is sin(pi w)
-    w = w - 2.0 * np.round(w / 2.0)
-    w = np.where(w > 0.5, 1.0 - w, np.where(w < -0.5, -1.0 - w, w))
-    half = (np.pi / period) * (t - S * delta)
-    den = np.sin(half)
-    zero = den == 0
-    m = np.sin(np.pi * w) / np.where(zero, 1.0, den) / B
-    if S % 2 == 0:
-        m = m * np.cos(half)
-    return np.where(zero, S / B, m)
-
-
-def shift_matrix_device64(B, S, delta, device):
-    """``shift_matrix64`` built on ``device`` with torch, operation for operation: float64 [S, B].  (On the host, 40 frames
-    times two 4096^2 matrices of sines are tens of seconds.)  It differs from the NumPy one by what the two sines differ."""
-    B, S = int(B), int(S)
-    if not 2 <= S <= B:
-        raise ValueError("shift_matrix: 2 <= S <= B, got B = %d, S = %d" % (B, S))
-    delta = _wrap_delta(B, delta)
-    period = S * B
-    i64 = dict(dtype=torch.int64, device=device)
-    t = (torch.arange(S, **i64)[:, None] * B - torch.arange(B, **i64)[None, :] * S) % period
-    t = torch.where(2 * t > period, t - period, t)
-    tn = t % (2 * B)
-    tn = torch.where(tn > B, tn - 2 * B, tn)
-    w = (tn.double() - S * delta) / B
-    w = w - 2.0 * torch.round(w / 2.0)
-    w = torch.where(w > 0.5, 1.0 - w, torch.where(w < -0.5, -1.0 - w, w))
-    half = (np.pi / period) * (t.double() - S * delta)
-    den = torch.sin(half)
-    zero = den == 0
-    m = torch.sin(np.pi * w) / torch.where(zero, torch.ones_like(den), den) / B
-    if S % 2 == 0:
-        m = m * torch.cos(half)
-    return torch.where(zero, torch.full_like(m, S / B), m)
-
-
-def shift_matrix(B, S, delta, device=None):
-    """``shift_matrix64`` rounded to float32.  Without a device: the [S, B] array.  With one: an operand of
-    ``torch.ops.sprk.align_accumulate``, built there (``shift_matrix_device64``) and padded as
-    ``ingest.resample_matrix(B, S, device)`` pads: [roundup(S, 16), roundup(B, 4)] with exact zeros added."""
-    if device is None:
-        return shift_matrix64(B, S, delta).astype(np.float32)
-    B, S = int(B), int(S)
-    padded = torch.zeros((-(-S // 16) * 16, -(-B // 4) * 4), dtype=torch.float32, device=device)
-    padded[:S, :B] = shift_matrix_device64(B, S, delta, device).float()
-    return padded
 
 
 # ---- the estimate ----------------------------------------------------------------------------------------------------------

@@ -23,7 +23,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, ingest, micrograph_io, torch_ops
+from . import _lib, fourier, ingest, micrograph_io, torch_ops
 
 logger = logging.getLogger("joint.ctf")
 
@@ -60,15 +60,10 @@ def dft_matrices64(T):
     the same angle.  W2 = [[C, -S], [S, C]] with C[u, r] = cos(2 pi ((u r) mod T) / T), S the sine.  The integer product is
     reduced mod T before the division, so the angle is as exact as float64 can hold it whatever the size."""
     T = check_tile(T)
-    H = T // 2 + 1
     n = np.arange(T, dtype=np.int64)
-    a1 = (2.0 * np.pi / T) * ((np.arange(H, dtype=np.int64)[:, None] * n[None, :]) % T)
-    a2 = (2.0 * np.pi / T) * ((n[:, None] * n[None, :]) % T)
+    a2 = fourier.phase(n, n, T)
     C, S = np.cos(a2), np.sin(a2)
-    return np.concatenate([np.cos(a1), np.sin(a1)]), np.block([[C, -S], [S, C]])
-
-
-_matrices = {}
+    return fourier.half_plane64(T // 2 + 1, T), np.block([[C, -S], [S, C]])
 
 
 def dft_matrices(T, device=None):
@@ -76,18 +71,7 @@ def dft_matrices(T, device=None):
     ``torch.ops.sprk.psd_tiles``, contiguous tensors [roundup(2H, 16), T] and [2T, 2T] on that device whose added rows
     are exact zeros (T is a multiple of 16, so no column is added), built once per (T, device)."""
     T = check_tile(T)
-    key = (T, None if device is None else str(torch.device(device)))
-    if key not in _matrices:
-        if device is None:
-            _matrices[key] = tuple(m.astype(np.float32) for m in dft_matrices64(T))
-        else:
-            out = []
-            for m, shape in zip(dft_matrices(T), torch_ops.psd_matrix_shapes(T)):
-                padded = np.zeros(shape, dtype=np.float32)
-                padded[:m.shape[0], :m.shape[1]] = m
-                out.append(torch.from_numpy(padded).to(device))
-            _matrices[key] = tuple(out)
-    return _matrices[key]
+    return fourier.operands(dft_matrices64, (T,), torch_ops.psd_matrix_shapes(T), device)
 
 
 def psd_sum(path_or_raw, tile, device="cuda", max_batch=0):

@@ -19,7 +19,8 @@ four matrices carry no shift and are built once per geometry; per frame only ``g
 import numpy as np
 import torch
 
-from . import torch_ops
+from . import fourier, torch_ops
+from .fourier import column_weights, kept_rows, wrap_delta
 
 KV_RANGE = (200.0, 300.0)
 _BLOCK = 1 << 23                                 # entries of a matrix built at a time (float64 and int64 temporaries)
@@ -56,52 +57,13 @@ def _check_sizes(ny, nx, by, bx):
 
 
 # ---- the kept frequencies and the four matrices -------------------------------------------------------------------------------
-def kept_rows(B, S):
-    """-> (k int64 [Ku], weights float64 [Ku]): the row frequencies of B samples that an output of S keeps, -h .. h with
-    h = S // 2.  Even S: Ku = S + 1 and the rows +-h weigh 1/2 each (also for S == B, where they are one frequency of the
-    frame).  Odd S: Ku = S, every weight 1."""
-    B, S = int(B), int(S)
-    if not 2 <= S <= B:
-        raise ValueError("kept_rows: 2 <= S <= B, got B = %d, S = %d" % (B, S))
-    h = S // 2
-    k = np.arange(-h, h + 1, dtype=np.int64)
-    return k, np.where((np.abs(k) == h) & (S % 2 == 0), 0.5, 1.0)
-
-
-def column_weights(bx):
-    """-> float64 [Hs]: what the last inverse stage weighs column v = 0 .. bx // 2 with: 1 at v = 0 and, even bx, at bx / 2"""
-    v = np.arange(bx // 2 + 1)
-    return np.where((v == 0) | ((bx % 2 == 0) & (v == bx // 2)), 1.0, 2.0)
-
-
 def spectrum_matrices64(ny, nx, by, bx):
-    """The four real matrices of ``align_spectrum`` / ``align_synthesize`` in float64: W1 [2Hs, nx] the half-plane DFT along
-    the rows of a frame, W2 [2Ku, 2ny] the DFT along its columns at the kept rows, W3 [2by, 2Ku] the inverse along the
-    columns with the row weights and 1 / ny, W4 [bx, 2Hs] the inverse along the rows with the column weights and 1 / nx.
-    Every integer phase is reduced mod its period before the division."""
+    """The four real matrices of ``align_spectrum`` / ``align_synthesize`` in float64 (``fourier.four_stage64``): W1 [2Hs, nx]
+    the half-plane DFT along the rows of a frame, W2 [2Ku, 2ny] the DFT along its columns at the kept rows, W3 [2by, 2Ku]
+    the inverse along the columns with the row weights and 1 / ny, W4 [bx, 2Hs] the inverse along the rows with the column
+    weights and 1 / nx."""
     ny, nx, by, bx = _check_sizes(ny, nx, by, bx)
-    k, a = kept_rows(ny, by)
-    v = np.arange(bx // 2 + 1, dtype=np.int64)
-    a1 = (2.0 * np.pi / nx) * ((v[:, None] * np.arange(nx, dtype=np.int64)[None, :]) % nx)
-    a2 = (2.0 * np.pi / ny) * ((k[:, None] * np.arange(ny, dtype=np.int64)[None, :]) % ny)
-    a3 = (2.0 * np.pi / by) * ((np.arange(by, dtype=np.int64)[:, None] * k[None, :]) % by)
-    a4 = (2.0 * np.pi / bx) * ((np.arange(bx, dtype=np.int64)[:, None] * v[None, :]) % bx)
-    a = a[None, :] / ny
-    w = column_weights(bx)[None, :] / nx
-    C2, S2, C3, S3 = np.cos(a2), np.sin(a2), a * np.cos(a3), a * np.sin(a3)
-    return (np.concatenate([np.cos(a1), np.sin(a1)]), np.block([[C2, -S2], [-S2, -C2]]), np.block([[C3, -S3], [S3, C3]]),
-            np.concatenate([w * np.cos(a4), -w * np.sin(a4)], axis=1))
-
-
-def _trig_blocks(rows, cols, period, device):
-    """cos and sin of 2 pi (rows x cols mod period) / period in float64 on ``device``, a block of rows at a time:
-    yields (slice, cos, sin)"""
-    cols = torch.as_tensor(cols, dtype=torch.int64, device=device)
-    step = max(1, _BLOCK // max(1, len(cols)))
-    for r0 in range(0, len(rows), step):
-        r = torch.as_tensor(rows[r0:r0 + step], dtype=torch.int64, device=device)
-        ang = ((r[:, None] * cols[None, :]) % period).double() * (2.0 * np.pi / period)
-        yield slice(r0, r0 + len(r)), torch.cos(ang), torch.sin(ang)
+    return fourier.four_stage64(ny, nx, by, bx, ny, nx)
 
 
 _matrices = {}
@@ -111,7 +73,8 @@ def spectrum_matrices(ny, nx, by, bx, device):
     """``spectrum_matrices64`` rounded to float32 as the operands of the two operators: contiguous tensors on ``device``,
     columns rounded up to a multiple of 4 with exact zeros (``torch_ops.align_spectrum_shapes``).  Built there with torch in
     row blocks (W2 of a 16384-pixel frame is 4.3 GB in float32; its float64 form never exists), operation for operation as
-    the NumPy ones, once per (ny, nx, by, bx, device): the two most recent geometries stay cached."""
+    the NumPy ones, once per (ny, nx, by, bx, device): the two most recent geometries stay cached (a cache of its own: the
+    one of ``fourier.operands`` has no bound)."""
     ny, nx, by, bx = _check_sizes(ny, nx, by, bx)
     device = torch.device(device)
     key = (ny, nx, by, bx, str(device))
@@ -124,18 +87,18 @@ def spectrum_matrices(ny, nx, by, bx, device):
     w = torch.as_tensor(column_weights(bx) / nx, device=device)[None, :]
     W1, W2, W3, W4 = (torch.zeros(s, dtype=torch.float32, device=device)
                       for s in torch_ops.align_spectrum_shapes(ny, nx, by, bx, Ku)[:4])
-    for s, c, sn in _trig_blocks(v, np.arange(nx), nx, device):
+    for s, c, sn in fourier.trig_blocks(v, np.arange(nx), nx, device, _BLOCK):
         W1[s, :nx], W1[Hs + s.start:Hs + s.stop, :nx] = c.float(), sn.float()
-    for s, c, sn in _trig_blocks(k, np.arange(ny), ny, device):
+    for s, c, sn in fourier.trig_blocks(k, np.arange(ny), ny, device, _BLOCK):
         lo = slice(Ku + s.start, Ku + s.stop)
         W2[s, :ny], W2[s, ny:2 * ny] = c.float(), (-sn).float()
         W2[lo, :ny], W2[lo, ny:2 * ny] = (-sn).float(), (-c).float()
-    for s, c, sn in _trig_blocks(np.arange(by), k, by, device):
+    for s, c, sn in fourier.trig_blocks(np.arange(by), k, by, device, _BLOCK):
         lo = slice(by + s.start, by + s.stop)
         c, sn = a * c, a * sn
         W3[s, :Ku], W3[s, Ku:2 * Ku] = c.float(), (-sn).float()
         W3[lo, :Ku], W3[lo, Ku:2 * Ku] = sn.float(), c.float()
-    for s, c, sn in _trig_blocks(np.arange(bx), v, bx, device):
+    for s, c, sn in fourier.trig_blocks(np.arange(bx), v, bx, device, _BLOCK):
         W4[s, :Hs], W4[s, Hs:2 * Hs] = (w * c).float(), (-(w * sn)).float()
     while len(_matrices) >= 2:
         _matrices.pop(next(iter(_matrices)))
@@ -185,18 +148,17 @@ def dose_filter64(ny, nx, by, bx, apix, dose, pre_dose, kv, Z):
 def frame_filter64(phi, ny, nx, by, bx, dy, dx):
     """G = phi e^{-2 pi i (k dy / ny + v dx / nx)}: complex128 [Ku, Hs] for one frame's float64 phi [Ku, Hs] (or 1.0) and its
     shift (dy, dx) in raw pixels, out(t) = in(t - d)"""
-    from .align import _wrap_delta
     k, _ = kept_rows(ny, by)
     v = np.arange(bx // 2 + 1, dtype=np.float64)
-    py = np.exp(1j * ((-2.0 * np.pi / ny) * (k * _wrap_delta(ny, dy))))
-    px = np.exp(1j * ((-2.0 * np.pi / nx) * (v * _wrap_delta(nx, dx))))
+    py = np.exp(1j * ((-2.0 * np.pi / ny) * (k * wrap_delta(ny, dy))))
+    px = np.exp(1j * ((-2.0 * np.pi / nx) * (v * wrap_delta(nx, dx))))
     return phi * (py[:, None] * px[None, :])
 
 
 def pack_filter(G):
     """complex [Ku, Hs] -> the float32 operand g [2Ku, roundup(Hs, 4)] (NumPy): real rows over imaginary rows, rounded once"""
     Ku, Hs = G.shape
-    g = np.zeros((2 * Ku, -(-Hs // 4) * 4), dtype=np.float32)
+    g = np.zeros((2 * Ku, torch_ops._up4(Hs)), dtype=np.float32)
     g[:Ku, :Hs], g[Ku:, :Hs] = G.real.astype(np.float32), G.imag.astype(np.float32)
     return g
 
@@ -229,9 +191,8 @@ class FrameFilters:
 
     def filter64(self, f, dy, dx):
         """-> (Gr, Gi) float64 [Ku, Hs] on the device, before the rounding"""
-        from .align import _wrap_delta
-        ay = (-2.0 * np.pi / self.ny) * (self._k * _wrap_delta(self.ny, dy))
-        ax = (-2.0 * np.pi / self.nx) * (self._v * _wrap_delta(self.nx, dx))
+        ay = (-2.0 * np.pi / self.ny) * (self._k * wrap_delta(self.ny, dy))
+        ax = (-2.0 * np.pi / self.nx) * (self._v * wrap_delta(self.nx, dx))
         cy, sy, cx, sx = torch.cos(ay)[:, None], torch.sin(ay)[:, None], torch.cos(ax)[None, :], torch.sin(ax)[None, :]
         phi = self.phi64(f)
         return phi * (cy * cx - sy * sx), phi * (cy * sx + sy * cx)
@@ -239,7 +200,7 @@ class FrameFilters:
     def g(self, f, dy, dx):
         """-> float32 [2Ku, roundup(Hs, 4)] on the device: a fresh tensor (the call that reads it is only enqueued)"""
         gr, gi = self.filter64(f, dy, dx)
-        out = torch.zeros((2 * self.Ku, -(-self.Hs // 4) * 4), dtype=torch.float32, device=self.device)
+        out = torch.zeros((2 * self.Ku, torch_ops._up4(self.Hs)), dtype=torch.float32, device=self.device)
         out[:self.Ku, :self.Hs], out[self.Ku:, :self.Hs] = gr.float(), gi.float()
         return out
 
@@ -252,7 +213,7 @@ def sum_frames_weighted(movie, by, bx, shifts_y, shifts_x, apix, dose, pre_dose=
     dev = movie._reader.device
     W1, W2, W3, W4 = spectrum_matrices(h.ny, h.nx, by, bx, dev)
     filters = FrameFilters(h.ny, h.nx, by, bx, h.nz, dev, apix, dose, pre_dose, kv)
-    F = torch.empty((2 * filters.Ku, -(-filters.Hs // 4) * 4), dtype=torch.float32, device=dev)
+    F = torch.empty((2 * filters.Ku, torch_ops._up4(filters.Hs)), dtype=torch.float32, device=dev)
     for k in range(h.nz):
         raw = movie.frame(k)
         torch.ops.sprk.align_spectrum(raw, h.mode, h.ny, h.nx, W1, W2, filters.g(k, shifts_y[k], shifts_x[k]), movie.anchor,

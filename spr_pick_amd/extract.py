@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, ctf as ctf_mod, export, ingest, micrograph_io, picks as picks_mod, torch_ops
+from . import _lib, ctf as ctf_mod, export, fourier, ingest, micrograph_io, picks as picks_mod, torch_ops
 
 logger = logging.getLogger("joint.extract")
 OK, OUTSIDE, FLAT = 0, 1, 2                     # status codes of sprk_extract_boxes
@@ -67,16 +67,13 @@ def crop_matrix64(B, S):
         raise ValueError("crop_matrix: 2 <= S <= B, got B = %d, S = %d" % (B, S))
     if S == B:
         return np.eye(B)
-    h, period = S // 2, S * B
+    h = S // 2
     base = np.arange(S, dtype=np.int64)[:, None] * B - np.arange(B, dtype=np.int64)[None, :] * S
     acc = np.ones((S, B), dtype=np.float64)                      # k = 0
     for k in range(1, h + 1):
         w = 1.0 if (S % 2 or k < h) else 0.5                     # both signs: 2 w cos
-        acc += (2.0 * w) * np.cos((2.0 * np.pi / period) * ((k * base) % period))
+        acc += (2.0 * w) * np.cos(fourier.reduced(k * base, S * B))
     return acc / B
-
-
-_matrices = {}
 
 
 def crop_matrix(B, S, device=None):
@@ -84,15 +81,7 @@ def crop_matrix(B, S, device=None):
     ``torch.ops.sprk.extract_scale``, a contiguous tensor [roundup(S, 16), roundup(B, 4)] on that device whose added
     rows and columns are exact zeros, built once per (B, S, device)."""
     B, S = int(B), int(S)
-    key = (B, S, None if device is None else str(torch.device(device)))
-    if key not in _matrices:
-        if device is None:
-            _matrices[key] = crop_matrix64(B, S).astype(np.float32)
-        else:
-            padded = np.zeros((-(-S // 16) * 16, -(-B // 4) * 4), dtype=np.float32)
-            padded[:S, :B] = crop_matrix(B, S)
-            _matrices[key] = torch.from_numpy(padded).to(device)
-    return _matrices[key]
+    return fourier.operands(crop_matrix64, (B, S), torch_ops.crop_matrix_shape(B, S), device)
 
 
 def check_filter(box, scale=None, bg_radius=None):
@@ -113,25 +102,11 @@ def filter_matrices64(B, S):
     """The four real matrices of ``torch.ops.sprk.extract_filter`` in float64 (include/sprk.h), h = S/2, Hs = h + 1, Ku =
     S + 1, k = -h .. h: W1 [2Hs, B] the half-plane DFT along the rows of the box, W2 [2Ku, 2B] the DFT along its columns at
     the kept k, W3 [2S, 2Ku] the inverse along the columns with the weights a_k (1/2 at k = +-h), W4 [S, 2Hs] the inverse
-    along the rows with w_v (1 at v = 0 and h, else 2) and 1/B^2.  Every integer phase is reduced mod B or S before the
-    division.  With a filter of ones the four stages are ``crop_matrix64(B, S)`` applied on both sides."""
+    along the rows with w_v (1 at v = 0 and h, else 2) and 1/B^2: ``fourier.four_stage64`` of a square box.  With a filter of
+    ones the four stages are ``crop_matrix64(B, S)`` applied on both sides."""
     B, S = int(B), int(S)
     check_filter(B, S)
-    h = S // 2
-    v = np.arange(h + 1, dtype=np.int64)
-    k = np.arange(-h, h + 1, dtype=np.int64)
-    a1 = (2.0 * np.pi / B) * ((v[:, None] * np.arange(B, dtype=np.int64)[None, :]) % B)
-    a2 = (2.0 * np.pi / B) * ((k[:, None] * np.arange(B, dtype=np.int64)[None, :]) % B)
-    a3 = (2.0 * np.pi / S) * ((np.arange(S, dtype=np.int64)[:, None] * k[None, :]) % S)
-    a4 = (2.0 * np.pi / S) * ((np.arange(S, dtype=np.int64)[:, None] * v[None, :]) % S)
-    a = np.where(np.abs(k) == h, 0.5, 1.0)[None, :]
-    w = np.where((v == 0) | (v == h), 1.0, 2.0)[None, :] / (float(B) * B)
-    C2, S2, C3, S3 = np.cos(a2), np.sin(a2), a * np.cos(a3), a * np.sin(a3)
-    return (np.concatenate([np.cos(a1), np.sin(a1)]), np.block([[C2, -S2], [-S2, -C2]]), np.block([[C3, -S3], [S3, C3]]),
-            np.concatenate([w * np.cos(a4), -w * np.sin(a4)], axis=1))
-
-
-_filter_matrices = {}
+    return fourier.four_stage64(B, B, S, S, 1.0, float(B) * B)
 
 
 def filter_matrices(B, S, device=None):
@@ -139,18 +114,7 @@ def filter_matrices(B, S, device=None):
     ``torch.ops.sprk.extract_filter``, contiguous tensors on that device whose columns are rounded up to a multiple of 4
     with exact zeros (``torch_ops.extract_filter_shapes``), built once per (B, S, device)."""
     B, S = int(B), int(S)
-    key = (B, S, None if device is None else str(torch.device(device)))
-    if key not in _filter_matrices:
-        if device is None:
-            _filter_matrices[key] = tuple(m.astype(np.float32) for m in filter_matrices64(B, S))
-        else:
-            out = []
-            for m, shape in zip(filter_matrices(B, S), torch_ops.extract_filter_shapes(B, S)):
-                padded = np.zeros(shape, dtype=np.float32)
-                padded[:m.shape[0], :m.shape[1]] = m
-                out.append(torch.from_numpy(padded).to(device))
-            _filter_matrices[key] = tuple(out)
-    return _filter_matrices[key]
+    return fourier.operands(filter_matrices64, (B, S), torch_ops.extract_filter_shapes(B, S)[:4], device)
 
 
 def extract_particles(path_or_raw, xy, box, bin=1, bg_radius=None, normalize=True, invert=False, device="cuda", scale=None,

@@ -37,6 +37,7 @@ import torch
 
 from . import micrograph_io, sampler as sampler_mod, torch_ops
 from .datasets import DetectionDataset
+from .fourier import resample_matrix, resample_matrix64          # the operands of --ftbin
 
 MAX_BIN = torch_ops.INGEST_MAX_BIN
 MAX_FLATTEN = torch_ops.INGEST_MAX_FLATTEN
@@ -104,53 +105,6 @@ def resample_geometry(ny, nx, F):
     if by < 2 or bx < 2:
         raise ValueError("a %dx%d image resampled by %s leaves %dx%d pixels (at least 2 a side)" % (ny, nx, F, by, bx))
     return by, bx
-
-
-def resample_matrix64(B, S):
-    """The Fourier crop of B samples to S as a real [S, B] matrix in float64, IDFT_S . crop . DFT_B scaled by S / B: the
-    operator of ``extract.crop_matrix64`` with its sum over k in closed form (a Dirichlet kernel).  With the phase
-    t = (s B - b S) mod (S B) in integers and theta / 2 = pi t / (S B):
-        M[s, b] = (1/B) sin(pi (t mod 2B) / B) / sin(theta / 2)              for odd S,
-        the same times cos(theta / 2)                                        for even S (the Nyquist term is shared),
-        S / B where t == 0;
-    t is taken in (-S B / 2, S B / 2] and then t mod 2B in (-B, B]: M keeps its value, and the sines of small arguments
-    their relative accuracy.  Every row sums to 1.  S == B is the identity and is returned as such.
-    Not the bits of ``crop_matrix64`` (they differ by a few 1e-13): that one stays the contract of ``joint extract --scale``."""
-    B, S = int(B), int(S)
-    if not 2 <= S <= B:
-        raise ValueError("resample_matrix: 2 <= S <= B, got B = %d, S = %d" % (B, S))
-    if S == B:
-        return np.eye(B)
-    period = S * B
-    t = (np.arange(S, dtype=np.int64)[:, None] * B - np.arange(B, dtype=np.int64)[None, :] * S) % period
-    zero = t == 0
-    t = np.where(2 * t > period, t - period, t)                  # numerator and denominator change sign together
-    tn = t % (2 * B)
-    tn = np.where(tn > B, tn - 2 * B, tn)
-    half = (np.pi / period) * t
-    m = np.sin((np.pi / B) * tn) / np.sin(np.where(zero, 1.0, half)) / B
-    if S % 2 == 0:
-        m = m * np.cos(half)
-    return np.where(zero, S / B, m)
-
-
-_resample_matrices = {}
-
-
-def resample_matrix(B, S, device=None):
-    """``resample_matrix64`` rounded to float32.  Without a device: the [S, B] array.  With one: an operand of
-    ``torch.ops.sprk.ingest_resample``, a contiguous tensor [roundup(S, 16), roundup(B, 4)] on that device whose added
-    rows and columns are exact zeros, built once per (B, S, device)."""
-    B, S = int(B), int(S)
-    key = (B, S, None if device is None else str(torch.device(device)))
-    if key not in _resample_matrices:
-        if device is None:
-            _resample_matrices[key] = resample_matrix64(B, S).astype(np.float32)
-        else:
-            padded = np.zeros((-(-S // 16) * 16, -(-B // 4) * 4), dtype=np.float32)
-            padded[:S, :B] = resample_matrix(B, S)
-            _resample_matrices[key] = torch.from_numpy(padded).to(device)
-    return _resample_matrices[key]
 
 
 def to_raw(x, y, ny, nx, by, bx):

@@ -556,9 +556,55 @@ MRC_ITEMSIZE = {0: 1, 1: 2, 2: 4, 6: 2}          # bytes per sample of the MRC m
 INGEST_MAX_BIN = 16                              # SPRK_INGEST_MAX_BIN
 
 
-def _binned_shape(mode, ny, nx, bin):
+def _up4(n):
+    return -(-int(n) // 4) * 4
+
+
+def _up16(n):
+    return -(-int(n) // 16) * 16
+
+
+def crop_matrix_shape(B, S):
+    """-> the shape of the operand that holds an [S, B] crop or shift matrix: [roundup(S, 16), roundup(B, 4)]"""
+    return _up16(S), _up4(B)
+
+
+# the operand checks that the operators below share: ``who`` is the operator's name, ``like`` the tensor whose device counts
+def _mode_check(who, mode):
     if mode not in MRC_ITEMSIZE:
-        raise _lib.SprkError("ingest_bin: unsupported MRC mode %d" % mode)
+        raise _lib.SprkError("%s: unsupported MRC mode %d" % (who, mode))
+
+
+def _raw_check(who, raw, mode, ny, nx, contiguous=False):
+    """after ``_mode_check``, which every operator makes first"""
+    if (raw.dtype != torch.uint8 or raw.dim() != 1 or (contiguous and not raw.is_contiguous())
+            or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]):
+        raise _lib.SprkError("%s: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
+                             % (who, ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+
+
+def _range_check(who, rng, like):
+    if rng.dtype != torch.float32 or rng.numel() != 2 or not rng.is_contiguous() or rng.device != like.device:
+        raise _lib.SprkError("%s: range must be a contiguous float32 tensor of 2 elements on %s, got %s %s on %s"
+                             % (who, like.device, rng.dtype, tuple(rng.shape), rng.device))
+
+
+def _xy_check(who, xy, like):
+    if xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or xy.device != like.device:
+        raise _lib.SprkError("%s: xy must be an int32 tensor [P, 2] on %s, got %s %s on %s"
+                             % (who, like.device, xy.dtype, tuple(xy.shape), xy.device))
+
+
+def _matrix_check(who, name, m, shape, like, of=None):
+    """m: float32 of ``shape`` on the device of ``like``; ``of``: what builds it ("matrix of ingest.resample_matrix(...)")"""
+    if m.dtype != torch.float32 or tuple(m.shape) != tuple(shape) or m.device != like.device:
+        what = "float32 [%d, %d]" % tuple(shape) if of is None else "the float32 %s, [%d, %d]" % (of, *shape)
+        raise _lib.SprkError("%s: %s must be %s on %s, got %s %s on %s"
+                             % (who, name, what, like.device, m.dtype, tuple(m.shape), m.device))
+
+
+def _binned_shape(mode, ny, nx, bin):
+    _mode_check("ingest_bin", mode)
     if not 1 <= bin <= INGEST_MAX_BIN or ny // bin < 1 or nx // bin < 1:
         raise _lib.SprkError("ingest_bin: bin factor %d on a %dx%d image (1..%d, at least one block)"
                              % (bin, ny, nx, INGEST_MAX_BIN))
@@ -573,9 +619,7 @@ def net_size(by, bx):
 def _ingest_bin(raw, mode, ny, nx, bin):
     """raw: uint8 CUDA tensor holding the file's ny*nx samples -> (binned float32 [by, bx], range float32 [2])."""
     by, bx = _binned_shape(mode, ny, nx, bin)
-    if raw.dtype != torch.uint8 or raw.dim() != 1 or not raw.is_contiguous() or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
-        raise _lib.SprkError("ingest_bin: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
-                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+    _raw_check("ingest_bin", raw, mode, ny, nx, contiguous=True)
     L = _lib.lib()
     binned, rng = _f32(raw, (by, bx)), _f32(raw, (2,))
     ws = _ws(L.sprk_ingest_ws_bytes(ny, nx, bin), raw)
@@ -602,9 +646,7 @@ def _ingest_finish(binned, rng, want_u8, want_net):
     if not (want_u8 or want_net):
         raise _lib.SprkError("ingest_finish: neither output asked for")
     su, sn = _finish_shapes(binned, want_u8, want_net)
-    if rng.dtype != torch.float32 or rng.numel() != 2 or not rng.is_contiguous() or rng.device != binned.device:
-        raise _lib.SprkError("ingest_finish: range must be a contiguous float32 tensor of 2 elements on %s, got %s %s on %s"
-                             % (binned.device, rng.dtype, tuple(rng.shape), rng.device))
+    _range_check("ingest_finish", rng, binned)
     binned = binned.contiguous()
     u8 = torch.empty(su, dtype=torch.uint8, device=binned.device)
     net = _f32(binned, sn)
@@ -627,9 +669,7 @@ def _clip_check(binned, rng, k_lo, k_hi):
     if binned.dim() != 2 or binned.dtype != torch.float32 or binned.numel() < 1:
         raise _lib.SprkError("ingest_clip: binned must be a non-empty 2-D float32 tensor, got %s %s"
                              % (binned.dtype, tuple(binned.shape)))
-    if rng.dtype != torch.float32 or rng.numel() != 2 or not rng.is_contiguous() or rng.device != binned.device:
-        raise _lib.SprkError("ingest_clip: range must be a contiguous float32 tensor of 2 elements on %s, got %s %s on %s"
-                             % (binned.device, rng.dtype, tuple(rng.shape), rng.device))
+    _range_check("ingest_clip", rng, binned)
     if not 0 <= k_lo <= k_hi <= binned.numel() - 1:
         raise _lib.SprkError("ingest_clip: ranks %d, %d of %d elements (0 <= k_lo <= k_hi <= n-1)"
                              % (k_lo, k_hi, binned.numel()))
@@ -664,9 +704,7 @@ def _flatten_check(binned, rng, R):
     if binned.dim() != 2 or binned.dtype != torch.float32 or binned.numel() < 1:
         raise _lib.SprkError("ingest_flatten: binned must be a non-empty 2-D float32 tensor, got %s %s"
                              % (binned.dtype, tuple(binned.shape)))
-    if rng.dtype != torch.float32 or rng.numel() != 2 or not rng.is_contiguous() or rng.device != binned.device:
-        raise _lib.SprkError("ingest_flatten: range must be a contiguous float32 tensor of 2 elements on %s, got %s %s on %s"
-                             % (binned.device, rng.dtype, tuple(rng.shape), rng.device))
+    _range_check("ingest_flatten", rng, binned)
     if not 1 <= R <= INGEST_MAX_FLATTEN:
         raise _lib.SprkError("ingest_flatten: radius %d (1..%d)" % (R, INGEST_MAX_FLATTEN))
 
@@ -697,19 +735,14 @@ INGEST_MAX_SIDE = 16384                          # sprk_ingest_resample: the lon
 
 
 def _resample_check(raw, mode, ny, nx, by, bx, my, mx):
-    if mode not in MRC_ITEMSIZE:
-        raise _lib.SprkError("ingest_resample: unsupported MRC mode %d" % mode)
+    _mode_check("ingest_resample", mode)
     if not (2 <= by <= ny <= INGEST_MAX_SIDE and 2 <= bx <= nx <= INGEST_MAX_SIDE):
         raise _lib.SprkError("ingest_resample: a %dx%d image resampled to %dx%d (2 <= by <= ny <= %d and 2 <= bx <= nx <= %d)"
                              % (ny, nx, by, bx, INGEST_MAX_SIDE, INGEST_MAX_SIDE))
-    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
-        raise _lib.SprkError("ingest_resample: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
-                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+    _raw_check("ingest_resample", raw, mode, ny, nx)
     for name, m, S, B in (("my", my, by, ny), ("mx", mx, bx, nx)):
-        shape = (-(-S // 16) * 16, -(-B // 4) * 4)
-        if m.dtype != torch.float32 or tuple(m.shape) != shape or m.device != raw.device:
-            raise _lib.SprkError("ingest_resample: %s must be the float32 matrix of ingest.resample_matrix(%d, %d), [%d, %d] "
-                                 "on %s, got %s %s on %s" % (name, B, S, *shape, raw.device, m.dtype, tuple(m.shape), m.device))
+        _matrix_check("ingest_resample", name, m, crop_matrix_shape(B, S), raw,
+                      "matrix of ingest.resample_matrix(%d, %d)" % (B, S))
 
 
 def _ingest_resample(raw, mode, ny, nx, by, bx, my, mx):
@@ -807,30 +840,17 @@ _register("align_accumulate", "(Tensor raw, int mode, int ny, int nx, int by, in
 
 
 # dose-weighted sums (dose.py: csrc/alignsum.hip): the movie accumulated in Fourier space
-def _up4(n):
-    return -(-int(n) // 4) * 4
-
-
 def align_spectrum_shapes(ny, nx, by, bx, Ku):
     """-> the shapes of w1, w2, w3, w4 and of F / g for a [ny, nx] frame, a [by, bx] sum and Ku kept rows (Hs = bx // 2 + 1)"""
     Hs = bx // 2 + 1
     return ((2 * Hs, _up4(nx)), (2 * Ku, _up4(2 * ny)), (2 * by, _up4(2 * Ku)), (bx, _up4(2 * Hs)), (2 * Ku, _up4(Hs)))
 
 
-def _matrix_check(who, name, m, shape, like):
-    if m.dtype != torch.float32 or tuple(m.shape) != tuple(shape) or m.device != like.device:
-        raise _lib.SprkError("%s: %s must be float32 [%d, %d] on %s, got %s %s on %s"
-                             % (who, name, shape[0], shape[1], like.device, m.dtype, tuple(m.shape), m.device))
-
-
 def _align_spectrum_check(raw, mode, ny, nx, w1, w2, g, F):
-    if mode not in MRC_ITEMSIZE:
-        raise _lib.SprkError("align_spectrum: unsupported MRC mode %d" % mode)
+    _mode_check("align_spectrum", mode)
     if not (2 <= ny <= INGEST_MAX_SIDE and 2 <= nx <= INGEST_MAX_SIDE):
         raise _lib.SprkError("align_spectrum: a %dx%d frame (2 <= ny, nx <= %d)" % (ny, nx, INGEST_MAX_SIDE))
-    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
-        raise _lib.SprkError("align_spectrum: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
-                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+    _raw_check("align_spectrum", raw, mode, ny, nx)
     if w1.dim() != 2 or w2.dim() != 2 or w1.shape[0] % 2 or w2.shape[0] % 2:
         raise _lib.SprkError("align_spectrum: w1 must be [2Hs, roundup(nx, 4)] and w2 [2Ku, roundup(2ny, 4)], got %s and %s"
                              % (tuple(w1.shape), tuple(w2.shape)))
@@ -905,13 +925,10 @@ FIX_MAX_RADIUS = 8                               # SPRK_FIX_MAX_RADIUS: larger v
 
 
 def _movie_correct_check(raw, mode, ny, nx, gain, dark, fix, out, sum):
-    if mode not in MRC_ITEMSIZE:
-        raise _lib.SprkError("movie_correct: unsupported MRC mode %d" % mode)
+    _mode_check("movie_correct", mode)
     if not (1 <= ny <= INGEST_MAX_SIDE and 1 <= nx <= INGEST_MAX_SIDE):
         raise _lib.SprkError("movie_correct: a %dx%d frame (both sides in 1..%d)" % (ny, nx, INGEST_MAX_SIDE))
-    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
-        raise _lib.SprkError("movie_correct: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
-                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+    _raw_check("movie_correct", raw, mode, ny, nx)
     for name, t, dtype in (("gain", gain, torch.float32), ("dark", dark, torch.float32), ("fix", fix, torch.uint8),
                            ("out", out, torch.float32), ("sum", sum, torch.float32)):
         if t is not None and (t.dtype != dtype or tuple(t.shape) != (ny, nx) or t.device != raw.device):
@@ -1156,17 +1173,12 @@ def extract_side(box, bin, bg_radius=0):
 
 
 def _extract_shapes(raw, mode, ny, nx, xy, box, bin, bg_radius):
-    if mode not in MRC_ITEMSIZE:
-        raise _lib.SprkError("extract_boxes: unsupported MRC mode %d" % mode)
+    _mode_check("extract_boxes", mode)
     b = extract_side(box, bin, bg_radius)
     if ny < 1 or nx < 1 or ny * nx >= 1 << 31:
         raise _lib.SprkError("extract_boxes: bad image size %dx%d" % (ny, nx))
-    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
-        raise _lib.SprkError("extract_boxes: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
-                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
-    if xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or xy.device != raw.device:
-        raise _lib.SprkError("extract_boxes: xy must be an int32 tensor [P, 2] on %s, got %s %s on %s"
-                             % (raw.device, xy.dtype, tuple(xy.shape), xy.device))
+    _raw_check("extract_boxes", raw, mode, ny, nx)
+    _xy_check("extract_boxes", xy, raw)
     return xy.shape[0], b
 
 
@@ -1204,21 +1216,14 @@ def extract_scale_side(box, side, bg_radius=0):
 
 
 def _extract_scale_shapes(raw, mode, ny, nx, xy, box, side, m, bg_radius):
-    if mode not in MRC_ITEMSIZE:
-        raise _lib.SprkError("extract_scale: unsupported MRC mode %d" % mode)
+    _mode_check("extract_scale", mode)
     extract_scale_side(box, side, bg_radius)
     if ny < 1 or nx < 1 or ny * nx >= 1 << 31:
         raise _lib.SprkError("extract_scale: bad image size %dx%d" % (ny, nx))
-    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
-        raise _lib.SprkError("extract_scale: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
-                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
-    if xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or xy.device != raw.device:
-        raise _lib.SprkError("extract_scale: xy must be an int32 tensor [P, 2] on %s, got %s %s on %s"
-                             % (raw.device, xy.dtype, tuple(xy.shape), xy.device))
-    rows, cols = -(-side // 16) * 16, -(-box // 4) * 4
-    if m.dtype != torch.float32 or tuple(m.shape) != (rows, cols) or m.device != raw.device:
-        raise _lib.SprkError("extract_scale: m must be the float32 matrix of extract.crop_matrix(%d, %d), [%d, %d] on %s, "
-                             "got %s %s on %s" % (box, side, rows, cols, raw.device, m.dtype, tuple(m.shape), m.device))
+    _raw_check("extract_scale", raw, mode, ny, nx)
+    _xy_check("extract_scale", xy, raw)
+    _matrix_check("extract_scale", "m", m, crop_matrix_shape(box, side), raw,
+                  "matrix of extract.crop_matrix(%d, %d)" % (box, side))
     return xy.shape[0]
 
 
@@ -1262,31 +1267,22 @@ def extract_filter_side(box, side, bg_radius=0):
 def extract_filter_shapes(box, side):
     """-> the shapes of the operands w1, w2, w3, w4 and phi: the columns of the matrices rounded up to a multiple of 4"""
     hs, ku = side // 2 + 1, side + 1
-    up4 = lambda n: -(-n // 4) * 4
-    return (2 * hs, up4(box)), (2 * ku, 2 * box), (2 * side, up4(2 * ku)), (side, up4(2 * hs)), (ku, hs)
+    return (2 * hs, _up4(box)), (2 * ku, 2 * box), (2 * side, _up4(2 * ku)), (side, _up4(2 * hs)), (ku, hs)
 
 
 def _extract_filter_shapes(raw, mode, ny, nx, xy, box, side, w1, w2, w3, w4, phi, bg_radius, max_batch):
-    if mode not in MRC_ITEMSIZE:
-        raise _lib.SprkError("extract_filter: unsupported MRC mode %d" % mode)
+    _mode_check("extract_filter", mode)
     extract_filter_side(box, side, bg_radius)
     if max_batch < 0:
         raise _lib.SprkError("extract_filter: max_batch %d (0 = the library's choice, or a positive number of particles)"
                              % max_batch)
     if ny < 1 or nx < 1 or ny * nx >= 1 << 31:
         raise _lib.SprkError("extract_filter: bad image size %dx%d" % (ny, nx))
-    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
-        raise _lib.SprkError("extract_filter: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
-                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
-    if xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or xy.device != raw.device:
-        raise _lib.SprkError("extract_filter: xy must be an int32 tensor [P, 2] on %s, got %s %s on %s"
-                             % (raw.device, xy.dtype, tuple(xy.shape), xy.device))
+    _raw_check("extract_filter", raw, mode, ny, nx)
+    _xy_check("extract_filter", xy, raw)
     for name, m, shape in zip(("w1", "w2", "w3", "w4", "phi"), (w1, w2, w3, w4, phi), extract_filter_shapes(box, side)):
-        if m.dtype != torch.float32 or tuple(m.shape) != shape or m.device != raw.device:
-            raise _lib.SprkError("extract_filter: %s must be the float32 %s, [%d, %d] on %s, got %s %s on %s"
-                                 % (name, "filter of ctf.correction_filter" if name == "phi" else
-                                    "matrix of extract.filter_matrices(%d, %d)" % (box, side), *shape, raw.device, m.dtype,
-                                    tuple(m.shape), m.device))
+        _matrix_check("extract_filter", name, m, shape, raw, "filter of ctf.correction_filter" if name == "phi" else
+                      "matrix of extract.filter_matrices(%d, %d)" % (box, side))
     return xy.shape[0]
 
 
@@ -1330,25 +1326,20 @@ def psd_tile(T):
 
 def psd_matrix_shapes(T):
     """-> the shapes of the operands w1 and w2: [roundup(2H, 16), T] and [2T, 2T]"""
-    return (-(-(T + 2) // 16) * 16, T), (2 * T, 2 * T)
+    return (_up16(T + 2), T), (2 * T, 2 * T)
 
 
 def _psd_check(raw, mode, ny, nx, T, w1, w2, max_batch):
-    if mode not in MRC_ITEMSIZE:
-        raise _lib.SprkError("psd_tiles: unsupported MRC mode %d" % mode)
+    _mode_check("psd_tiles", mode)
     psd_tile(T)
     if not (T <= ny <= INGEST_MAX_SIDE and T <= nx <= INGEST_MAX_SIDE):
         raise _lib.SprkError("psd_tiles: a %dx%d image with tiles of %d (tile <= ny <= %d and tile <= nx <= %d)"
                              % (ny, nx, T, INGEST_MAX_SIDE, INGEST_MAX_SIDE))
     if max_batch < 0:
         raise _lib.SprkError("psd_tiles: max_batch %d (0 = the library's choice, or a positive number of tiles)" % max_batch)
-    if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < ny * nx * MRC_ITEMSIZE[mode]:
-        raise _lib.SprkError("psd_tiles: raw must be a flat uint8 tensor of at least ny*nx samples (%d bytes), got %s %s"
-                             % (ny * nx * MRC_ITEMSIZE[mode], raw.dtype, tuple(raw.shape)))
+    _raw_check("psd_tiles", raw, mode, ny, nx)
     for name, m, shape in zip(("w1", "w2"), (w1, w2), psd_matrix_shapes(T)):
-        if m.dtype != torch.float32 or tuple(m.shape) != shape or m.device != raw.device:
-            raise _lib.SprkError("psd_tiles: %s must be the float32 matrix of ctf.dft_matrices(%d), [%d, %d] on %s, got %s %s "
-                                 "on %s" % (name, T, *shape, raw.device, m.dtype, tuple(m.shape), m.device))
+        _matrix_check("psd_tiles", name, m, shape, raw, "matrix of ctf.dft_matrices(%d)" % T)
 
 
 def _psd_tiles(raw, mode, ny, nx, T, w1, w2, max_batch):
