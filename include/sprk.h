@@ -819,6 +819,57 @@ int sprk_class_score(const float *Q, int ldq, int N, const float *B, int ldb, in
 int sprk_class_average(const float *src, int n_src, int S, const int *ang, const int *shift, const float *cs, int A_n,
                        const int *members, int N, const int *offsets, int K, float *out, void *stream);
 
+/* ---- Wiener-weighted class averages (`joint class2d --ctf_weight`) -----------------------------------
+ * Per class A = IDFT2(sum_i wn_i . DFT2(y_i) / (sum_i wd_i + tau)) in three calls, over the half plane sprk_extract_filter
+ * keeps.  side = S even, 16..128; h = S/2, Hs = h + 1, Ku = S + 1, ldv = roundup4(Hs), ldz = roundup4(2Hs).  A spectrum is
+ * fp32 [2Ku, ldv]: row kk = k + h holds Re at the row frequency k = -h .. h, row Ku + kk holds Im, column v = 0 .. h the
+ * column frequency; columns Hs .. ldv-1 are written by nobody and read by nobody.  w1 [2Hs, roundup4(S)], w2 [2Ku, 2S],
+ * w3 [2S, roundup4(2Ku)], w4 [S, ldz] are the four matrices of sprk_extract_filter for box = side = S
+ * (spr_pick_amd.extract.filter_matrices(S, S); the weights of the rows +-h, of the columns and 1/S^2 sit inside w3 and w4).
+ * Every chain below is an fmaf chain on v_mfma_f32_16x16x4_f32 over its K ascending from 0.0f, one accumulator per element,
+ * K never split; data are taken to be finite.
+ *
+ * sprk_class_spectrum: spec[p] of img[p] for p < n, img fp32 [n, S, S] (stages 1 and 2 of sprk_extract_filter with the image
+ * as D, no anchor, no filter):
+ *   U[r, q]   = chain over c = 0 .. S-1 of img[r, c] * w1[q, c],  q < 2Hs;     V = [U[:, :Hs] ; U[:, Hs:]]   [2S, Hs]
+ *   Re[kk, v] = chain over t = 0 .. 2S-1 of w2[kk, t] * V[t, v];  Im[kk, v] the same with row Ku + kk of w2.
+ * Images run in batches of max_batch (0: the library's choice) that share the workspace (V of one batch,
+ * sprk_class_spectrum_ws_bytes(n, side, max_batch)); an image's bits depend on nothing but the image.  Two launches per
+ * batch.  n == 0 is SPRK_OK with nothing done.
+ *
+ * sprk_class_wiener: the class sums.  spec [n, 2Ku, ldv]; wn, wd fp32 [G, Ku, ldv] (spr_pick_amd.ctf.weight_tables); group
+ * int32 [n]: the table of each IMAGE; members int32 [N]: image indices grouped by class; offsets int32 [K + 1]: class k's
+ * members are members[offsets[k] .. offsets[k+1] - 1].  Per class k with offsets[k+1] > offsets[k] and per bin (kk, v < Hs):
+ *   nr = ni = d = 0.0f;   over the members m in list order, with g = group[m]:
+ *     nr = fmaf(wn[g, kk, v], spec[m, kk, v], nr);   ni = fmaf(wn[g, kk, v], spec[m, Ku + kk, v], ni);
+ *     d  = d + wd[g, kk, v]                                       (one fp32 add);
+ *   den = d + tau (one fp32 add);   out[k, kk, v] = nr / den,   out[k, Ku + kk, v] = ni / den   (correctly rounded quotients).
+ * A member listed twice counts twice.  An empty class leaves out[k] untouched.  Every index read from device memory is
+ * clamped into its array (a member to 0 .. n-1, a group to 0 .. G-1, an offset to 0 .. N): no content of these arrays makes
+ * the kernel read or write out of bounds.  out fp32 [K, 2Ku, ldv], not spec; 1 <= K <= 65535, G >= 1, tau finite and > 0
+ * (1 / SNR per image and bin).  n == 0 or N == 0 is SPRK_OK with nothing done.  One launch, one workgroup per class and 256
+ * bins, no workspace.
+ *
+ * sprk_class_synthesize: out[k] fp32 [S, S] of the spectrum f[k] for k < K, f [K, 2Ku, ldv] (stages 3 and 4 of
+ * sprk_extract_filter; no anchor, no normalisation):
+ *   Zr[i, v] = chain over t = 0 .. 2Ku-1 of w3[i, t] * f[t, v];  Zi the same with row S + i of w3;   Z = [Zr, Zi]   [S, 2Hs]
+ *   out[i, j] = chain over t = 0 .. 2Hs-1 of Z[i, t] * w4[j, t].
+ * The workspace is Z of all K spectra (sprk_class_synthesize_ws_bytes(K, side)); 1 <= K <= 65535.  Two launches.
+ *
+ * All three: refused (SPRK_EINVAL, nothing launched): an odd side or one outside 16..128, negative counts, K < 1, G < 1, a
+ * tau that is not finite or not > 0, a negative max_batch, null pointers, fp32 arrays or a workspace that do not start
+ * 16-byte aligned (index arrays: 4-byte); SPRK_EWORKSPACE for a missing or short workspace (the message states the bytes
+ * needed: the _ws_bytes query of the same arguments returns them, 0 for arguments that would be refused).  On `stream`, no
+ * atomics, no host synchronisation. */
+size_t sprk_class_spectrum_ws_bytes(int n, int side, int max_batch);
+int sprk_class_spectrum(const float *img, int n, int side, const float *w1, const float *w2, int max_batch, float *spec,
+                        void *ws, size_t ws_bytes, void *stream);
+int sprk_class_wiener(const float *spec, int n, int side, const float *wn, const float *wd, int G, const int *group,
+                      const int *members, int N, const int *offsets, int K, float tau, float *out, void *stream);
+size_t sprk_class_synthesize_ws_bytes(int K, int side);
+int sprk_class_synthesize(const float *f, int K, int side, const float *w3, const float *w4, float *out, void *ws,
+                          size_t ws_bytes, void *stream);
+
 /* ---- tiled power spectra (`joint ctf`)-----------------------------------------------------
  * sprk_psd_tiles: the summed half-plane power spectrum of T x T tiles of ONE raw micrograph (raw as for sprk_ingest_bin:
  * [ny,nx] samples of mode 0 / 1 / 2 / 6, 16-byte aligned start; rows may be only itemsize-aligned).  T a multiple of 16 in

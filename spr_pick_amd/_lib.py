@@ -152,6 +152,11 @@ _SIGS = {
     "sprk_class_transform": (c_i, [c_f, c_i, c_i, c_vp, c_vp, c_vp, c_i, c_f, c_i, c_i, c_i, c_vp, c_i, c_i, c_f, c_vp]),
     "sprk_class_score": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_f, ctypes.c_long, c_f, c_vp, c_vp]),
     "sprk_class_average": (c_i, [c_f, c_i, c_i, c_vp, c_vp, c_f, c_i, c_vp, c_i, c_vp, c_i, c_f, c_vp]),
+    "sprk_class_spectrum_ws_bytes": (c_sz, [c_i, c_i, c_i]),
+    "sprk_class_spectrum": (c_i, [c_f, c_i, c_i, c_f, c_f, c_i, c_f, c_vp, c_sz, c_vp]),
+    "sprk_class_wiener": (c_i, [c_f, c_i, c_i, c_f, c_f, c_i, c_vp, c_vp, c_i, c_vp, c_i, ctypes.c_float, c_f, c_vp]),
+    "sprk_class_synthesize_ws_bytes": (c_sz, [c_i, c_i]),
+    "sprk_class_synthesize": (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, c_vp, c_sz, c_vp]),
     "sprk_psd_tiles_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "sprk_psd_tiles": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i, c_f, c_vp, c_sz, c_vp]),
     "sprk_ctf_score_ws_bytes": (c_sz, [c_i, c_i]),

@@ -21,8 +21,15 @@ the median of their members' scores (``split_classes``), both halves averaged fr
 iteration.  The level with K classes ends the run.  A class that loses all its members keeps its average and is reported as
 empty.
 
-Not covered: CTF weighting of the averages, soft (probabilistic) assignment, sub-pixel shifts, boxes that are not 64 or 128
-pixels."""
+With ``ctf`` (``joint class2d --ctf_weight``) step (e) and the start are Wiener sums instead of plain means, for
+stacks that went through ``joint extract --ctf STAR --ctf_correct``: per class IDFT2(sum wn_i DFT2(y_i) / (sum wd_i + tau)),
+y_i the particle turned back as in (e), wn and wd the tables ``ctf.weight_tables`` builds from the particle's CTF row
+(``torch.ops.sprk.class_transform`` into images, then ``class_spectrum``, ``class_wiener`` and ``class_synthesize``).
+Turning a particle back by the angle index a turns its CTF with it: a row with DefocusU != DefocusV gets a table per (row, a)
+that occurs, at DefocusAngle + 360 a / A_n.  Scoring, the shift search and the splitting are the same.
+
+Not covered: scoring against CTF-modulated references, stacks that were not CTF-corrected, per-particle defocus, soft
+(probabilistic) assignment, sub-pixel shifts, boxes that are not 64 or 128 pixels."""
 import logging
 import os
 
@@ -40,6 +47,9 @@ MAX_SHIFT = 31                                   # torch_ops.ALIGN_MAX_SHIFT
 SIDES = (64, 128)                                # align_corr needs Sx % 64 == 0, class_transform S <= 128
 CORR_CHUNK = 65535                               # particles per align_corr call at most
 STAR_COLUMNS = ("ClassNumber", "AnglePsi", "OriginX", "OriginY")
+DEFAULT_WIENER = 1.0                             # tau of the Wiener sums: 1 / SNR per particle and bin
+CTF_COLUMNS = ("DefocusU", "DefocusV", "DefocusAngle", "Voltage", "SphericalAberration", "AmplitudeContrast", "Magnification",
+               "DetectorPixelSize")              # what --ctf_weight reads from particles.star
 
 
 def angle_count(angle_step):
@@ -70,6 +80,61 @@ def check_class2d_args(classes, angle_step=DEFAULT_ANGLE_STEP, max_shift=DEFAULT
     if iters < 2:
         raise ValueError("--iters %d: a level runs at least 2 iterations (8 is the default)" % iters)
     return A_n
+
+
+def check_ctf_weight(mode, tau):
+    """``--ctf_weight`` and ``--wiener`` -> tau (the default where None), or ValueError"""
+    from .ctf import CORRECTION_MODES
+    if mode is None:
+        if tau is not None:
+            raise ValueError("--wiener %r belongs to the Wiener-weighted averages: give --ctf_weight flip (or multiply: what "
+                             "`joint extract --ctf_correct` was given) as well" % (tau,))
+        return None
+    if mode not in CORRECTION_MODES:
+        raise ValueError("--ctf_weight %r: one of %s, what `joint extract --ctf_correct` was given" % (mode, ", ".join(CORRECTION_MODES)))
+    tau = DEFAULT_WIENER if tau is None else float(tau)
+    if not (np.isfinite(tau) and tau > 0):
+        raise ValueError("--wiener %r: a finite number > 0, 1 / SNR per particle and frequency (1.0 is the default)" % (tau,))
+    return tau
+
+
+def ctf_rows(labels, rows, path="particles.star"):
+    """The CTF columns of a ``particles.star`` -> (index int64 [N]: each particle's row of ``table``, table float64 [M, 7]:
+    the distinct (DefocusU, DefocusV, DefocusAngle, kV, Cs, Q, apix of the stack) in order of appearance), apix =
+    DetectorPixelSize . 10^4 / Magnification.  ValueError when a column is missing."""
+    missing = [c for c in CTF_COLUMNS if c not in labels]
+    if missing:
+        raise ValueError("%s: --ctf_weight needs the column%s _rln%s; write the stacks with `joint extract --ctf STAR "
+                         "--ctf_correct flip`" % (path, "s" if len(missing) > 1 else "", ", _rln".join(missing)))
+    cols = [labels.index(c) for c in CTF_COLUMNS]
+    seen, index, table = {}, [], []
+    for row in rows:
+        fields = row.split()
+        key = tuple(fields[c] for c in cols)
+        if key not in seen:
+            u, v, angle, kv, cs, q, mag, dps = (float(x) for x in key)
+            if not (mag > 0 and dps > 0):
+                raise ValueError("%s: Magnification %r and DetectorPixelSize %r must be positive" % (path, key[6], key[7]))
+            seen[key] = len(table)
+            table.append((u, v, angle, kv, cs, q, dps * 1e4 / mag))
+        index.append(seen[key])
+    return np.array(index, dtype=np.int64), np.array(table, dtype=np.float64).reshape(-1, 7)
+
+
+def ctf_groups(index, table, inv, A_n):
+    """The weight tables an averaging step needs beyond one per row -> (group int64 [N], extra float64 [G - M, 7]): a particle
+    of a row with DefocusU == DefocusV uses table ``index`` (the row as it is); the distinct (row, a) pairs of the others, a
+    = ``inv`` the angle index the particle is turned back by, follow from M on, each the row at DefocusAngle + 360 a / A_n."""
+    index, inv = np.asarray(index, dtype=np.int64), np.asarray(inv, dtype=np.int64)
+    astig = (table[:, 0] != table[:, 1])[index]
+    group = index.copy()
+    if not astig.any():
+        return group, np.zeros((0, 7))
+    keys, where = np.unique(index[astig] * A_n + inv[astig], return_inverse=True)
+    extra = table[keys // A_n].copy()
+    extra[:, 2] += 360.0 * (keys % A_n) / A_n
+    group[astig] = len(table) + where
+    return group, extra
 
 
 def check_geometry(S, N, classes, max_shift, radius=None):
@@ -121,10 +186,13 @@ def split_classes(cls, scores, Kc, K):
     return cls, [int(k) for k in order]
 
 
-def classify(P, classes, angle_step=DEFAULT_ANGLE_STEP, max_shift=DEFAULT_MAX_SHIFT, radius=None, iters=DEFAULT_ITERS):
+def classify(P, classes, angle_step=DEFAULT_ANGLE_STEP, max_shift=DEFAULT_MAX_SHIFT, radius=None, iters=DEFAULT_ITERS,
+             ctf=None):
     """P: float32 CUDA tensor [N, S, S], all particles on the device -> dict: ``cls`` int [N], ``ang`` int [N] (angle index),
     ``shift`` int [N, 2] (dy, dx: the aligned particle is P[i + dy, j + dx]), ``scores`` float32 [N], ``averages`` float32
-    [K, S, S], ``levels`` [(classes, iterations used)], ``A_n`` and ``radius``; all NumPy."""
+    [K, S, S], ``levels`` [(classes, iterations used)], ``A_n`` and ``radius``; all NumPy.
+    ctf = (index int [N], table [M, 7], mode, tau): Wiener-weighted averages; each particle's row of ``table`` (``ctf_rows``),
+    the mode ``joint extract --ctf_correct`` was given and tau of ``check_ctf_weight``."""
     import torch
     from . import torch_ops  # noqa: F401  (registers torch.ops.sprk)
     A_n = check_class2d_args(classes, angle_step, max_shift, radius, iters)
@@ -158,13 +226,37 @@ def classify(P, classes, angle_step=DEFAULT_ANGLE_STEP, max_shift=DEFAULT_MAX_SH
     ang = torch.zeros(N, dtype=torch.int32, device=dev)
     shift = torch.zeros((N, 2), dtype=torch.int32, device=dev)
     n = 2 * R + 1
+    if ctf is not None:
+        from . import ctf as ctf_mod, extract
+        ctf_index, ctf_table, ctf_mode, tau = ctf
+        ctf_index, ctf_table = np.asarray(ctf_index, dtype=np.int64), np.asarray(ctf_table, dtype=np.float64).reshape(-1, 7)
+        tau = check_ctf_weight(ctf_mode, tau)
+        if ctf_index.shape != (N,) or not len(ctf_table) or ctf_index.min() < 0 or ctf_index.max() >= len(ctf_table):
+            raise ValueError("classify: ctf needs one row index per particle into a table [M, 7]")
+        w1, w2, w3, w4 = extract.filter_matrices(S, S, dev)
+        base_wn, base_wd = ctf_mod.weight_tables(S, ctf_table, ctf_mode, dev)            # (row, 0): once per run
+        aligned = torch.empty((N, S, S), dtype=torch.float32, device=dev)
+        spec = torch.empty((N,) + torch_ops.class_spectrum_shapes(S)[4], dtype=torch.float32, device=dev)
+        fsum = torch.zeros((K,) + tuple(spec.shape[1:]), dtype=torch.float32, device=dev)   # an empty class keeps its spectrum
 
     def average(Kc):
         """avgs[:Kc] from the state: members grouped by class, ascending within a class"""
         members = torch.argsort(cls, stable=True).to(torch.int32)
         offsets = torch.zeros(Kc + 1, dtype=torch.int32, device=dev)
         offsets[1:] = torch.cumsum(torch.bincount(cls, minlength=Kc), 0).to(torch.int32)
-        ops.class_average(P, ((A_n - ang) % A_n).to(torch.int32), shift, cs, members, offsets, avgs[:Kc])
+        inv = ((A_n - ang) % A_n).to(torch.int32)
+        if ctf is None:
+            ops.class_average(P, inv, shift, cs, members, offsets, avgs[:Kc])
+            return
+        ops.class_transform(P, everyone, inv, shift, cs, 0, 0, None, aligned)
+        ops.class_spectrum(aligned, w1, w2, 0, spec)
+        group, extra = ctf_groups(ctf_index, ctf_table, inv.cpu().numpy(), A_n)
+        wn, wd = base_wn, base_wd
+        if len(extra):
+            more = ctf_mod.weight_tables(S, extra, ctf_mode, dev)
+            wn, wd = torch.cat([wn, more[0]]), torch.cat([wd, more[1]])
+        ops.class_wiener(spec, S, wn, wd, i32(group), members, offsets, tau, fsum[:Kc])
+        ops.class_synthesize(fsum[:Kc], S, w3, w4, avgs[:Kc])
 
     average(1)                                                   # the plain mean: angle 0, shift 0, one class
     Kc, levels = 1, []
@@ -200,6 +292,8 @@ def classify(P, classes, angle_step=DEFAULT_ANGLE_STEP, max_shift=DEFAULT_MAX_SH
         host_cls, parents = split_classes(cls.cpu().numpy(), best_score.cpu().numpy(), Kc, K)
         cls = torch.as_tensor(host_cls, device=dev)
         avgs[Kc:Kc + len(parents)] = avgs[torch.as_tensor(parents, device=dev)]   # an empty half starts as its parent
+        if ctf is not None:
+            fsum[Kc:Kc + len(parents)] = fsum[torch.as_tensor(parents, device=dev)]
         Kc += len(parents)
         average(Kc)
     return {"cls": cls.cpu().numpy(), "ang": ang.cpu().numpy().astype(np.int64), "shift": shift.cpu().numpy().astype(np.int64),
@@ -276,17 +370,25 @@ def write_averages(path, averages, header):
 
 
 def class2d_dataset(particles, out_dir, classes, angle_step=DEFAULT_ANGLE_STEP, max_shift=DEFAULT_MAX_SHIFT, radius=None,
-                    iters=DEFAULT_ITERS, device="cuda"):
+                    iters=DEFAULT_ITERS, device="cuda", ctf_weight=None, wiener=None):
     """``joint class2d``: the particles of ``particles`` (the STAR file of ``joint extract``) classified into ``classes``
     classes; writes ``classes.mrcs``, ``particles_class2d.star`` (the input rows and header verbatim plus _rlnClassNumber,
     1-based, _rlnAnglePsi in degrees: the in-plane rotation of the class average that fits the particle, and _rlnOriginX /
     _rlnOriginY in pixels of the stack: the displacement that aligns the particle) and ``class2d.txt`` into ``out_dir``.
+    ctf_weight = "flip" or "multiply", what ``joint extract --ctf_correct`` was given (the STAR file has no column for it):
+    the averages are Wiener sums with tau = ``wiener`` (default 1.0) over the CTF columns of ``particles``, which must be
+    there (refused before any stack is read); the STAR output is the same.
     -> {"particles", "classes": [{"members", "mean_score"}], "levels"}"""
     import torch
     A_n = check_class2d_args(classes, angle_step, max_shift, radius, iters)
+    tau = check_ctf_weight(ctf_weight, wiener)
+    ctf = None
+    if ctf_weight is not None:
+        _, labels, rows = read_particles_star(particles)
+        ctf = ctf_rows(labels, rows, particles) + (ctf_weight, tau)
     P, head, labels, rows, header = load_particles(particles)
     radius = check_geometry(P.shape[1], len(P), classes, max_shift, radius)
-    res = classify(torch.as_tensor(P, device=device), classes, angle_step, max_shift, radius, iters)
+    res = classify(torch.as_tensor(P, device=device), classes, angle_step, max_shift, radius, iters, ctf=ctf)
     os.makedirs(out_dir, exist_ok=True)
     write_averages(os.path.join(out_dir, "classes.mrcs"), res["averages"], header)
     step = 360.0 / A_n
@@ -300,8 +402,9 @@ def class2d_dataset(particles, out_dir, classes, angle_step=DEFAULT_ANGLE_STEP, 
         mem = res["cls"] == k
         summary.append({"members": int(mem.sum()), "mean_score": float(res["scores"][mem].mean()) if mem.any() else 0.0})
     with open(os.path.join(out_dir, "class2d.txt"), "w") as f:
-        f.write("# %d particles of %dx%d, %d classes, %d angles, max shift %d, mask radius %d\n"
-                % (len(P), P.shape[1], P.shape[2], classes, A_n, max_shift, radius))
+        f.write("# %d particles of %dx%d, %d classes, %d angles, max shift %d, mask radius %d%s\n"
+                % (len(P), P.shape[1], P.shape[2], classes, A_n, max_shift, radius,
+                   "" if ctf is None else ", ctf_weight %s, wiener %s" % (ctf_weight, repr(tau))))
         f.write("# class\tmembers\tmean_score\n")
         for k, s in enumerate(summary):
             f.write("%d\t%d\t%s\n" % (k + 1, s["members"], repr(s["mean_score"]) if s["members"] else "empty"))

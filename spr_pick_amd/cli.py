@@ -140,6 +140,8 @@ def _check_ctf(ns):
 def _check_class2d(ns):
     from .class2d import check_class2d_args
     check_class2d_args(ns.classes, ns.angle_step, ns.max_shift, ns.radius, ns.iters)
+    from .class2d import check_ctf_weight
+    check_ctf_weight(ns.ctf_weight, ns.wiener)
 
 
 def _check_align(ns):
@@ -367,9 +369,10 @@ def build_parser():
     c2_help = ("Reference-free 2-D class averages of extracted particles on the GPU: a multi-reference alignment over "
                "in-plane angles and integer shifts that starts from one class and splits the largest classes until there "
                "are K (replaces a first relion_refine / EMAN2 2-D classification run when the aim is to judge the picks).  "
-               "Reads the particles.star and the float32 stacks of `joint extract --scale 64` (or 128).  Not covered: CTF "
-               "weighting of the averages, soft (probabilistic) assignment, sub-pixel shifts, boxes that are not 64 or 128 "
-               "pixels.")
+               "Reads the particles.star and the float32 stacks of `joint extract --scale 64` (or 128).  With --ctf_weight "
+               "the averages are Wiener sums over the particles' CTFs.  Not covered: CTF weighting of the scores (the "
+               "references are not CTF-modulated), per-particle defocus, soft (probabilistic) assignment, sub-pixel shifts, "
+               "boxes that are not 64 or 128 pixels.")
     c2 = cmds.add_parser("class2d", help=c2_help, description=c2_help)
     c2.add_argument("--particles", "-p", required=True, metavar="STAR",
                     help="particles.star of `joint extract`; the {name}.mrcs stacks of _rlnImageName lie beside it")
@@ -384,6 +387,12 @@ def build_parser():
                     help="mask radius in pixels (default and at most S/2 - R - 2 for a box of S pixels)")
     c2.add_argument("--iters", type=int, default=8, metavar="I",
                     help="iterations per level at most (default 8, at least 2; a level stops when no assignment changes)")
+    c2.add_argument("--ctf_weight", choices=("flip", "multiply"), metavar="MODE",
+                    help="Wiener-weighted class averages for stacks of `joint extract --ctf STAR --ctf_correct MODE` (flip or "
+                         "multiply: say which, the STAR file has no column for it); needs the CTF columns in particles.star")
+    c2.add_argument("--wiener", type=float, metavar="T",
+                    help="tau of the Wiener sums, 1 / SNR per particle and frequency: finite and > 0 (default 1.0; needs "
+                         "--ctf_weight)")
     c2.check = _check_class2d
     return parser
 
@@ -503,7 +512,8 @@ def run_class2d(args, parser):
     from . import class2d
     try:
         res = class2d.class2d_dataset(args["particles"], args["out"], args["classes"], angle_step=args["angle_step"],
-                                      max_shift=args["max_shift"], radius=args.get("radius"), iters=args["iters"])
+                                      max_shift=args["max_shift"], radius=args.get("radius"), iters=args["iters"],
+                                      ctf_weight=args.get("ctf_weight"), wiener=args.get("wiener"))
     except ValueError as e:                      # what only the stacks can tell: their side, their number
         parser.error(str(e))
     print(json.dumps(res))

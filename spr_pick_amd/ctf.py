@@ -157,16 +157,67 @@ def correction_filter(B, S, apix, defocus_u, defocus_v, angle, kv, cs, ac, mode)
         raise ValueError("ctf correction needs an even box and an even output side, 2 <= S <= B; got B = %d, S = %d" % (B, S))
     if not (apix > 0 and np.isfinite(apix)):
         raise ValueError("apix must be positive, got %r" % (apix,))
-    h = S // 2
-    k = np.arange(-h, h + 1, dtype=np.float64)[:, None]
-    v = np.arange(h + 1, dtype=np.float64)[None, :]
-    s = np.sqrt(k * k + v * v) / (B * float(apix))
-    d0, d1 = 0.5 * (float(defocus_u) + float(defocus_v)), 0.5 * (float(defocus_u) - float(defocus_v))
-    dz = d0 + d1 * np.cos(2.0 * (np.arctan2(k, v) - math.radians(float(angle))))
+    s, dz = filter_grid(np, B, S, float(apix), float(defocus_u), float(defocus_v), math.radians(float(angle)))
     c = ctf(s, dz, kv, cs, ac)
     if mode == "flip":
         return np.where(c <= 0, 1.0, -1.0).astype(np.float32)
     return (-c).astype(np.float32)
+
+
+def filter_grid(xp, B, S, apix, defocus_u, defocus_v, angle_rad, **where):
+    """The grid and the dz(phi) rule of ``correction_filter``, for NumPy or torch (``xp``; torch with ``device=``): ->
+    (s, dz) float64 over rows k = -S/2 .. S/2 and columns v = 0 .. S/2.  The four parameters are floats, or arrays [G, 1, 1]
+    for G filters at once (``angle_rad`` in radians)."""
+    h = S // 2
+    k = xp.arange(-h, h + 1, dtype=xp.float64, **where)[:, None]
+    v = xp.arange(h + 1, dtype=xp.float64, **where)[None, :]
+    s = xp.sqrt(k * k + v * v) / (B * apix)
+    d0, d1 = 0.5 * (defocus_u + defocus_v), 0.5 * (defocus_u - defocus_v)
+    dz = d0 + d1 * xp.cos(2.0 * (xp.arctan2(k, v) - angle_rad))
+    return s, dz
+
+
+def weight_tables(S, rows, mode, device=None):
+    """The weights of the Wiener class sums (``torch.ops.sprk.class_wiener``) for a stack of side S whose
+    particles went through ``correction_filter(.., mode)``: -> (wn, wd) float32 [G, S + 1, roundup(S/2 + 1, 4)], one table per
+    row of ``rows`` = (DefocusU, DefocusV, DefocusAngle in degrees, kV, Cs, Q, apix of the STACK), formed in float64 and
+    rounded once, the padded columns exact zeros.  c is ``ctf`` on the grid of ``correction_filter(S, S, apix, ..)``.
+    "flip" (data -|c| S + n): wn = |c|, wd = c^2; "multiply" (data -c^2 S - c n): wn = 1, wd = c^2.  Without a device: NumPy
+    arrays.  With one: tensors there, built there in one batch (what torch's sine differs from NumPy's is what they differ
+    by)."""
+    if mode not in CORRECTION_MODES:
+        raise ValueError("ctf weighting mode %r (one of %s: what `joint extract --ctf_correct` was given)"
+                         % (mode, ", ".join(CORRECTION_MODES)))
+    try:
+        S = torch_ops.class_ctf_side("weight_tables", int(S))
+    except _lib.SprkError as e:
+        raise ValueError(str(e)) from None
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 7)
+    if not len(rows) or not np.isfinite(rows).all() or not (rows[:, 6] > 0).all() or not (rows[:, 3] > 0).all():
+        raise ValueError("weight_tables: at least one row of seven finite numbers with kV > 0 and apix > 0")
+    # per row, in the operations of ``ctf``: the phase is a dz s^2 - b s^4 + shift
+    lam = np.array([wavelength(kv) for kv in rows[:, 3]])
+    a = np.array([np.pi * l for l in lam])
+    b = np.array([0.5 * np.pi * (cs * 1e7) * l ** 3 for cs, l in zip(rows[:, 4], lam)])
+    shift = np.array([math.atan2(q, math.sqrt(1 - q * q)) for q in rows[:, 5]])
+    if device is None:
+        xp, where, col = np, {}, lambda x: x[:, None, None]
+    else:
+        xp, where = torch, {"device": device}
+        col = lambda x: torch.as_tensor(x, dtype=torch.float64, device=device)[:, None, None]   # noqa: E731
+    s, dz = filter_grid(xp, S, S, col(rows[:, 6]), col(rows[:, 0]), col(rows[:, 1]), col(np.radians(rows[:, 2])), **where)
+    s2 = s * s
+    c = -xp.sin(col(a) * dz * s2 - col(b) * s2 * s2 + col(shift))
+    wd = c * c
+    wn = xp.abs(c) if mode == "flip" else xp.ones_like(c)
+    Hs, ldv = S // 2 + 1, torch_ops.class_spectrum_shapes(S)[5][1]
+    if device is None:
+        out = np.zeros((2, len(rows), S + 1, ldv), dtype=np.float32)
+        out[0, :, :, :Hs], out[1, :, :, :Hs] = wn, wd
+    else:
+        out = torch.zeros((2, len(rows), S + 1, ldv), dtype=torch.float32, device=device)
+        out[0, :, :, :Hs], out[1, :, :, :Hs] = wn.float(), wd.float()
+    return out[0], out[1]
 
 
 def check_fit_args(apix, kv, cs, ac, min_res, max_res, min_defocus, max_defocus):

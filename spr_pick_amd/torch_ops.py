@@ -1155,6 +1155,148 @@ _register("class_average", "(Tensor src, Tensor ang, Tensor shift, Tensor cs, Te
           "-> ()", _class_average, _class_average_fake)
 
 
+# Wiener-weighted class averages (class2d.py with ctf=: csrc/classctf.hip)
+CLASS_CTF_MIN_SIDE = 16                          # sprk_class_spectrum / _wiener / _synthesize: side even, 16..CLASS_MAX_SIDE
+
+
+def class_ctf_side(who, side):
+    """Argument check shared by the three operators and ctf.weight_tables -> side."""
+    if not (CLASS_CTF_MIN_SIDE <= side <= CLASS_MAX_SIDE) or side % 2:
+        raise _lib.SprkError("%s: a side of %d (even, %d..%d; `joint extract --scale 64` writes such stacks)"
+                             % (who, side, CLASS_CTF_MIN_SIDE, CLASS_MAX_SIDE))
+    return int(side)
+
+
+def class_spectrum_shapes(side):
+    """-> the shapes of w1, w2, w3, w4 (``extract_filter_shapes(side, side)``), of one spectrum [2Ku, roundup(Hs, 4)] and
+    of one weight table [Ku, roundup(Hs, 4)]"""
+    hs, ku = side // 2 + 1, side + 1
+    return extract_filter_shapes(side, side)[:4] + ((2 * ku, _up4(hs)), (ku, _up4(hs)))
+
+
+def _class_spectra_check(who, name, t, side, like):
+    """t: float32 [n, 2Ku, ldv] on the device of ``like`` -> n"""
+    shape = class_spectrum_shapes(side)[4]
+    if t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape[1:]) != shape or t.device != like.device:
+        raise _lib.SprkError("%s: %s must be float32 [n, %d, %d] on %s, got %s %s on %s"
+                             % (who, name, *shape, like.device, t.dtype, tuple(t.shape), t.device))
+    return int(t.shape[0])
+
+
+def _class_spectrum_check(img, w1, w2, max_batch, spec):
+    if img.dtype != torch.float32 or img.dim() != 3 or img.shape[1] != img.shape[2]:
+        raise _lib.SprkError("class_spectrum: img must be float32 [n, S, S], got %s %s" % (img.dtype, tuple(img.shape)))
+    n, S = int(img.shape[0]), class_ctf_side("class_spectrum", int(img.shape[1]))
+    if max_batch < 0:
+        raise _lib.SprkError("class_spectrum: max_batch %d (0 = the library's choice, or a positive number of images)" % max_batch)
+    shapes = class_spectrum_shapes(S)
+    for name, m, shape in (("w1", w1, shapes[0]), ("w2", w2, shapes[1])):
+        _matrix_check("class_spectrum", name, m, shape, img, "matrix of extract.filter_matrices(%d, %d)" % (S, S))
+    if _class_spectra_check("class_spectrum", "spec", spec, S, img) != n:
+        raise _lib.SprkError("class_spectrum: %d images but room for %d spectra" % (n, spec.shape[0]))
+    return n, S
+
+
+def _class_spectrum(img, w1, w2, max_batch, spec):
+    """img float32 [n, S, S]; w1, w2 of ``extract.filter_matrices(S, S)``; spec float32 [n, 2Ku, roundup(Hs, 4)] receives the
+    half-plane spectrum of every image, Re rows over Im rows (sprk_class_spectrum)."""
+    n, S = _class_spectrum_check(img, w1, w2, max_batch, spec)
+    if not all(t.is_contiguous() for t in (img, w1, w2, spec)):
+        raise _lib.SprkError("class_spectrum: img, w1, w2 and spec must be contiguous")
+    if n == 0:
+        return
+    L = _lib.lib()
+    ws = _ws(L.sprk_class_spectrum_ws_bytes(n, S, int(max_batch)), img)
+    check(L.sprk_class_spectrum(_p(img), n, S, _p(w1), _p(w2), int(max_batch), _p(spec), _p(ws), ws.numel(), _stream(img)),
+          "sprk_class_spectrum")
+
+
+def _class_spectrum_fake(img, w1, w2, max_batch, spec):
+    _class_spectrum_check(img, w1, w2, max_batch, spec)
+
+
+_register("class_spectrum", "(Tensor img, Tensor w1, Tensor w2, int max_batch, Tensor(a!) spec) -> ()", _class_spectrum,
+          _class_spectrum_fake)
+
+
+def _class_wiener_check(spec, side, wn, wd, group, members, offsets, tau, out):
+    S = class_ctf_side("class_wiener", side)
+    n = _class_spectra_check("class_wiener", "spec", spec, S, spec)
+    table = class_spectrum_shapes(S)[5]
+    G = int(wn.shape[0]) if wn.dim() == 3 else 0
+    for name, t in (("wn", wn), ("wd", wd)):
+        if t.dtype != torch.float32 or G < 1 or tuple(t.shape) != (G,) + table or t.device != spec.device:
+            raise _lib.SprkError("class_wiener: %s must be the float32 [G >= 1, %d, %d] of ctf.weight_tables on %s, got %s %s "
+                                 "on %s" % (name, *table, spec.device, t.dtype, tuple(t.shape), t.device))
+    N = members.shape[0] if members.dim() == 1 else -1
+    K = offsets.shape[0] - 1 if offsets.dim() == 1 else 0
+    if not (_is_i32(group, (n,), spec.device) and N >= 0 and 1 <= K <= 65535 and _is_i32(members, (N,), spec.device)
+            and _is_i32(offsets, (K + 1,), spec.device)):
+        raise _lib.SprkError("class_wiener: group must be int32 [%d] (one table per image), members int32 [N] and offsets "
+                             "int32 [K + 1] (1 <= K <= 65535) on %s, got %s, %s and %s"
+                             % (n, spec.device, tuple(group.shape), tuple(members.shape), tuple(offsets.shape)))
+    if not (tau > 0 and tau != float("inf")):
+        raise _lib.SprkError("class_wiener: tau %r (finite and > 0; 1.0 is the default of --wiener)" % (tau,))
+    if _class_spectra_check("class_wiener", "out", out, S, spec) != K:
+        raise _lib.SprkError("class_wiener: %d classes but room for %d spectra" % (K, out.shape[0]))
+    return n, S, G, int(N), int(K)
+
+
+def _class_wiener(spec, side, wn, wd, group, members, offsets, tau, out):
+    """spec float32 [n, 2Ku, ldv]; wn, wd float32 [G, Ku, ldv]; group int32 [n]: each image's table; members int32 [N] grouped
+    by class, offsets int32 [K + 1]: out[k] = sum of wn . spec over the class's members in list order over (sum of wd + tau);
+    an empty class keeps what out[k] holds (sprk_class_wiener)."""
+    n, S, G, N, K = _class_wiener_check(spec, side, wn, wd, group, members, offsets, tau, out)
+    for t in (spec, wn, wd, group, members, offsets, out):
+        if not t.is_contiguous():
+            raise _lib.SprkError("class_wiener: every tensor must be contiguous")
+    if spec.data_ptr() == out.data_ptr():
+        raise _lib.SprkError("class_wiener: out must not be spec")
+    check(_lib.lib().sprk_class_wiener(_p(spec), n, S, _p(wn), _p(wd), G, _p(group), _p(members), N, _p(offsets), K, float(tau),
+                                       _p(out), _stream(spec)), "sprk_class_wiener")
+
+
+def _class_wiener_fake(spec, side, wn, wd, group, members, offsets, tau, out):
+    _class_wiener_check(spec, side, wn, wd, group, members, offsets, tau, out)
+
+
+_register("class_wiener", "(Tensor spec, int side, Tensor wn, Tensor wd, Tensor group, Tensor members, Tensor offsets, float tau, "
+          "Tensor(a!) out) -> ()", _class_wiener, _class_wiener_fake)
+
+
+def _class_synthesize_check(f, side, w3, w4, out):
+    S = class_ctf_side("class_synthesize", side)
+    K = _class_spectra_check("class_synthesize", "f", f, S, f)
+    if not 1 <= K <= 65535:
+        raise _lib.SprkError("class_synthesize: %d spectra (1..65535; split a larger stack into several calls)" % K)
+    shapes = class_spectrum_shapes(S)
+    for name, m, shape in (("w3", w3, shapes[2]), ("w4", w4, shapes[3])):
+        _matrix_check("class_synthesize", name, m, shape, f, "matrix of extract.filter_matrices(%d, %d)" % (S, S))
+    if out.dtype != torch.float32 or tuple(out.shape) != (K, S, S) or out.device != f.device:
+        raise _lib.SprkError("class_synthesize: out must be float32 [%d, %d, %d] on %s, got %s %s"
+                             % (K, S, S, f.device, out.dtype, tuple(out.shape)))
+    return K, S
+
+
+def _class_synthesize(f, side, w3, w4, out):
+    """f float32 [K, 2Ku, ldv]; w3, w4 of ``extract.filter_matrices(S, S)``; out float32 [K, S, S] receives the image of
+    every spectrum (sprk_class_synthesize)."""
+    K, S = _class_synthesize_check(f, side, w3, w4, out)
+    if not all(t.is_contiguous() for t in (f, w3, w4, out)):
+        raise _lib.SprkError("class_synthesize: f, w3, w4 and out must be contiguous")
+    L = _lib.lib()
+    ws = _ws(L.sprk_class_synthesize_ws_bytes(K, S), f)
+    check(L.sprk_class_synthesize(_p(f), K, S, _p(w3), _p(w4), _p(out), _p(ws), ws.numel(), _stream(f)), "sprk_class_synthesize")
+
+
+def _class_synthesize_fake(f, side, w3, w4, out):
+    _class_synthesize_check(f, side, w3, w4, out)
+
+
+_register("class_synthesize", "(Tensor f, int side, Tensor w3, Tensor w4, Tensor(a!) out) -> ()", _class_synthesize,
+          _class_synthesize_fake)
+
+
 # ---- particle extraction (extract.py: raw MRC samples + pick coordinates -> normalised particle stack) ------------------------
 EXTRACT_MAX_BOX = 1024                           # sprk_extract_boxes: the int64 sum of squares stays below 2^63 up to here
 EXTRACT_NORMALIZE, EXTRACT_INVERT = 1, 2         # SPRK_EXTRACT_*
