@@ -737,6 +737,41 @@ int sprk_align_synthesize(const float *F, int Ku, int Hs, int by, int bx, const 
 int sprk_movie_correct(const void *raw, int mode, int ny, int nx, const float *gain, const float *dark,
                        const uint8_t *fix, float *out, float *sum, int first, void *stream);
 
+/* ---- TIFF movies in (`joint align` on .tif / .tiff) ----------------------------------------------
+ * sprk_tiff_decode: the strips of one frame, as they lie in the file, decoded into the frame's sample block.
+ * src: `nbytes` bytes on the device.  strip_off, strip_len, strip_out: int64 [n_strips] on the device.  Strip s reads the
+ * bytes [lo, hi) of src: [strip_off[s], strip_off[s] + strip_len[s]) clamped into [0, nbytes) (empty for a length <= 0).
+ * It must yield so = strip_out[s] decoded bytes, and writes them at the decoded position base(s) = the sum of strip_out[t]
+ * over t < s; every strip_out value is clamped into [0, out_elems], base(s) to out_elems and so to out_elems - base(s) and to
+ * 2^31 - 1.  `out` holds out_elems decoded bytes: one byte each, or (widen = 1) one little-endian uint16 each with the byte
+ * in its low half.  Decoded positions at or past the sum of all strip_out are not written.  status: int32 [n_strips].
+ *
+ * Each strip is decoded on its own; its output and status depend on nothing but its own bytes and so.
+ * compression 1 (stored): the first min(hi - lo, so) bytes are copied; fewer than so: status 2.
+ * compression 5 (LZW, TIFF 6.0): codes of 9..12 bits, the first bit of a code in the most significant free bit of the byte
+ * (MSB first).  State: width = 9, next = 258 (the next free code), no previous string; this is also the state a strip
+ * starts in, so a strip that does not begin with a Clear is decoded as if it did.  Until so bytes are out:
+ *   fewer than `width` bits left in [lo, hi): status 2, stop;   code = the next `width` bits;
+ *   code 256 (Clear): back to the starting state;   code 257 (EOI): status 2, stop (so bytes are not out yet);
+ *   no previous string: a code above 255: status 1, stop; else the string is the byte `code`;
+ *   else code < 256: that byte;  258 <= code < next: the string of that table entry;  code == next: the previous string
+ *     plus its own first byte;  code > next: status 1, stop;
+ *   a string longer than the so - n bytes still missing: its first so - n bytes are written, status 3, stop;
+ *   the string is written;  with a previous string and next < 4096: entry `next` = the previous string plus the first byte
+ *     of this one, next = next + 1, and when next is now 511, 1023 or 2047, width = width + 1 (the early change);
+ *   the string becomes the previous string.
+ * Decoding ends when so bytes are out: an EOI is not asked for, and what follows it is not read.  The first error of a
+ * strip is its status (0: none); the bytes before it stay, and the rest of the strip's so bytes are zeros, so the output is
+ * a function of the input alone.
+ * Bounds: no byte outside [0, nbytes) of src is read and no bit outside [lo, hi) reaches the output; every write lies in
+ * the strip's own [base(s), base(s) + so) within out_elems; every table index comes from a code below `next` <= 4096.  No
+ * content of src, strip_off, strip_len or strip_out makes the kernel read or write out of bounds.
+ * Refused (SPRK_EINVAL, nothing launched): a null pointer, nbytes < 1, n_strips outside 1 .. 2^20, another compression or
+ * widen, out_elems < 1, src or out not 16-byte aligned, a table not 8-byte or status not 4-byte aligned, out == src.  One
+ * launch on `stream` (one wave per strip), no workspace, no atomics, no host synchronisation. */
+int sprk_tiff_decode(const uint8_t *src, long nbytes, const long *strip_off, const long *strip_len, const long *strip_out,
+                     int n_strips, int compression, int widen, void *out, long out_elems, int *status, void *stream);
+
 /* ---- local motion correction (`joint align --patch`) ---------------------------------------------
  * sprk_align_warp: one fp32 frame src [ny, nx] resampled through a smooth displacement field into a running sum y [ny, nx]:
  *   out(i, j) = src(i + sy(i, j), j + sx(i, j)) with periodic edges;   y = out when `first` (y is then not read), else

@@ -149,6 +149,7 @@ _SIGS = {
     "sprk_align_synthesize": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_vp, c_sz, c_vp]),
     "sprk_movie_correct": (c_i, [c_vp, c_i, c_i, c_i, c_f, c_f, c_vp, c_f, c_f, c_i, c_vp]),
     "sprk_align_warp": (c_i, [c_f, c_i, c_i, c_vp, c_vp, c_f, c_i, c_vp]),
+    "sprk_tiff_decode": (c_i, [c_vp, ctypes.c_long, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp, ctypes.c_long, c_vp, c_vp]),
     "sprk_class_transform": (c_i, [c_f, c_i, c_i, c_vp, c_vp, c_vp, c_i, c_f, c_i, c_i, c_i, c_vp, c_i, c_i, c_f, c_vp]),
     "sprk_class_score": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_f, ctypes.c_long, c_f, c_vp, c_vp]),
     "sprk_class_average": (c_i, [c_f, c_i, c_i, c_vp, c_vp, c_f, c_i, c_vp, c_i, c_vp, c_i, c_f, c_vp]),

@@ -1,7 +1,7 @@
 """``joint align``: whole-frame motion correction of movies on the device — the step before ``joint bin`` /
 ``joint eval --bin`` / ``joint ctf`` / ``joint extract``, in place of a MotionCor2 or ``relion_motioncorr`` run.
 
-A movie is an MRC stack of Z >= 2 short-exposure frames (modes 0 / 1 / 2 / 6): gain-corrected, or as the detector wrote it
+A movie is an MRC stack (or a TIFF, below) of Z >= 2 short-exposure frames (modes 0 / 1 / 2 / 6): gain-corrected, or as the detector wrote it
 together with its references (``gain``, ``dark``, ``defects``, ``hot_sigma``; ``joint align --gain ...``): every frame then
 passes ``torch.ops.sprk.movie_correct`` first (``moviefix.CorrectedMovie``), and what follows sees float32
 frames whose fixed pattern is gone.  Per movie:
@@ -25,8 +25,12 @@ Fourier space (``dose.sum_frames_weighted``); the plain sum and t
 With ``patch`` (``joint align --patch PY,PX``) one smooth local field per movie is fitted after the whole-frame estimate and
 every frame is warped by it before it is summed (``localmotion``): ``torch.ops.sprk.align_warp``.
 
-Out of scope: local motion finer than that one smooth field (per-particle polishing), TIFF and EER input, and gain
-references meant to be divided by.
+A movie may also be a multi-page TIFF (``.tif`` / ``.tiff``: stored or LZW strips, as SerialEM and EPU write them; ``tiffio``,
+DESIGN §4.3o): its strips are uploaded as they lie in the file and decoded on the device (``torch.ops.sprk.tiff_decode``)
+into the sample block an MRC frame is, and everything after that is the same.
+
+Out of scope: local motion finer than that one smooth field (per-particle polishing), EER input, TIFF with another
+compression, a predictor or tiles, TIFF references, and gain references meant to be divided by.
 
 Coordinates and signs: x runs along nx (columns), y along ny (rows).  ``{name}_shifts.txt`` lists, per frame, the
 displacement (dx, dy) of the frame's content in raw pixels against the movie's mean position (mean zero over the frames);
@@ -164,12 +168,16 @@ class MovieReader(ingest.RawReader):
     def read_frame(self, f, path, start, nbytes, k):
         """-> (uint8 CUDA tensor with frame k's ny*nx samples, the first ``nbytes`` of the pinned slot as a NumPy view,
         valid until the slot is used again: two reads later)"""
+        return self.read_range(f, path, start + k * nbytes, nbytes, k, "of samples, the header promises")
+
+    def read_range(self, f, path, offset, nbytes, k, what="of strips, the directory of the frame promises"):
+        """``nbytes`` bytes of the file from ``offset`` on, frame k's -> as ``read_frame``"""
         slot = self._slot(nbytes)
-        f.seek(start + k * nbytes)
+        f.seek(offset)
         host = self._bufs[slot].numpy()[:nbytes]
         got = f.readinto(memoryview(host))
         if got != nbytes:
-            raise ValueError("%s: frame %d has %d bytes of samples, the header promises %d" % (path, k, got, nbytes))
+            raise ValueError("%s: frame %d has %d bytes %s %d" % (path, k, got, what, nbytes))
         raw = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         raw.copy_(self._bufs[slot][:nbytes], non_blocking=True)
         ev = torch.cuda.Event()
@@ -178,18 +186,45 @@ class MovieReader(ingest.RawReader):
         return raw, host
 
 
+TIFF_EXTS = (".tif", ".tiff")
+
+
+def is_tiff(path):
+    return os.path.splitext(path)[1].lower() in TIFF_EXTS
+
+
+def require_movie(path):
+    """a TIFF movie (``tiffio``), or what ``ingest.require_mrc`` lets pass"""
+    if not is_tiff(path):
+        ingest.require_mrc(path)
+
+
+def tiff_header(t):
+    """The MRC header a TIFF movie would have: its size, the mapped mode and, when the file states a pixel size, the cell
+    of that sampling; without one, the header of an MRC movie that states none."""
+    buf = io.BytesIO()
+    micrograph_io.write_mrc(buf, np.zeros((1, 1, 1), dtype=np.float32))
+    h = micrograph_io.MRCHeader._make(micrograph_io._HEADER.unpack(buf.getvalue()[:1024]))
+    h = h._replace(nx=t.nx, ny=t.ny, nz=t.frames, mode=t.mode, mx=t.nx, my=t.ny, mz=t.frames, xlen=0.0, ylen=0.0, zlen=0.0)
+    if t.apix is not None:
+        h = h._replace(xlen=float(np.float32(t.apix * t.nx)), ylen=float(np.float32(t.apix * t.ny)),
+                       zlen=float(np.float32(t.apix * t.frames)))
+    return h
+
+
 class Movie:
-    """An open movie: ``frame(k)`` -> the uint8 CUDA tensor of frame k's samples.  The frames stay on the device after
+    """An open MRC movie: ``frame(k)`` -> the uint8 CUDA tensor of frame k's samples.  The frames stay on the device after
     their first read when the whole movie is at most ``resident_bytes``; they are read again from the file otherwise.
-    ``anchor``: the first sample of frame 0 (0.0 for float32), known on the host without a device read."""
+    ``anchor``: the first sample of frame 0 (0.0 for float32), known on the host without a device read.
+    ``open_movie`` opens a path as this or, for a TIFF, as ``TiffMovie``, which differs in ``_open`` and ``_read`` only."""
 
     def __init__(self, path, device="cuda", resident_bytes=RESIDENT_BYTES):
-        ingest.require_mrc(path)
+        self._require(path)
         self.path = path
         self._reader = MovieReader(device)
         self._f = open(path, "rb")
         try:
-            self.header, self._start = read_movie_header(path, self._f)
+            self._open()
         except Exception:
             self._f.close()
             raise
@@ -198,14 +233,28 @@ class Movie:
         self.frame_bytes = h.ny * h.nx * self.dtype.itemsize
         self.resident = h.nz * self.frame_bytes <= resident_bytes
         self._frames = [None] * h.nz
+
+    @staticmethod
+    def _require(path):
+        ingest.require_mrc(path)
+
+    def _open(self):
+        self.header, self._start = read_movie_header(self.path, self._f)
         self.anchor = None
+
+    def _read(self, k):
+        raw, host = self._reader.read_frame(self._f, self.path, self._start, self.frame_bytes, k)
+        if k == 0 and self.anchor is None:
+            self.anchor = 0.0 if self.header.mode == 2 else float(host[:self.dtype.itemsize].view(self.dtype)[0])
+        return raw
+
+    def verify(self):
+        """Raises when frames read so far were damaged in a way only the device could see (``TiffMovie``); MRC: nothing."""
 
     def frame(self, k):
         if self._frames[k] is not None:
             return self._frames[k]
-        raw, host = self._reader.read_frame(self._f, self.path, self._start, self.frame_bytes, k)
-        if k == 0 and self.anchor is None:
-            self.anchor = 0.0 if self.header.mode == 2 else float(host[:self.dtype.itemsize].view(self.dtype)[0])
+        raw = self._read(k)
         if self.resident:
             self._frames[k] = raw
         return raw
@@ -219,6 +268,58 @@ class Movie:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class TiffMovie(Movie):
+    """An open TIFF movie (``.tif`` / ``.tiff``; ``tiffio``): ``tiff`` is its ``tiffio.TiffMovie``, ``header``
+    the MRC header it would have, and ``frame(k)`` uploads the frame's strips as they lie in the file and decodes them on
+    the device (``torch.ops.sprk.tiff_decode``) into the sample block an MRC frame is.  Residency counts decoded bytes.
+    ``verify()`` raises when a strip of the frames decoded so far did not decode."""
+
+    @staticmethod
+    def _require(path):
+        if not is_tiff(path):
+            raise ValueError("%s: not a TIFF movie (.tif / .tiff)" % path)
+
+    def _open(self):
+        from . import tiffio
+        t = self.tiff = tiffio.read_tiff_movie(self.path, self._f)
+        self.header = tiff_header(t)
+        self.anchor = 0.0 if t.mode == 2 else tiffio.first_sample(t, self._f)
+        # per frame: the byte range from the lowest strip offset to the highest strip end, and the strips within it
+        self._lo = [int(o.min()) for o in t.strip_offsets]
+        self._span = [int((o + n).max()) - lo for o, n, lo in zip(t.strip_offsets, t.strip_lengths, self._lo)]
+        tables = np.stack([np.stack([o - lo, n, tiffio.strip_bytes(t)]) for o, n, lo in
+                           zip(t.strip_offsets, t.strip_lengths, self._lo)])
+        self._tables = torch.from_numpy(tables).to(self._reader.device)                  # int64 [Z, 3, n_strips], once
+        self._status = torch.zeros((t.frames, len(t.strip_rows)), dtype=torch.int32, device=self._reader.device)
+        if len(t.strip_rows) == 1 and t.compression == tiffio.LZW:
+            logger.warning("%s: every frame is one LZW strip (the writer's RowsPerStrip is %d for %d rows): a strip is decoded "
+                           "by one wave, so each frame decodes serially; strips of 1 to 8 rows decode in parallel",
+                           self.path, t.rows_per_strip, t.ny)
+
+    def _read(self, k):
+        t = self.tiff
+        src, _ = self._reader.read_range(self._f, self.path, self._lo[k], max(self._span[k], 1), k)
+        out = torch.empty(self.frame_bytes, dtype=torch.uint8, device=self._reader.device)
+        off, length, size = self._tables[k]
+        torch.ops.sprk.tiff_decode(src, off, length, size, t.compression, t.widen, out, self._status[k])
+        return out
+
+    def verify(self):
+        """Raises ValueError naming the first strip of the frames decoded so far whose stream was damaged."""
+        bad = torch.nonzero(self._status).cpu().numpy()
+        if len(bad):
+            k, s = (int(v) for v in bad[0])
+            why = {1: "holds a code that is not in the table", 2: "ends before the strip's rows are complete",
+                   3: "decodes to more bytes than the strip's rows hold"}[int(self._status[k, s])]
+            raise ValueError("%s: frame %d, strip %d: the LZW stream %s (%d strip(s) of the movie are damaged): the file is "
+                             "corrupt, copy or write it again" % (self.path, k, s, why, len(bad)))
+
+
+def open_movie(path, device="cuda", resident_bytes=RESIDENT_BYTES):
+    """By extension: ``.tif`` / ``.tiff`` (any case) a ``TiffMovie``, everything else what ``Movie`` makes of it"""
+    return (TiffMovie if is_tiff(path) else Movie)(path, device, resident_bytes)
 
 
 def sum_frames(movie, by, bx, shifts_y, shifts_x):
@@ -288,7 +389,8 @@ def align_movie(path, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_shift=DEFAULT_
     weighting = _dose_args(dose, pre_dose, kv, apix)
     if references is None:
         references = _references(gain, gain_rot, gain_flip, dark, defects, hot_sigma)
-    with Movie(path, device, resident_bytes) as movie:
+    with open_movie(path, device, resident_bytes) as movie:
+        source = movie
         h = movie.header
         fixed = None
         if references is not None and references.active:
@@ -348,6 +450,7 @@ def align_movie(path, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_shift=DEFAULT_
             sy, sx = summed.shifts_y, summed.shifts_x
         if fixed is not None:
             info = dict(info, defects=fixed)
+        source.verify()
     return total, np.stack([0.0 - sx, 0.0 - sy], axis=1), h, info             # 0.0 - x: no "-0.0000" in the table
 
 
@@ -395,7 +498,7 @@ def align_dataset(movies, out_dir, ftbin=1, align_size=DEFAULT_ALIGN_SIZE, max_s
     if not rows:
         raise ValueError("no movies found in %s" % movies)
     for _, _, path in rows:
-        ingest.require_mrc(path)
+        require_movie(path)
     os.makedirs(out_dir, exist_ok=True)
     results, lines, lines_dw = {}, ["image_name\tpath"], ["image_name\tpath"]
     for _, name, path in rows:

@@ -304,13 +304,18 @@ def build_parser():
                "before it is summed; {name}_local.txt reports it.  With --dose also a dose-weighted sum per movie, "
                "{name}_DW.mrc: give the plain sums (images.txt) to `joint ctf`, the weighted ones (images_DW.txt) to `joint "
                "eval` / `joint extract`, and pass those tables, not the directory, which then holds both.  Not covered: "
-               "local motion finer than the one smooth field of --patch (per-particle polishing), TIFF and EER input, and "
-               "references meant to be divided by.")
+               "local motion finer than the one smooth field of --patch (per-particle polishing), EER input, TIFF that is "
+               "tiled, uses a predictor or another compression than LZW, and references meant to be divided by.")
     al = cmds.add_parser("align", help=al_help, description=al_help)
     al.add_argument("--movies", "-d", required=True, metavar="T",
                     help="Table (image_name, path) or directory of MRC movie stacks (modes 0 / 1 / 2 / 6, at least 2 frames, "
                          "at most 16384 pixels a side; gain-corrected, or raw together with --gain / --dark / --defects / "
-                         "--hot_sigma).")
+                         "--hot_sigma).  A movie may also be a multi-page TIFF (.tif / .tiff; a directory is searched for "
+                         ".tiff, a table names either), as SerialEM and EPU write them: little-endian classic or BigTIFF, one "
+                         "frame per directory, in strips, stored or LZW without a predictor, uint8 / int8 / uint16 / int16 / "
+                         "float32; the strips are decoded on the GPU, and both kinds may stand in one table.  Row r of the "
+                         "TIFF is row r of the frame; IMOD shows TIFF flipped in Y against MRC, so a gain reference that "
+                         "IMOD converted to MRC needs --gain_flip ud.  --gain, --dark and --defects stay MRC and text.")
     al.add_argument("--out", "-o", required=True,
                     help="Directory for {name}.mrc (the aligned sum, float32), {name}_shifts.txt (frame, dx, dy in raw pixels, "
                          "mean zero) and images.txt.")

@@ -1001,6 +1001,53 @@ def _align_warp_fake(src, cy, cx, y, first):
 _register("align_warp", "(Tensor src, float[] cy, float[] cx, Tensor(a!) y, bool first) -> ()", _align_warp, _align_warp_fake)
 
 
+# TIFF movies in (tiffio.py, align.TiffMovie: csrc/tiff.hip): the strips of one frame decoded, one wave per strip
+TIFF_MAX_STRIPS = 1 << 20
+TIFF_COMPRESSIONS = (1, 5)                       # stored, LZW
+
+
+def _tiff_decode_check(src, strip_off, strip_len, strip_out, compression, widen, out, status):
+    if src.dtype != torch.uint8 or src.dim() != 1 or src.numel() < 1:
+        raise _lib.SprkError("tiff_decode: src must be uint8 [nbytes >= 1], got %s %s" % (src.dtype, tuple(src.shape)))
+    n = strip_off.numel()
+    if not 1 <= n <= TIFF_MAX_STRIPS:
+        raise _lib.SprkError("tiff_decode: %d strips (1..%d)" % (n, TIFF_MAX_STRIPS))
+    for name, t in (("strip_off", strip_off), ("strip_len", strip_len), ("strip_out", strip_out)):
+        if t.dtype != torch.int64 or tuple(t.shape) != (n,) or t.device != src.device:
+            raise _lib.SprkError("tiff_decode: %s must be int64 [%d] on %s, got %s %s on %s"
+                                 % (name, n, src.device, t.dtype, tuple(t.shape), t.device))
+    if compression not in TIFF_COMPRESSIONS:
+        raise _lib.SprkError("tiff_decode: compression %d (1: stored, 5: LZW)" % compression)
+    if out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < (2 if widen else 1) or out.device != src.device \
+            or (widen and out.numel() % 2):
+        raise _lib.SprkError("tiff_decode: out must be uint8 [decoded bytes%s] on %s, got %s %s on %s"
+                             % (" x 2" if widen else "", src.device, out.dtype, tuple(out.shape), out.device))
+    if status.dtype != torch.int32 or tuple(status.shape) != (n,) or status.device != src.device:
+        raise _lib.SprkError("tiff_decode: status must be int32 [%d] on %s, got %s %s on %s"
+                             % (n, src.device, status.dtype, tuple(status.shape), status.device))
+    return n, out.numel() // (2 if widen else 1)
+
+
+def _tiff_decode(src, strip_off, strip_len, strip_out, compression, widen, out, status):
+    """src: uint8 CUDA [nbytes], a frame's strips as they lie in the file; strip_off, strip_len, strip_out: int64 [n_strips]
+    (offset into src, bytes, decoded bytes to yield); compression 1 (stored) or 5 (LZW); widen: every decoded byte becomes
+    one little-endian uint16; out: uint8 [sum of strip_out (x 2 with widen)], the sample block; status int32 [n_strips]:
+    0 ok, 1 bad code, 2 input ran out, 3 a string past the strip's end (sprk_tiff_decode)."""
+    n, out_elems = _tiff_decode_check(src, strip_off, strip_len, strip_out, compression, widen, out, status)
+    if not all(t.is_contiguous() for t in (src, strip_off, strip_len, strip_out, out, status)):
+        raise _lib.SprkError("tiff_decode: src, the strip tables, out and status must be contiguous")
+    check(_lib.lib().sprk_tiff_decode(_p(src), src.numel(), _p(strip_off), _p(strip_len), _p(strip_out), n, int(compression),
+                                      1 if widen else 0, _p(out), out_elems, _p(status), _stream(src)), "sprk_tiff_decode")
+
+
+def _tiff_decode_fake(src, strip_off, strip_len, strip_out, compression, widen, out, status):
+    _tiff_decode_check(src, strip_off, strip_len, strip_out, compression, widen, out, status)
+
+
+_register("tiff_decode", "(Tensor src, Tensor strip_off, Tensor strip_len, Tensor strip_out, int compression, bool widen, "
+          "Tensor(a!) out, Tensor(b!) status) -> ()", _tiff_decode, _tiff_decode_fake)
+
+
 # ---- reference-free 2-D classification (class2d.py: csrc/class2d.hip) ----------------------------------------------------------
 CLASS_MAX_SIDE = 128                             # sprk_class_transform / _average: S even, at most this
 CLASS_MAX_ANGLES = 720                           # rows of the cos / sin table at most
